@@ -12,12 +12,21 @@ All inputs are resident in HBM before the timed region.  With N > 1 every rank o
 environments (weak scaling, envs shard with no data-path collective; the one exchange per optimiser
 step is the flat-gradient all-reduce).
 
-Prints ONE JSON line on rank 0.  ``roofline`` is measured live: every launch of the dominant
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps, writes the last timed step's outputs
+when --dump-outputs DIR is given, and prints the line (``ms_per_step`` = wall-clock milliseconds of one timed step).  The
+diagnostics below take extra GPU / host time and run only with --full.
+
+--full: ``roofline`` is measured live: every launch of the dominant
 kernel (gemm_x3_kernel: the fp32 GEMM computed as six bf16 MFMAs per k step over an exact three-way operand split; or
 gemm_f32_kernel, the fp32 MFMA GEMM, with PULSE_GEMM_F32=mfma32) inside the LAST step of the timed region is bracketed by
 a HIP event pair on the launch stream; achieved = algorithmic FLOPs / summed kernel time.  ``cpu_baseline`` is
 the PyTorch-CPU oracle agent (oracle/agent_oracle.py, kind "port") timed on the host cores on a
 bounded sample of the same workload (rank 0, N=1 only).
+
+--dump-outputs DIR: after the timed region, what the last timed ``train_epoch()`` returned (its per-minibatch loss / statistics
+tensors, stacked) and the parameters it left behind (every flat buffer the optimiser owns) are written as DIR/<name>.npy (float32,
+or float64 for the statistics); a buffer larger than the per-array cap is replaced by a fixed, seeded sample of its elements.
+Inputs and initial weights are seeded, so two runs (or two builds) with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -56,7 +65,50 @@ def parse():
     ap.add_argument("--keep-gc", action="store_true", help="leave Python's cyclic garbage collector running during the timed region")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every rank owns the config's env count; strong: the config's env count is divided over the ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the diagnostics: live GEMM roofline, sustained-clock probe, CPU-oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
     return ap.parse_args()
+
+
+DUMP_CAP_BYTES = 64 << 20          # all arrays of one --dump-outputs together
+DUMP_ARRAY_CAP = 4 << 20           # elements of one parameter array before it is sampled (16 MB of float32)
+
+
+def dump_outputs(agent, info, out_dir):
+    """Write what the last timed step computed: the per-minibatch statistics train_epoch() returned (stacked, float64) and every
+    flat parameter buffer the optimiser owns (float32; a fixed, seeded sample of DUMP_ARRAY_CAP elements of a larger one)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for k in sorted(info):
+        if k.endswith("_time"):
+            continue                                              # wall-clock timings, not computed values
+        v = info[k]
+        if isinstance(v, (list, tuple)) and v and all(isinstance(x, torch.Tensor) for x in v):
+            parts = [x.detach().reshape(-1) for x in v]
+            same = len({p.numel() for p in parts}) == 1 and parts[0].numel() > 1
+            v = torch.stack(parts) if same else torch.cat(parts)
+        elif isinstance(v, (list, tuple)) and v and all(isinstance(x, (int, float)) for x in v):
+            v = torch.tensor(v, dtype=torch.float64)
+        if isinstance(v, torch.Tensor) and v.is_floating_point():
+            arrays["train_" + k] = v.detach().to("cpu", torch.float64).numpy()
+    for i, g in enumerate(agent._param_groups()):
+        flat = g[0][:g[4]].detach()
+        name = "params" if i == 0 else f"params_{i}"
+        if flat.numel() > DUMP_ARRAY_CAP:
+            gen = torch.Generator().manual_seed(20240 + i)              # the same elements in every run of the same config
+            idx = torch.randperm(flat.numel(), generator=gen)[:DUMP_ARRAY_CAP].sort().values
+            name += "_sample"
+            flat = flat[idx.to(flat.device)]
+        arrays[name] = flat.to("cpu", torch.float32).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_CAP_BYTES, f"--dump-outputs would write {total} bytes"
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    log(f"wrote {len(arrays)} arrays ({total / 1e6:.1f} MB) to {out_dir}")
 
 
 def cpu_baseline_worker(cfg_name, seed, sample_steps, n_minibatches, reference="motion_lib"):
@@ -287,6 +339,8 @@ def main():
     if a.cpu_baseline_worker:
         print(json.dumps(cpu_baseline_worker(a.config, 1234, a.cpu_steps, a.cpu_minibatches, a.reference)), flush=True)
         return
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit(f"bench.py: --steps {a.steps} --warmup {a.warmup}: at least one timed step, no negative warm-up")
     plan = launch_plan(a.gpus, os.environ)
     if plan["action"] == "refuse":
         raise SystemExit("bench.py: " + plan["why"])
@@ -310,6 +364,10 @@ def main():
     device = f"cuda:{local_rank}"
     dist = DistContext(enabled=world > 1)
     seed = 1234
+    # torch seeds its default generators from the OS at start-up: the network's initial weights (drawn from the default CPU generator)
+    # and every other unseeded draw would differ from run to run.  One fixed seed, the same on every rank, makes two runs with the
+    # same arguments compute the same thing.
+    torch.manual_seed(seed)
     cfg, num_envs = configs.agent_config(a.config)
     T = cfg["horizon_length"]
     over = {}
@@ -349,7 +407,7 @@ def main():
     play = upd = 0.0
     per_step = []
     for step in range(a.steps):
-        if step == a.steps - 1 and not a.no_roofline:
+        if step == a.steps - 1 and a.full and not a.no_roofline:
             prof.start()      # the LAST timed step carries the HIP-event brackets (an event pair costs ~10 us of stream time per GEMM)
         info = agent.train_epoch()
         play += info["play_time"]
@@ -361,6 +419,8 @@ def main():
     prof.stop()
     elapsed = dist.max_over_ranks(elapsed)
     log(f"rank {rank}: timed region done: {elapsed:.3f} s")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(agent, info, a.dump_outputs)
 
     env_steps = a.steps * T * num_envs * world
     out = {
@@ -395,7 +455,7 @@ def main():
                             "ms_per_step_host_enqueue": 1e3 * st["seconds"] / max(1, a.steps + a.warmup),
                             # device-side: how long the optimiser's stream actually waited for gradient buckets (what the overlap did not hide)
                             "ms_per_step_exposed_wait_device": exp_ms / max(1, a.steps), "waits_timed": exp_n}
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         s = prof.summary()
 
         def roof(tags, peak, kernel, traffic_key=None):
@@ -471,7 +531,7 @@ def main():
                 r["clock_probe_tile"] = getattr(gemm_clock_probe, "tile", None)     # rows of the tile the probe's launches ran on (256 = gemm_x3w_kernel)
                 r["clock_note"] = ("peak is quoted at 2.4 GHz; sustained_clock_ghz is the shader clock measured (per-workgroup s_memtime vs wall stamps) "
                                    "under 30 back-to-back launches of this config's layer-1 forward GEMM right after the timed region")
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         log("timing the CPU oracle (subprocess, bounded)")
         out["cpu_baseline"] = cpu_baseline(a.config, seed, a.cpu_steps, a.cpu_minibatches, a.cpu_budget, a.reference)
         if out["cpu_baseline"]["value"]:

@@ -19,7 +19,7 @@ def _run(args, extra_env, timeout=600):
 
 
 def test_bench_self_launches_two_ranks():
-    p = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-clock-probe"],
+    p = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-clock-probe"],
              {"PULSE_BENCH_SHARE_GPU": "1", "PULSE_DIST_BACKEND": "gloo"})
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

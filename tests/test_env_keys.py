@@ -1,7 +1,7 @@
 """CPU: no env option the reference reads on this path can be dropped silently (pulse_amd/env/env_keys.py).
 
-  * when /root/reference is mounted: the set of ``cfg["env"]`` keys read by the reference's task classes is re-derived from its sources
-    and every one of them must be classified (HONOURED / INERT / UNBUILT);
+  * the set of ``cfg["env"]`` keys read by the reference's task classes (re-derived from its sources where the reference checkout is
+    present, the recorded set elsewhere: oracle/refrecord.py) -- every one of them must be classified (HONOURED / INERT / UNBUILT);
   * every key classified HONOURED is actually read somewhere in pulse_amd/env or pulse_amd/learning;
   * every shipped phc/data/cfg/env/*.yaml either passes the audit or raises NotImplementedError naming the offending key -- the expected
     outcome per file is written down below;
@@ -16,15 +16,13 @@ import pytest
 import yaml
 
 from oracle import refload
+from oracle.refrecord import RefRecord
 from pulse_amd.env import env_keys as K
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TASK_FILES = ["humanoid.py", "humanoid_amp.py", "humanoid_amp_task.py", "humanoid_im.py", "humanoid_z.py", "humanoid_im_getup.py", "humanoid_im_distill.py",
               "humanoid_im_distill_getup.py", "base_task.py", "humanoid_speed.py", "humanoid_reach.py", "humanoid_strike.py", "humanoid_traj.py",
               "humanoid_pedestrian_terrain.py", "vec_task.py", "vec_task_wrappers.py"]
-needs_reference = pytest.mark.skipif(not refload.available(), reason="reference checkout not mounted")
-
-
 def _reference_keys():
     pat = re.compile(r"""cfg\[['"]env['"]\](?:\.get\(|\[)['"]([A-Za-z_0-9]+)['"]""")
     keys = set()
@@ -39,9 +37,9 @@ def _reference_keys():
     return keys
 
 
-@needs_reference
-def test_every_key_the_reference_reads_is_classified():
-    keys = _reference_keys()
+def test_every_key_the_reference_reads_is_classified(request):
+    with RefRecord(request) as R:
+        keys = set(R.obj("keys", lambda: sorted(_reference_keys())))
     assert len(keys) > 120, "the source scan found implausibly few keys"
     missing = sorted(keys - K.ALL_KNOWN)
     assert not missing, f"env keys read by the reference but not classified in env_keys.py: {missing}"
@@ -71,16 +69,22 @@ EXPECTED = {
 }
 
 
-@needs_reference
-def test_yaml_walk_every_shipped_env_config_constructs_or_raises_by_name():
-    files = sorted(glob.glob(os.path.join(refload.REFERENCE_ROOT, "phc", "data", "cfg", "env", "*.yaml")))
-    assert {os.path.basename(f) for f in files} == set(EXPECTED), "a shipped env config is not covered by the walk"
-    zof = []
-    for f in files:
+def _shipped_env_configs():
+    out = {}
+    for f in sorted(glob.glob(os.path.join(refload.REFERENCE_ROOT, "phc", "data", "cfg", "env", "*.yaml"))):
         with open(f) as fh:
             d = yaml.safe_load(fh)
-        env = d["env"] if isinstance(d.get("env"), dict) else d                # legacy files nest their options under env:
-        name = os.path.basename(f)
+        out[os.path.basename(f)] = d["env"] if isinstance(d.get("env"), dict) else d      # legacy files nest their options under env:
+    return out
+
+
+def test_yaml_walk_every_shipped_env_config_constructs_or_raises_by_name(request):
+    R = RefRecord(request)
+    configs = R.obj("env_configs", _shipped_env_configs)
+    assert set(configs) == set(EXPECTED), "a shipped env config is not covered by the walk"
+    zof = []
+    for name in sorted(configs):
+        env = configs[name]
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")                                   # (unread legacy spellings are reported as warnings)
             if EXPECTED[name] is None:
@@ -92,6 +96,7 @@ def test_yaml_walk_every_shipped_env_config_constructs_or_raises_by_name():
             zof.append(name)
     # the five configs round 5 silently mis-computed
     assert zof == ["env_im_getup_mcp.yaml", "phc_kp_mcp_iccv.yaml", "phc_kp_pnn_iccv.yaml", "phc_shape_mcp_iccv.yaml", "phc_shape_pnn_iccv.yaml"]
+    R.close()
 
 
 @pytest.mark.parametrize("key", sorted(K.UNBUILT))

@@ -1,6 +1,6 @@
 """CPU: the device ReplayBuffer (pulse_amd/learning/amp_agent.py) draws the same rows as the reference's
-phc/learning/replay_buffer.py -- via the oracle restatement everywhere, and via the reference class itself when
-/root/reference is mounted (this container only)."""
+phc/learning/replay_buffer.py -- via the oracle restatement, and via the reference class itself (run where the reference
+checkout is present, replayed from its recorded draws elsewhere: oracle/refrecord.py)."""
 import importlib.util
 import os
 
@@ -8,9 +8,42 @@ import pytest
 import torch
 
 from oracle import agent_oracle as AO
+from oracle import refload
+from oracle.refrecord import RefRecord
 from pulse_amd.learning.amp_agent import ReplayBuffer
 
-REF = "/root/reference/phc/learning/replay_buffer.py"
+REF = os.path.join(refload.REFERENCE_ROOT, "phc", "learning", "replay_buffer.py")
+
+
+class _Recorded:
+    """The reference ReplayBuffer seen through a RefRecord: every sample (rows and the RNG state it leaves) and every count is
+    recorded when the reference class runs, and replayed in the same order when it does not."""
+
+    def __init__(self, R, tag, make):
+        self.R, self.tag, self.i = R, tag, 0
+        self.buf = make() if R.live else None
+
+    def _key(self, what):
+        self.i += 1
+        return f"{self.tag}/{self.i}/{what}"
+
+    def store(self, d):
+        if self.buf is not None:
+            self.buf.store(d)
+
+    def sample(self, n):
+        if self.buf is not None:
+            d = self.buf.sample(n)
+            self.R.obj(self._key("keys"), lambda: sorted(d))
+            out = {k: self.R.t(self._key("rows/" + k), lambda: d[k]) for k in sorted(d)}
+        else:
+            out = {k: self.R.t(self._key("rows/" + k), lambda: None) for k in self.R.obj(self._key("keys"), lambda: None)}
+        torch.set_rng_state(self.R.t(self._key("rng"), torch.get_rng_state))
+        return out
+
+    def get_total_count(self):
+        b = self.buf
+        return self.R.obj(self._key("count"), lambda: b.get_total_count() if hasattr(b, "get_total_count") else b.total)
 
 
 def _drive(make_ref, size, width, script, seed):
@@ -46,16 +79,18 @@ def test_replay_buffer_matches_oracle(seed):
     _drive(lambda size: AO.OracleReplayBuffer(size), 128, 12, SCRIPT, seed)
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference checkout not mounted")
 @pytest.mark.parametrize("seed", [0, 5])
-def test_oracle_and_device_buffer_match_reference_class(seed):
-    spec = importlib.util.spec_from_file_location("_ref_replay_buffer", REF)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    _drive(lambda size: mod.ReplayBuffer(size, "cpu"), 128, 12, SCRIPT, seed)
+def test_oracle_and_device_buffer_match_reference_class(request, seed):
+    R = RefRecord(request)
+    mod = None
+    if R.live:
+        spec = importlib.util.spec_from_file_location("_ref_replay_buffer", REF)
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+    _drive(lambda size: _Recorded(R, "drive", lambda: mod.ReplayBuffer(size, "cpu")), 128, 12, SCRIPT, seed)
     # and the oracle itself against the reference class
     torch.manual_seed(seed)
-    ref = mod.ReplayBuffer(64, "cpu")
+    ref = _Recorded(R, "oracle", lambda: mod.ReplayBuffer(64, "cpu"))
     torch.manual_seed(seed)
     orc = AO.OracleReplayBuffer(64)
     g = torch.Generator().manual_seed(3)
@@ -68,3 +103,4 @@ def test_oracle_and_device_buffer_match_reference_class(seed):
         torch.set_rng_state(s)
         b = orc.sample(n_sample)["x"]
         assert torch.equal(a, b)
+    R.close()

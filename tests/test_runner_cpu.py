@@ -1,13 +1,16 @@
 """CPU: the rl_games plugin seam (phc/run_hydra.py:246-268) -- factories, builder names, config resolution -- without a GPU.
-Where the reference tree is present (build container) the learner config dict is checked key-for-key against the reference's own
-learning/im.yaml, so the config surface the runner accepts is the reference's."""
+The learner config dict is checked key-for-key against the reference's own learning/im.yaml (read where the reference checkout is
+present, its recorded parameters elsewhere: oracle/refrecord.py), so the config surface the runner accepts is the reference's."""
 import os
 
 import pytest
 
 from pulse_amd import configs, runner as R
 
-REF_YAML = "/root/reference/phc/data/cfg/learning/im.yaml"
+from oracle import refload
+from oracle.refrecord import RefRecord
+
+REF_YAML = os.path.join(refload.REFERENCE_ROOT, "phc", "data", "cfg", "learning", "im.yaml")
 
 
 def im_params():
@@ -42,11 +45,15 @@ def test_env_registry():
         R.create_vec_env("nope", 1)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_YAML), reason="reference tree not present")
-def test_config_surface_matches_reference_yaml():
+def _reference_im_params():
     import yaml
     with open(REF_YAML) as f:
-        ref = yaml.safe_load(f)["params"]
+        return yaml.safe_load(f)["params"]
+
+
+def test_config_surface_matches_reference_yaml(request):
+    with RefRecord(request) as RR:
+        ref = RR.obj("im_yaml_params", _reference_im_params)
     mine = im_params()["params"]
     assert mine["algo"]["name"] == ref["algo"]["name"] == "im_amp"
     assert mine["network"]["mlp"]["units"] == ref["network"]["mlp"]["units"] and mine["network"]["disc"]["units"] == ref["network"]["disc"]["units"]

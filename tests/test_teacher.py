@@ -9,6 +9,7 @@ import torch
 
 from oracle import agent_oracle as AO
 from oracle import refload
+from oracle.refrecord import RefRecord
 
 
 def synthetic_teacher_checkpoints(num_prim=3, in_dim=934, units=(96, 64), comp_units=(80, 48), seed=0, has_lateral=False):
@@ -36,24 +37,26 @@ def synthetic_teacher_checkpoints(num_prim=3, in_dim=934, units=(96, 64), comp_u
     return {"model": pm, "running_mean_std": rms}, {"model": cm}
 
 
-@pytest.mark.skipif(not refload.available(), reason="reference checkout not mounted")
 @pytest.mark.parametrize("activation", ["silu", "relu"])
 @pytest.mark.parametrize("has_lateral", [False, True])
-def test_oracle_teacher_matches_reference_loaders_and_pnn(activation, has_lateral):
-    ref = refload.pnn_reference()
+def test_oracle_teacher_matches_reference_loaders_and_pnn(request, activation, has_lateral):
     pck, cck = synthetic_teacher_checkpoints(seed=3, has_lateral=has_lateral)
-    pnn = ref["load_pnn"](pck, num_prim=3, has_lateral=has_lateral, activation=activation, device="cpu")
-    composer = ref["load_mcp_mlp"](cck, activation=activation, device="cpu", mlp_name="composer")
     obs = torch.randn(40, 934, generator=torch.Generator().manual_seed(1)) * 2
     rm, rv = pck["running_mean_std"]["running_mean"], pck["running_mean_std"]["running_var"]
-    with torch.no_grad():                                                  # humanoid_im_distill.py:165-198 with identical teacher / student obs
-        full_obs = torch.clamp((obs - rm.float()) / torch.sqrt(rv.float() + 1e-05), min=-5.0, max=5.0)
-        _, pnn_actions = pnn(full_obs)
-        x_all = torch.stack(pnn_actions, dim=1)
-        weights = composer(full_obs)
-        want = torch.sum(weights[:, :, None] * x_all, dim=1)
+
+    def want():
+        ref = refload.pnn_reference()
+        pnn = ref["load_pnn"](pck, num_prim=3, has_lateral=has_lateral, activation=activation, device="cpu")
+        composer = ref["load_mcp_mlp"](cck, activation=activation, device="cpu", mlp_name="composer")
+        with torch.no_grad():                                              # humanoid_im_distill.py:165-198 with identical teacher / student obs
+            full_obs = torch.clamp((obs - rm.float()) / torch.sqrt(rv.float() + 1e-05), min=-5.0, max=5.0)
+            _, pnn_actions = pnn(full_obs)
+            x_all = torch.stack(pnn_actions, dim=1)
+            weights = composer(full_obs)
+            return torch.sum(weights[:, :, None] * x_all, dim=1)
     got = AO.oracle_pnn_teacher_action(pck["model"], cck["model"], 3, activation, obs, rm, rv, has_lateral=has_lateral)
-    assert torch.equal(got, want)
+    with RefRecord(request) as R:
+        assert R.equal(got, R.t("action", want))
 
 
 @pytest.mark.gpu
