@@ -198,8 +198,10 @@ __device__ __forceinline__ void xp_epilogue(const XpArgs& g, f32x16 (&acc)[2][2]
                     }
                 }
                 if (g.colsum) {
+                    // the sums of the output AS STORED: a single-plane Cp holds the bf16 rounding of o (a no-op for the rounded product itself and
+                    // its ReLU / mask forms; the SiLU-derivative epilogue's products are not bf16 values -- they were summed unrounded before)
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) cs[k] += o[k];
+                    for (int k = 0; k < 8; ++k) cs[k] += (NPL == 1 && Cp) ? (float)(__bf16)o[k] : o[k];
                 }
                 if (C) {
                     float* pc = C + (long long)row * g.ldc + col;
