@@ -247,7 +247,7 @@ __global__ void __launch_bounds__(256) reduce_grads_kernel(const float* __restri
         const int ns = rg.nslabs[r];
         const long long n4 = rg.count[r] >> 2;                          // offsets / counts are multiples of 4 floats (checked by the launcher)
         for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-            // the SAME association as reduce_slabs_kernel (gemm_f32.hip): slab 0 + four chains over the groups of four, remainder onto chain 0,
+            // the SAME association as reduce_slabs_kernel (gemm_api.hip): slab 0 + four chains over the groups of four, remainder onto chain 0,
             // ((c0 + c1) + (c2 + c3)) -- a gradient reduced by either kernel is bit-identical (the data-parallel path reduces bucket by bucket
             // with pulse_reduce_slabs, the single-GPU path with this kernel)
             float4 a1 = make_float4(0.f, 0.f, 0.f, 0.f), a2 = a1, a3 = a1;

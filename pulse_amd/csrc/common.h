@@ -25,6 +25,21 @@ inline int check_launch(const char* what) {
 
 inline hipStream_t as_stream(pulse_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Launch ``Kernel`` with ``lds`` bytes of dynamic LDS.  Requests above 64 KiB need a per-function opt-in: hipFuncSetAttribute is called only when
+// the size differs from the one last granted to THIS instantiation (never per launch: the call serialises the host against the stream).  A refused
+// opt-in is returned without a launch: the caller reports it, or falls back to another tiling (and clears hipGetLastError()).
+template <auto Kernel, typename Args>
+hipError_t launch_dyn_lds(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args& args) {
+    static size_t granted = 0;
+    if (granted != lds) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        granted = lds;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args);
+    return hipSuccess;
+}
+
 constexpr int kWave = 64;  // gfx950 wavefront
 
 // ---- the exact three-way bf16 split of fp32 values (gemm_x3 / gemm_x3p arithmetic): x = p0 + p1 + p2, p0 = bf16(x), p1 = bf16(x - p0),
@@ -78,8 +93,8 @@ __device__ __forceinline__ WgMap map_workgroup(int ntile, int batch, int splitk)
     return WgMap{id, z / splitk, z % splitk};
 }
 
-long long* gemm_debug_buffer();  // the calling thread's pulse_gemm_set_debug_buffer pointer (gemm_f32.hip)
-int gemm_option(int key);        // the calling thread's pulse_gemm_set_option value (gemm_f32.hip)
+long long* gemm_debug_buffer();  // the calling thread's pulse_gemm_set_debug_buffer pointer (gemm_api.hip)
+int gemm_option(int key);        // the calling thread's pulse_gemm_set_option value (gemm_api.hip)
 
 }  // namespace pulse
 

@@ -654,13 +654,9 @@ int pulse_im_step(const pulse_im_step_args* args, pulse_stream_t s) {
     const unsigned grid = (unsigned)((count + E - 1) / E);
     // a whole wave per env when both halves have work (task observation beside self observation / reward / reset): see the kernel's note
     const bool two = (a.what & PULSE_IM_TASK_OBS) && (a.what & (PULSE_IM_SELF_OBS | PULSE_IM_REWARD | PULSE_IM_RESET)) && g_im_two_roles;
-    const void* fn = two ? reinterpret_cast<const void*>(im_step_kernel<E, 2>) : reinterpret_cast<const void*>(im_step_kernel<E, 1>);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(PULSE_ERR_LAUNCH, "pulse_im_step: cannot raise LDS limit: %s", hipGetErrorString(e));
-    }
-    if (two) hipLaunchKernelGGL((im_step_kernel<E, 2>), dim3(grid), dim3(E * 2 * kLanesPerEnv), lds, as_stream(s), a);
-    else hipLaunchKernelGGL((im_step_kernel<E, 1>), dim3(grid), dim3(E * kLanesPerEnv), lds, as_stream(s), a);
+    const hipError_t e = two ? launch_dyn_lds<im_step_kernel<E, 2>>(dim3(grid), dim3(E * 2 * kLanesPerEnv), lds, as_stream(s), a)
+                             : launch_dyn_lds<im_step_kernel<E, 1>>(dim3(grid), dim3(E * kLanesPerEnv), lds, as_stream(s), a);
+    if (e != hipSuccess) return fail(PULSE_ERR_LAUNCH, "pulse_im_step: cannot raise LDS limit: %s", hipGetErrorString(e));
     return check_launch("pulse_im_step");
 }
 }

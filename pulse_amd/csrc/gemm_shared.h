@@ -1,5 +1,6 @@
-// Pieces shared by the fp32-storage GEMM translation units (gemm_f32.hip: fp32 MFMA, bf16 MFMA over fp32 storage, the 128 x 128 x3 kernel;
-// gemm_x3w.hip: the 256 x 256 x3 kernel): the launch argument block, the LDS slot permutation, raw-buffer and LDS access helpers.
+// Pieces shared by the fp32-storage GEMM translation units (gemm_f32.hip: fp32 MFMA, bf16 MFMA over fp32 storage; gemm_x3.hip: the 128 x 128 x3
+// kernel; gemm_x3w.hip: the 256 x 256 x3 kernel; gemm_x3s.hip: the skinny-N x3 kernel; gemm_api.hip: pulse_gemm_f32, which chooses between them):
+// the launch argument block, the tile constants, the LDS slot permutation, raw-buffer and LDS access helpers, the launchers each unit exports.
 #pragma once
 #include "common.h"
 
@@ -18,8 +19,8 @@ struct GemmArgs {
     long long sA, sB, sC, sC2, sBias, sAux;   // batch strides (floats)
     int batch, splitk, kchunk;
     long long sSplit;                          // C slab stride per k-split (floats)
-    int act;                                   // 0 none, 1 relu, 2 silu (EPI 0 only)
-    int epi;                                   // 0 bias+act, 1 relu-grad mask, 2 silu-grad
+    int act;                                   // EPI 0 only: 0 none, 1 relu, 2 silu (C2, if given, keeps the pre-activation), 3 silu with d silu / d z into C2
+    int epi;                                   // 0 bias + act, 1 relu-grad (aux > 0, or the bit mask), 2 silu-grad (aux = pre-activation), 3 multiply by aux
     int tiles_m, tiles_n;
     int vec_epi;                               // all epilogue pointers / pitches are 16-byte aligned
     float* rowsum; long long sRowsum;          // <MC,MC> only: per-slab sums over k of A(k, m)  (bias gradient)
@@ -30,6 +31,10 @@ struct GemmArgs {
 
 // word of the ReLU bit mask that holds output row r (within its 64-row block: rows r, r + 8, .., r + 56 share a word), column group cg = col / 4
 __device__ __forceinline__ long long mask_word(int r, int cg, int ldmask) { return (long long)((r >> 6) * 8 + (r & 7)) * ldmask + cg; }
+
+constexpr int BM = 128, BN = 128;                    // output tile of the 128-row kernels (the 64-row x3 tile: 64 x BN)
+constexpr int BK = 32, BK16 = 64, XK = 16;           // k-tile depth: fp32 MFMA, bf16 MFMA, x3 (split-K chunks are whole k-tiles)
+constexpr int CP = BN;                               // epilogue image pitch of the 128-row kernels (floats): 128 x 128 x 4 B = 65,536 B
 
 // launch_gemm_x3w's answer when the device refuses the 256 x 256 tile's dynamic-LDS request: not an error, the launcher falls back (internal code)
 constexpr int kWideTileUnavailable = -1000;
@@ -62,8 +67,21 @@ __device__ __forceinline__ unsigned pack_rn(float lo_elem, float hi_elem) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){lo_elem, hi_elem}, bf16x2));
 }
 
+// what a launcher returns after launch_dyn_lds (common.h) when a refused LDS request is an error
+inline int lds_launch_status(hipError_t e, const char* what) {
+    if (e != hipSuccess) return fail(PULSE_ERR_LAUNCH, "%s: LDS attribute: %s", what, hipGetErrorString(e));
+    return check_launch(what);
+}
+
+// The launchers fill in their own grid and LDS size; ``g.tiles_m`` / ``g.tiles_n`` arrive set for the tiling that is launched (gemm_x3w recomputes
+// them).  ``extra_lds``: gemm option 1, bytes of LDS added per workgroup (an occupancy knob of the tools).  All return a PULSE_* code.
+// gemm_f32.hip: the fp32 MFMA kernel and the bf16 MFMA kernel over fp32 storage, 128 x 128 tile
+int launch_gemm_mfma32(const GemmArgs& g, bool akc, bool bkc, size_t extra_lds, hipStream_t stream);
+int launch_gemm_bf16c(const GemmArgs& g, bool akc, bool bkc, size_t extra_lds, hipStream_t stream);
+// gemm_x3.hip: the x3 arithmetic on a 128 x 128 x 16 tile, or 64 x 128 (``half_tile``)
+int launch_gemm_x3(const GemmArgs& g, bool akc, bool bkc, bool half_tile, size_t extra_lds, hipStream_t stream);
 // gemm_x3w.hip: the x3 arithmetic on a 256 x 256 x 16 tile (one wave per SIMD, accumulators in AGPRs).  ``g.tiles_m`` / ``g.tiles_n`` are
-// recomputed for the 256-wide tiling by the callee.  Returns a PULSE_* code.
+// recomputed for the 256-wide tiling by the callee.  Returns a PULSE_* code, or kWideTileUnavailable when the device refuses its dynamic LDS.
 int launch_gemm_x3w(const GemmArgs& g, bool akc, bool bkc, hipStream_t stream);
 // gemm_x3s.hip: the x3 arithmetic for skinny outputs (N <= 96, A reduction-contiguous, plain / ReLU epilogue): 128 rows x all columns per
 // workgroup.  Returns a PULSE_* code, or kWideTileUnavailable when the device refuses its dynamic LDS.

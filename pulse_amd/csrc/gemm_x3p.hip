@@ -1,6 +1,6 @@
 // fp32-grade GEMM on the bf16 matrix pipe over operands kept PRE-SPLIT in HBM ("x3p": x3, planar).
 //
-// Same arithmetic as gemm_x3_kernel (gemm_f32.hip): every fp32 operand is the exact sum of three bf16 numbers (a1 = bf16(a),
+// Same arithmetic as gemm_x3_kernel (gemm_x3.hip): every fp32 operand is the exact sum of three bf16 numbers (a1 = bf16(a),
 // a2 = bf16(a - a1), a3 = bf16(a - a1 - a2), round to nearest even), and C = sum_k a b is the six bf16 MFMAs per 16-deep k step whose
 // plane indices satisfy i + j <= 2, accumulated in fp32.  It replaces the same reference call sites (every nn.Linear forward / backward
 // of phc/learning/network_builder.py:105-124,245-261, amp_network_builder.py:127-148,206-211, amp_network_z_builder.py:469-580).
@@ -82,7 +82,7 @@ struct XpGeom {
 
 __device__ __forceinline__ unsigned xp_pack_rn(float lo, float hi) { return split_pack_rn(lo, hi); }
 __device__ __forceinline__ float xp_bitsf(unsigned v) { return split_bitsf(v); }
-// the three planes' packed dwords of an element pair (same rounding as StagerX::split_pair in gemm_f32.hip; common.h)
+// the three planes' packed dwords of an element pair (same rounding as StagerX::split_pair in gemm_x3.hip; common.h)
 __device__ __forceinline__ void xp_split_pair(float a, float b, unsigned& q0, unsigned& q1, unsigned& q2) { split_pair3(a, b, q0, q1, q2); }
 
 __device__ __forceinline__ bf16x8 xp_lds128(int addr) {
@@ -1150,60 +1150,28 @@ int pulse_gemm_x3p(const pulse_gemm_x3p_desc* d, pulse_stream_t s) {
     PULSE_REQUIRE(akc || (long long)g.kchunk * d->lda * 2 < (1LL << 31), "pulse_gemm_x3p: split the reduction further (k extent x pitch exceeds 2 GiB)");
     PULSE_REQUIRE(bkc || (long long)g.kchunk * d->ldb * 2 < (1LL << 31), "pulse_gemm_x3p: split the reduction further (k extent x pitch exceeds 2 GiB)");
     const dim3 grid((unsigned)(g.tiles_m * g.tiles_n), (unsigned)(d->batch * d->split_k));
-    hipError_t e = hipSuccess;
-#define PULSE_XP_LAUNCH(AK, BK_, W, NP, SLOT)                                                                                                   \
-    do {                                                                                                                                        \
-        constexpr int lds = XpGeom<W>::LDS;                                                                                                     \
-        static bool done = false;                                                                                                               \
-        if (!done) {                                                                                                                            \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3p_kernel<AK, BK_, W, NP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-            if (e != hipSuccess) return fail(PULSE_ERR_LAUNCH, "pulse_gemm_x3p: LDS attribute: %s", hipGetErrorString(e));                     \
-            done = true;                                                                                                                        \
-        }                                                                                                                                       \
-        hipLaunchKernelGGL((gemm_x3p_kernel<AK, BK_, W, NP>), grid, dim3(128 * W), lds, as_stream(s), g);                                       \
-    } while (0)
-    if (npl == 3 && akc && bkc) {
-        if (big) PULSE_XP_LAUNCH(true, true, 4, 3, 0); else PULSE_XP_LAUNCH(true, true, 2, 3, 1);
-    } else if (npl == 3 && akc) {
-        if (big) PULSE_XP_LAUNCH(true, false, 4, 3, 8); else PULSE_XP_LAUNCH(true, false, 2, 3, 9);
-    } else if (npl == 3) {
-        if (big) PULSE_XP_LAUNCH(false, false, 4, 3, 10); else PULSE_XP_LAUNCH(false, false, 2, 3, 11);
+    hipError_t e;
+    const hipStream_t st = as_stream(s);
+    if (npl == 3 || !ring) {                                          // gemm_x3p_kernel<AKC, BKC, waves / 2, planes>: 256-row (``big``) or 128-row tiles
+        auto go = [&](auto ak, auto bk, auto np) {
+            constexpr bool AK = decltype(ak)::value, BK_ = decltype(bk)::value;
+            constexpr int NP = decltype(np)::value;
+            return big ? launch_dyn_lds<gemm_x3p_kernel<AK, BK_, 4, NP>>(grid, dim3(512), XpGeom<4>::LDS, st, g)
+                       : launch_dyn_lds<gemm_x3p_kernel<AK, BK_, 2, NP>>(grid, dim3(256), XpGeom<2>::LDS, st, g);
+        };
+        using T = std::true_type; using F = std::false_type; using P1 = std::integral_constant<int, 1>; using P3 = std::integral_constant<int, 3>;
+        if (npl == 3) e = akc && bkc ? go(T{}, T{}, P3{}) : akc ? go(T{}, F{}, P3{}) : go(F{}, F{}, P3{});
+        else e = akc && bkc ? go(T{}, T{}, P1{}) : akc ? go(T{}, F{}, P1{}) : go(F{}, F{}, P1{});
     } else if (wide) {
-#define PULSE_B16W_LAUNCH(AK, BK_)                                                                                                              \
-    do {                                                                                                                                        \
-        constexpr int lds = XpGeom<4>::LDS;                                                                                                     \
-        static bool done = false;                                                                                                               \
-        if (!done) {                                                                                                                            \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_b16w_kernel<AK, BK_>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-            if (e != hipSuccess) return fail(PULSE_ERR_LAUNCH, "pulse_gemm_x3p: LDS attribute: %s", hipGetErrorString(e));                     \
-            done = true;                                                                                                                        \
-        }                                                                                                                                       \
-        hipLaunchKernelGGL((gemm_b16w_kernel<AK, BK_>), grid, dim3(512), lds, as_stream(s), g);                                                 \
-    } while (0)
-        if (akc && bkc) PULSE_B16W_LAUNCH(true, true); else if (akc) PULSE_B16W_LAUNCH(true, false); else PULSE_B16W_LAUNCH(false, false);
-#undef PULSE_B16W_LAUNCH
-    } else if (ring) {
-#define PULSE_B16R_LAUNCH(AK, BK_)                                                                                                              \
-    do {                                                                                                                                        \
-        constexpr int lds = XpGeom<4>::LDS;                                                                                                     \
-        static bool done = false;                                                                                                               \
-        if (!done) {                                                                                                                            \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_b16r_kernel<AK, BK_>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-            if (e != hipSuccess) return fail(PULSE_ERR_LAUNCH, "pulse_gemm_x3p: LDS attribute: %s", hipGetErrorString(e));                     \
-            done = true;                                                                                                                        \
-        }                                                                                                                                       \
-        hipLaunchKernelGGL((gemm_b16r_kernel<AK, BK_>), grid, dim3(512), lds, as_stream(s), g);                                                 \
-    } while (0)
-        if (akc && bkc) PULSE_B16R_LAUNCH(true, true); else if (akc) PULSE_B16R_LAUNCH(true, false); else PULSE_B16R_LAUNCH(false, false);
-#undef PULSE_B16R_LAUNCH
-    } else if (akc && bkc) {
-        if (big) PULSE_XP_LAUNCH(true, true, 4, 1, 2); else PULSE_XP_LAUNCH(true, true, 2, 1, 3);
-    } else if (akc) {
-        if (big) PULSE_XP_LAUNCH(true, false, 4, 1, 4); else PULSE_XP_LAUNCH(true, false, 2, 1, 5);
+        e = akc && bkc ? launch_dyn_lds<gemm_b16w_kernel<true, true>>(grid, dim3(512), XpGeom<4>::LDS, st, g)
+            : akc      ? launch_dyn_lds<gemm_b16w_kernel<true, false>>(grid, dim3(512), XpGeom<4>::LDS, st, g)
+                       : launch_dyn_lds<gemm_b16w_kernel<false, false>>(grid, dim3(512), XpGeom<4>::LDS, st, g);
     } else {
-        if (big) PULSE_XP_LAUNCH(false, false, 4, 1, 6); else PULSE_XP_LAUNCH(false, false, 2, 1, 7);
+        e = akc && bkc ? launch_dyn_lds<gemm_b16r_kernel<true, true>>(grid, dim3(512), XpGeom<4>::LDS, st, g)
+            : akc      ? launch_dyn_lds<gemm_b16r_kernel<true, false>>(grid, dim3(512), XpGeom<4>::LDS, st, g)
+                       : launch_dyn_lds<gemm_b16r_kernel<false, false>>(grid, dim3(512), XpGeom<4>::LDS, st, g);
     }
-#undef PULSE_XP_LAUNCH
+    if (e != hipSuccess) return fail(PULSE_ERR_LAUNCH, "pulse_gemm_x3p: LDS attribute: %s", hipGetErrorString(e));
     return check_launch("pulse_gemm_x3p");
 }
 }

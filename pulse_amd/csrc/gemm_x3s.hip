@@ -255,30 +255,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 }
 
 int launch_gemm_x3s(const GemmArgs& g, bool bkc, hipStream_t stream) {
+    const dim3 grid((unsigned)((g.M + S_ROWS - 1) / S_ROWS), (unsigned)g.batch), block(256);
     const int exp_mode = gemm_option(7);
     if (exp_mode && bkc) {                                   // timing experiments (tools/bench_gemm_x3_skinny.py --exp): results are garbage
-        const dim3 grid((unsigned)((g.M + S_ROWS - 1) / S_ROWS), (unsigned)g.batch);
-#define LAUNCHE(E_)                                                                                                                        \
-        { static bool once = false; if (!once) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3s_kernel<true, E_>), hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS); once = true; } \
-          hipLaunchKernelGGL((gemm_x3s_kernel<true, E_>), grid, dim3(256), S_LDS, stream, g); }
-        switch (exp_mode) { case 1: LAUNCHE(1) break; case 2: LAUNCHE(2) break; case 4: LAUNCHE(4) break; case 8: LAUNCHE(8) break; case 16: LAUNCHE(16) break;
-                            case 31: LAUNCHE(31) break; case 30: LAUNCHE(30) break; default: LAUNCHE(3) break; }
+        hipError_t e;
+#define LAUNCHE(E_) e = launch_dyn_lds<gemm_x3s_kernel<true, E_>>(grid, block, S_LDS, stream, g)
+        switch (exp_mode) { case 1: LAUNCHE(1); break; case 2: LAUNCHE(2); break; case 4: LAUNCHE(4); break; case 8: LAUNCHE(8); break; case 16: LAUNCHE(16); break;
+                            case 31: LAUNCHE(31); break; case 30: LAUNCHE(30); break; default: LAUNCHE(3); break; }
 #undef LAUNCHE
-        return check_launch("pulse_gemm_f32 (skinny-N tile, experiment)");
+        return lds_launch_status(e, "pulse_gemm_f32 (skinny-N tile, experiment)");
     }
-    const dim3 grid((unsigned)((g.M + S_ROWS - 1) / S_ROWS), (unsigned)g.batch);
-    static bool attr_done[2] = {false, false};
-    hipError_t e = hipSuccess;
-#define LAUNCHS(IDX, BK_)                                                                                                                  \
-    if (!attr_done[IDX]) {                                                                                                                 \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3s_kernel<BK_>), hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS);   \
-        if (e != hipSuccess) { (void)hipGetLastError(); return kWideTileUnavailable; }                                                     \
-        attr_done[IDX] = true;                                                                                                             \
-    }                                                                                                                                      \
-    hipLaunchKernelGGL((gemm_x3s_kernel<BK_>), grid, dim3(256), S_LDS, stream, g)
-    if (bkc) { LAUNCHS(0, true); }
-    else { LAUNCHS(1, false); }
-#undef LAUNCHS
+    const hipError_t e = bkc ? launch_dyn_lds<gemm_x3s_kernel<true>>(grid, block, S_LDS, stream, g)
+                             : launch_dyn_lds<gemm_x3s_kernel<false>>(grid, block, S_LDS, stream, g);
+    if (e != hipSuccess) { (void)hipGetLastError(); return kWideTileUnavailable; }
     return check_launch("pulse_gemm_f32 (skinny-N tile)");
 }
 

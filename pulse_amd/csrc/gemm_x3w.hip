@@ -1,6 +1,6 @@
 // fp32 GEMM on the bf16 matrix pipe ("x3": three-way operand split, six products) on a 256 x 256 x 16 workgroup tile.
 //
-// Same arithmetic, operand layouts, epilogues and split-K contract as gemm_x3_kernel (gemm_f32.hip) -- the six plane products are issued in the
+// Same arithmetic, operand layouts, epilogues and split-K contract as gemm_x3_kernel (gemm_x3.hip) -- the six plane products are issued in the
 // same order per 16-deep k step, so both tilings give BIT-IDENTICAL matrix outputs -- for the nn.Linear calls of the PPO update path:
 //   phc/learning/network_builder.py:105-124,245-261, phc/learning/amp_network_builder.py:127-148, phc/learning/amp_network_z_builder.py:341-467.
 //
@@ -32,6 +32,7 @@
 #include <type_traits>
 #include "common.h"
 #include "gemm_shared.h"
+#include "gemm_epilogue.h"
 
 namespace pulse {
 
@@ -165,178 +166,43 @@ struct StagerW {
 // ---- epilogue: one 256 x 128 pass through the LDS image (pitch W_CP floats).  Image column c holds tile column (c >> 6) * 128 + 64 pass + (c & 63) --------
 __device__ __forceinline__ int w_tile_col(int c, int pass) { return ((c >> 6) << 7) + 64 * pass + (c & 63); }
 
-__device__ __forceinline__ void w_store_pass(const GemmArgs& g, int pass, int tid, int m0, int n0, float* C, float* C2, const float* aux, unsigned* mask) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
+__device__ __forceinline__ void w_store_pass(const GemmArgs& g, const EpiOut& e, int pass, int tid, int wm, int wn, int half, int l31, int m0, int n0) {
+    if (!(g.vec_epi && m0 + WT <= g.M && n0 + WT <= g.N && epi_fast_form(g)))
+        return epi_general<W_CP, 32>(g, e, tid, wm, wn, half, l31, m0, n0, [pass](int c) { return w_tile_col(c, pass); });
+    // fast path (gemm_epilogue.h); with one wave per SIMD the aux values are loaded eight sweeps at a time AFTER the image exists
     const int c4 = (tid & 31) * 4;               // image column of this thread's four values
     const int tc = w_tile_col(c4, pass);         // tile column
     const int rl0 = tid >> 5;                    // 8 rows per sweep, 32 sweeps
-    const bool use_mask = g.epi == 1 && aux == nullptr;      // relu-grad from the forward's bit mask (gemm_shared.h: mask_word)
     const int cg = (n0 + tc) >> 2;
-    if (g.vec_epi) {
-        const bool fast = m0 + WT <= g.M && n0 + WT <= g.N && (g.epi == 1 || g.epi == 3 || (g.epi == 0 && g.act < 2));
-        if (fast) {
-            const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(C + (long long)m0 * g.ldc + n0, 0, 0xffffffffu, RSRC_FLAGS);
-            const int voC = (rl0 * g.ldc + tc) * 4;
-            const int ldsC = (rl0 * W_CP + c4) * 4;
-            if (g.epi == 0) {
-                const bool relu = g.act == 1;
-                const bool wmask = relu && mask != nullptr;
-                unsigned w = 0;
-#pragma unroll 8
-                for (int q = 0; q < 32; ++q) {
-                    f32x4 v = lds_read(ldsC + q * 8 * W_CP * 4);
-                    if (wmask) {
-                        w |= ((v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u)) << (4 * (q & 7));
-                        if ((q & 7) == 7) { mask[mask_word(m0 + 64 * (q >> 3) + rl0, cg, g.ldmask)] = w; w = 0; }
-                    }
-                    if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-                    buf_store(v, rsC, voC, q * 8 * g.ldc * 4);
-                }
-            } else if (use_mask) {
+    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(e.C + (long long)m0 * g.ldc + n0, 0, 0xffffffffu, RSRC_FLAGS);
+    const int voC = (rl0 * g.ldc + tc) * 4;
+    const int ldsC = (rl0 * W_CP + c4) * 4;
+    if (g.epi == 0) {
+        epi_fast_act<W_CP, 32, 8>(g, e.mask, rsC, voC, ldsC, m0 + rl0, cg);
+    } else if (e.use_mask) {
 #pragma unroll 1
-                for (int b = 0; b < 4; ++b) {                                      // one mask word per 64-row block of this thread's column group
-                    const unsigned mw = mask[mask_word(m0 + 64 * b + rl0, cg, g.ldmask)];
+        for (int b = 0; b < 4; ++b) {                                      // one mask word per 64-row block of this thread's column group
+            const unsigned mw = e.mask[mask_word(m0 + 64 * b + rl0, cg, g.ldmask)];
 #pragma unroll
-                    for (int qq = 0; qq < 8; ++qq) {
-                        const int q = 8 * b + qq;
-                        const unsigned nb = mw >> (4 * qq);
-                        f32x4 v = lds_read(ldsC + q * 8 * W_CP * 4);
-                        v.x = (nb & 1u) ? v.x : 0.f; v.y = (nb & 2u) ? v.y : 0.f; v.z = (nb & 4u) ? v.z : 0.f; v.w = (nb & 8u) ? v.w : 0.f;
-                        buf_store(v, rsC, voC, q * 8 * g.ldc * 4);
-                    }
-                }
-            } else {
-                const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(aux) + (long long)m0 * g.ldaux + n0, 0,
-                                                                                    0xffffffffu, RSRC_FLAGS);
-                const int voX = (rl0 * g.ldaux + tc) * 4;
-#pragma unroll 1
-                for (int q0 = 0; q0 < 32; q0 += 8) {
-                    f32x4 ax[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) ax[q] = buf_load(rsX, voX, (q0 + q) * 8 * g.ldaux * 4);
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const f32x4 a = ax[q];
-                        f32x4 v = lds_read(ldsC + (q0 + q) * 8 * W_CP * 4);
-                        if (g.epi == 1) { v.x = a.x > 0.f ? v.x : 0.f; v.y = a.y > 0.f ? v.y : 0.f; v.z = a.z > 0.f ? v.z : 0.f; v.w = a.w > 0.f ? v.w : 0.f; }
-                        else { v.x *= a.x; v.y *= a.y; v.z *= a.z; v.w *= a.w; }       // EPI_MUL_AUX: aux = the producer's stored activation derivative
-                        buf_store(v, rsC, voC, (q0 + q) * 8 * g.ldc * 4);
-                    }
-                }
-            }
-            return;
-        }
-        const int col = n0 + tc;
-        if (col < g.N) {
-            const bool full = col + 3 < g.N;
-            const bool wmask = g.epi == 0 && g.act == 1 && mask != nullptr;
-            unsigned w = 0;
-#pragma unroll 4
-            for (int q = 0; q < 32; ++q) {
-                const int rl = rl0 + 8 * q;
-                const int row = m0 + rl;
-                // ragged tiles: a 64-row block's word is read at its first row slot / stored after its last one (rows past M: zero bits)
-                if (use_mask && (q & 7) == 0 && m0 + 64 * (q >> 3) < g.M) w = mask[mask_word(m0 + 64 * (q >> 3) + rl0, cg, g.ldmask)];
-                if (row >= g.M) {
-                    if (wmask && (q & 7) == 7 && m0 + 64 * (q >> 3) < g.M) { mask[mask_word(m0 + 64 * (q >> 3) + rl0, cg, g.ldmask)] = w; w = 0; }
-                    continue;
-                }
-                const float4 v = *reinterpret_cast<const float4*>(smem + rl * W_CP + c4);
-                float o[4] = {v.x, v.y, v.z, v.w};
-                if (wmask) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) w |= (col + k < g.N && o[k] > 0.f ? 1u : 0u) << (4 * (q & 7) + k);
-                    if ((q & 7) == 7) { mask[mask_word(m0 + 64 * (q >> 3) + rl0, cg, g.ldmask)] = w; w = 0; }
-                }
-                if (use_mask) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) o[k] = ((w >> (4 * (q & 7) + k)) & 1u) ? o[k] : 0.f;
-                    float* pc = C + (long long)row * g.ldc + col;
-                    if (full) *reinterpret_cast<float4*>(pc) = make_float4(o[0], o[1], o[2], o[3]);
-                    else for (int k = 0; k < 4 && col + k < g.N; ++k) pc[k] = o[k];
-                    continue;
-                }
-                if (g.epi == 0) {
-                    if (g.act == 1) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) o[k] = fmaxf(o[k], 0.f);
-                    } else if (g.act == 2) {
-                        if (C2) {
-                            float* p2 = C2 + (long long)row * g.ldc2 + col;
-                            if (full) *reinterpret_cast<float4*>(p2) = make_float4(o[0], o[1], o[2], o[3]);
-                            else for (int k = 0; k < 4 && col + k < g.N; ++k) p2[k] = o[k];
-                        }
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) o[k] = o[k] / (1.f + __expf(-o[k]));
-                    } else if (g.act == 3) {             // SiLU whose C2 receives d silu / d z (the backward pass then multiplies: EPI_MUL_AUX)
-                        float d[4];
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const float sg = 1.f / (1.f + __expf(-o[k]));
-                            d[k] = sg * (1.f + o[k] * (1.f - sg));
-                            o[k] = o[k] / (1.f + __expf(-o[k]));
-                        }
-                        float* p2 = C2 + (long long)row * g.ldc2 + col;
-                        if (full) *reinterpret_cast<float4*>(p2) = make_float4(d[0], d[1], d[2], d[3]);
-                        else for (int k = 0; k < 4 && col + k < g.N; ++k) p2[k] = d[k];
-                    }
-                } else {
-                    const float* pa = aux + (long long)row * g.ldaux + col;
-                    float a4[4] = {0.f, 0.f, 0.f, 0.f};
-                    if (full) { const float4 t = *reinterpret_cast<const float4*>(pa); a4[0] = t.x; a4[1] = t.y; a4[2] = t.z; a4[3] = t.w; }
-                    else for (int k = 0; k < 4 && col + k < g.N; ++k) a4[k] = pa[k];
-                    if (g.epi == 1) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) o[k] = a4[k] > 0.f ? o[k] : 0.f;
-                    } else if (g.epi == 3) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) o[k] *= a4[k];
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const float sg = 1.f / (1.f + __expf(-a4[k]));
-                            o[k] *= sg * (1.f + a4[k] * (1.f - sg));
-                        }
-                    }
-                }
-                float* pc = C + (long long)row * g.ldc + col;
-                if (full) *reinterpret_cast<float4*>(pc) = make_float4(o[0], o[1], o[2], o[3]);
-                else for (int k = 0; k < 4 && col + k < g.N; ++k) pc[k] = o[k];
+            for (int qq = 0; qq < 8; ++qq) {
+                const int q = 8 * b + qq;
+                const unsigned nb = mw >> (4 * qq);
+                f32x4 v = lds_read(ldsC + q * 8 * W_CP * 4);
+                v.x = (nb & 1u) ? v.x : 0.f; v.y = (nb & 2u) ? v.y : 0.f; v.z = (nb & 4u) ? v.z : 0.f; v.w = (nb & 8u) ? v.w : 0.f;
+                buf_store(v, rsC, voC, q * 8 * g.ldc * 4);
             }
         }
-        return;
-    }
-    // scalar path (unaligned C / aux pitches: odd test shapes, not the training shapes): thread = (row group tid >> 7, image column tid & 127)
-    {
-        const int c = tid & 127;
-        const int col = n0 + w_tile_col(c, pass);
-        if (col >= g.N) return;
+    } else {
+        const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(e.aux) + (long long)m0 * g.ldaux + n0, 0,
+                                                                            0xffffffffu, RSRC_FLAGS);
+        const int voX = (rl0 * g.ldaux + tc) * 4;
 #pragma unroll 1
-        for (int rl = tid >> 7; rl < WT; rl += 2) {
-            const int row = m0 + rl;
-            if (row >= g.M) break;
-            float v = smem[rl * W_CP + c];
-            if (g.epi == 0) {
-                if (g.act == 1) {
-                    v = fmaxf(v, 0.f);
-                } else if (g.act == 2) {
-                    if (C2) C2[(long long)row * g.ldc2 + col] = v;
-                    v = v / (1.f + __expf(-v));
-                } else if (g.act == 3) {
-                    const float sg = 1.f / (1.f + __expf(-v));
-                    C2[(long long)row * g.ldc2 + col] = sg * (1.f + v * (1.f - sg));
-                    v = v / (1.f + __expf(-v));
-                }
-            } else if (g.epi == 1) {
-                v = aux[(long long)row * g.ldaux + col] > 0.f ? v : 0.f;
-            } else if (g.epi == 3) {
-                v *= aux[(long long)row * g.ldaux + col];
-            } else {
-                const float zz = aux[(long long)row * g.ldaux + col];
-                const float sg = 1.f / (1.f + __expf(-zz));
-                v *= sg * (1.f + zz * (1.f - sg));
-            }
-            C[(long long)row * g.ldc + col] = v;
+        for (int q0 = 0; q0 < 32; q0 += 8) {
+            f32x4 ax[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) ax[q] = buf_load(rsX, voX, (q0 + q) * 8 * g.ldaux * 4);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) epi_fast_grad(g.epi == 3, ax[q], ldsC + (q0 + q) * 8 * W_CP * 4, rsC, voC, (q0 + q) * 8 * g.ldc * 4);
         }
     }
 }
@@ -517,10 +383,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 
     // epilogue: pass p covers MFMA column tiles j = 2p, 2p + 1 of every wave (all four waves write 128 registers per pass, 16 bytes at a time)
     {
-        float* C = g.C + bz * g.sC + sp * g.sSplit;
-        float* C2 = g.C2 ? g.C2 + bz * g.sC2 : nullptr;
-        const float* aux = g.aux ? g.aux + bz * g.sAux : nullptr;
-        unsigned* mask = g.mask ? g.mask + bz * g.sMask : nullptr;
+        const EpiOut e = epi_out(g, bz, sp);
         const int img = lb + ((wm * 128 + l31) * W_CP + wn * 64 + 4 * half) * 4;
         __syncthreads();                                          // the image overlays the staging buffers
 #pragma unroll
@@ -536,7 +399,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
                         lds_st<f32x4>(img + (i * 32 * W_CP + jj * 32 + 8 * gq) * 4, (f32x4){t[4 * gq], t[4 * gq + 1], t[4 * gq + 2], t[4 * gq + 3]});
                     }
             __syncthreads();
-            w_store_pass(g, pass, tid, m0, n0, C, C2, aux, mask);
+            w_store_pass(g, e, pass, tid, wm, wn, half, l31, m0, n0);
         }
     }
     if (g.dbg && tid == 0) {
@@ -552,19 +415,11 @@ int launch_gemm_x3w(const GemmArgs& g0, bool akc, bool bkc, hipStream_t stream) 
     g.tiles_m = (g.M + WT - 1) / WT;
     g.tiles_n = (g.N + WT - 1) / WT;
     const dim3 grid((unsigned)(g.tiles_m * g.tiles_n), (unsigned)(g.batch * g.splitk));
-    static bool attr_done[3] = {false, false, false};
-    hipError_t e = hipSuccess;
-#define LAUNCHW(IDX, AK, BK_)                                                                                          \
-    if (!attr_done[IDX]) {                                                                                             \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3w_kernel<AK, BK_>), hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS); \
-        if (e != hipSuccess) { (void)hipGetLastError(); return kWideTileUnavailable; }   /* the device will not grant 135 KB of LDS: the caller keeps the 128 x 128 tile */ \
-        attr_done[IDX] = true;                                                                                         \
-    }                                                                                                                  \
-    hipLaunchKernelGGL((gemm_x3w_kernel<AK, BK_>), grid, dim3(256), W_LDS, stream, g)
-    if (akc && bkc) { LAUNCHW(0, true, true); }
-    else if (akc && !bkc) { LAUNCHW(1, true, false); }
-    else { LAUNCHW(2, false, false); }
-#undef LAUNCHW
+    const dim3 block(256);
+    const hipError_t e = akc && bkc ? launch_dyn_lds<gemm_x3w_kernel<true, true>>(grid, block, W_LDS, stream, g)
+                         : akc      ? launch_dyn_lds<gemm_x3w_kernel<true, false>>(grid, block, W_LDS, stream, g)
+                                    : launch_dyn_lds<gemm_x3w_kernel<false, false>>(grid, block, W_LDS, stream, g);
+    if (e != hipSuccess) { (void)hipGetLastError(); return kWideTileUnavailable; }   // the device will not grant 135 KB of LDS: the caller keeps the 128 x 128 tile
     return check_launch("pulse_gemm_f32 (256 x 256 tile)");
 }
 

@@ -137,7 +137,7 @@ def dw_split(tiles, max_split, fill=512):
 
 
 def x3_tile_costs(M, N, z, k=16384):
-    """(narrow, wide) cost of an x3 launch with z = batch x split_k grid slices, in the launcher's units (gemm_f32.hip: x3_wide_tile): one
+    """(narrow, wide) cost of an x3 launch with z = batch x split_k grid slices, in the launcher's units (gemm_api.hip: x3_wide_tile): one
     128 x 128 tile alone on a CU = 1.5 per unit of reduction length, two sharing a CU 2; a 256 x 256 workgroup has a CU to itself at about
     3.3 (more on short reductions, whose prologue / epilogue nothing hides)."""
     nt = ((M + 127) // 128) * ((N + 127) // 128) * z

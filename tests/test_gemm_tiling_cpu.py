@@ -1,5 +1,5 @@
 """Host-side logic of the two-tiling x3 GEMM (no GPU): the planner's cost model / slab-count choice (pulse_amd/kernels.py: x3_tile_costs,
-dw_split_x3 -- the python mirror of gemm_f32.hip: x3_wide_tile) and the per-layer slab regions of the actor / critic gradient reduce
+dw_split_x3 -- the python mirror of gemm_api.hip: x3_wide_tile) and the per-layer slab regions of the actor / critic gradient reduce
 (pulse_amd/learning/network.py: _slab_regions).  Reference of the op being planned: the weight gradients of nn.Linear in
 phc/learning/network_builder.py:105-124 (autograd's mm over the batch dimension)."""
 import pytest

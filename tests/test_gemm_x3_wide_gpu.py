@@ -317,7 +317,7 @@ def test_random_shapes_both_tilings_agree(dev):
 @pytest.mark.parametrize("form", ["fwd_relu_mask", "dx_mul_aux", "fwd_silu_d"])
 def test_column_tail_split_is_invisible(dev, form):
     """A narrow column tail that would cost the 256 x 256 tiling a whole extra round of workgroups (cfg3's N = 3096 = 12 x 256 + 24) is launched
-    on the 128 x 128 tiling beside the wide main part (gemm_f32.hip; gemm option 5 = 1 switches the split off): same bits, every output
+    on the 128 x 128 tiling beside the wide main part (gemm_api.hip; gemm option 5 = 1 switches the split off): same bits, every output
     (C, C2, the ReLU bit mask) and nothing written past N."""
     g = torch.Generator().manual_seed(77)
     m, n, k = 4096, 16 * 256 + 24, 64                       # 16 x 17 = 272 wide tiles = 2 rounds; 16 x 16 = 256 = 1 round + the tail
