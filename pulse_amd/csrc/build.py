@@ -46,6 +46,8 @@ SOURCES = [
     ("gemm_x3.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form"]),
     ("gemm_api.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form"]),
     ("gemm_x3p.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form"]),
+    ("gemm_b16.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form"]),
+    ("gemm_x3p_api.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form"]),
     # the 256 x 256 x3 tile runs ONE wave per SIMD with its 256 accumulator registers in AGPRs: no VGPR-form flag here
     # (its k-tile body is one fully unrolled 96-MFMA schedule: lift the pragma-unroll size limit, or the loop stays rolled and the accumulators go to scratch)
     ("gemm_x3w.hip", ["-mllvm", "-pragma-unroll-threshold=4000000", "-Wno-unused-const-variable"]),

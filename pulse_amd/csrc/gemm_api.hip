@@ -123,7 +123,7 @@ thread_local int g_last_tile = 0;               // tile rows of the calling thre
 thread_local int g_opt[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // [1] extra LDS bytes per workgroup, [2] no 64-row tile, [3] bf16-storage tile choice (see pulse_hip.h)
 }
 
-namespace pulse { int gemm_option(int key) { return key >= 0 && key < 16 ? g_opt[key] : 0; } long long* gemm_debug_buffer() { return g_dbg; } }    // read by gemm_x3p.hip (common.h)
+namespace pulse { int gemm_option(int key) { return key >= 0 && key < 16 ? g_opt[key] : 0; } long long* gemm_debug_buffer() { return g_dbg; } }    // read by gemm_x3p_api.hip (common.h)
 
 namespace {
 // Which tiling serves an x3 launch.  Cost model in units of (one 128 x 128 output tile) x (k per split), per CU: the narrow kernel keeps two

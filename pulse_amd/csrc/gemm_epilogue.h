@@ -12,15 +12,7 @@
 
 namespace pulse {
 
-// ---- element math ---------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float silu(float z) { return z / (1.f + __expf(-z)); }
-__device__ __forceinline__ float silu_deriv(float z) {               // d silu / d z
-    const float sg = 1.f / (1.f + __expf(-z));
-    return sg * (1.f + z * (1.f - sg));
-}
-// ``round_bf16``: results leave as bf16-representable fp32 values -- what a bf16 autocast Linear hands to the next op.
-__device__ __forceinline__ float rbf(float v) { return (float)(__bf16)v; }
-
+// ---- element math (silu, silu_deriv, rbf: gemm_shared.h) -----------------------------------------------------------------------------------------
 // N elements through EPI 0's activation ``act`` (GemmArgs): o = the accumulators in, C's values out; c2 = what C2 receives from the SiLU forms
 // (act 2: the pre-activation, kept for the backward pass if C2 is given; act 3: d silu / d z, which the backward pass multiplies by: EPI 3)
 template <int N>

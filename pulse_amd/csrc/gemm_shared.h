@@ -1,6 +1,7 @@
 // Pieces shared by the fp32-storage GEMM translation units (gemm_f32.hip: fp32 MFMA, bf16 MFMA over fp32 storage; gemm_x3.hip: the 128 x 128 x3
 // kernel; gemm_x3w.hip: the 256 x 256 x3 kernel; gemm_x3s.hip: the skinny-N x3 kernel; gemm_api.hip: pulse_gemm_f32, which chooses between them):
 // the launch argument block, the tile constants, the LDS slot permutation, raw-buffer and LDS access helpers, the launchers each unit exports.
+// The vector types and the epilogues' element math are also what the planar units use (gemm_planar.h).
 #pragma once
 #include "common.h"
 
@@ -66,6 +67,15 @@ __device__ __forceinline__ float bitsf(unsigned v) { return __builtin_bit_cast(f
 __device__ __forceinline__ unsigned pack_rn(float lo_elem, float hi_elem) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){lo_elem, hi_elem}, bf16x2));
 }
+
+// ---- element math of the epilogues (gemm_epilogue.h: the fp32-storage kernels; gemm_planar.h: the planar ones)
+__device__ __forceinline__ float silu(float z) { return z / (1.f + __expf(-z)); }
+__device__ __forceinline__ float silu_deriv(float z) {               // d silu / d z
+    const float sg = 1.f / (1.f + __expf(-z));
+    return sg * (1.f + z * (1.f - sg));
+}
+// ``round_bf16``: results leave as bf16-representable fp32 values -- what a bf16 autocast Linear hands to the next op.
+__device__ __forceinline__ float rbf(float v) { return (float)(__bf16)v; }
 
 // what a launcher returns after launch_dyn_lds (common.h) when a refused LDS request is an error
 inline int lds_launch_status(hipError_t e, const char* what) {
