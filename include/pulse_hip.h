@@ -36,7 +36,7 @@ extern "C" {
 #define PULSE_ERR_LAUNCH (-2)
 #define PULSE_ERR_UNSUPPORTED (-3)
 
-#define PULSE_ABI_VERSION 29
+#define PULSE_ABI_VERSION 30
 
 typedef void* pulse_stream_t; /* hipStream_t */
 
@@ -79,7 +79,7 @@ typedef struct pulse_motion_tables {
     const float* frames;              /* (total_frames, frame_stride) packed records */
     int64_t frame_stride;             /* floats per record, multiple of 4 */
     int64_t total_frames;
-    int32_t num_bodies;               /* J <= 32 */
+    int32_t num_bodies;               /* J in [1, 64] (v30; 32 before) */
     int32_t off_gts, off_grs, off_lrs, off_gvs, off_gavs, off_dvs;   /* float offsets of the fields inside a record */
     const float* motion_lengths;      /* (num_motions) seconds  (_motion_lengths) */
     const float* motion_dt;           /* (num_motions)          (_motion_dt) */
@@ -102,13 +102,19 @@ typedef struct pulse_reward_specs {
 #define PULSE_IM_REWARD   4u  /* compute_imitation_reward (+ power term), humanoid_im.py:853-919,1543-1574 */
 #define PULSE_IM_RESET    8u  /* compute_humanoid_im_reset, humanoid_im.py:1119-1192,1600-1628 */
 #define PULSE_IM_DEBUG_POISON_LDS 0x80000000u /* debug: the kernel pre-fills its LDS with NaN (uninitialised-read detector) */
+/* debug (v30): take the 64-lane form of the kernel whatever the body count.  pulse_im_step maps lane = body inside a group of 32 lanes
+ * (num_bodies <= 32: SMPL, 24) or 64 lanes (33 .. 64: SMPL-X / SMPL-H, 52).  At num_bodies <= 32 both forms do the same arithmetic in the same
+ * order, so their outputs are bit-identical; the bit exists so that a test can say so.
+ * Width rule of the launcher: 64 lanes when num_bodies > 32, when the reset stage runs with num_reset > 32 (lane = reset id there; ids may repeat,
+ * at most 64 of them), or when this bit is set; 32 lanes otherwise. */
+#define PULSE_IM_FORCE_WIDE 0x40000000u
 
 typedef struct pulse_im_step_args {
     /* ---- simulation state (read) ---- */
     const float* rb;          /* (num_envs, >=num_bodies, 13) */
     int64_t rb_env_stride;    /* floats between consecutive envs (>= num_bodies*13) */
     int32_t num_envs;
-    int32_t num_bodies;       /* J, 24 for SMPL; <= 32 */
+    int32_t num_bodies;       /* J, 24 for SMPL, 52 for SMPL-X / SMPL-H; in [1, 64] (num_reset <= 64, num_track <= J; occl_bits: J <= 32) */
     /* optional subset selection (partial reset, humanoid_im.py:677-706 with env_ids):
        env_ids != NULL: process only env_ids[0..num_ids);  env_mask != NULL: skip
        envs whose mask byte is 0.  Both NULL: all envs. */

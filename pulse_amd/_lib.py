@@ -12,12 +12,14 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int6
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PULSE_HIP_LIB: another build of the SAME library (tools/im_step_repro.py compares compile variants); default = the in-tree build
 LIB_PATH = os.environ.get("PULSE_HIP_LIB") or os.path.join(_HERE, "csrc", "libpulse_hip.so")
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 PULSE_IM_SELF_OBS = 1
 PULSE_IM_TASK_OBS = 2
 PULSE_IM_REWARD = 4
 PULSE_IM_RESET = 8
+PULSE_IM_DEBUG_POISON_LDS = 0x80000000   # debug: the step kernel pre-fills its LDS with NaN
+PULSE_IM_FORCE_WIDE = 0x40000000         # debug: 64-lane groups whatever the body count (bit-identical at <= 32 bodies)
 
 
 class PulseLibraryError(RuntimeError):

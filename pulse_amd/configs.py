@@ -95,7 +95,14 @@ CONFIGS = {
     "cfg3_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_z", "env": "vae", "agent": "amp",
                    "extra": {"use_seq_rl": True}},
     "cfg3_ppo_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_z", "env": "vae_ppo", "agent": "amp"},
+    # the 52-body SMPL-X humanoid (robot/smplx_humanoid.yaml: non-upright rest pose) on the imitation env: observation 778 + 1248 = 2026 columns
+    # (row pitch 2048), 153 actions
+    "smplx_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "units": [512, 512], "humanoid": "smplx"},
 }
+
+# cfg.robot of the two shipped humanoids (robot/smpl_humanoid.yaml, robot/smplx_humanoid.yaml: humanoid_type and has_upright_start)
+ROBOTS = {"smpl": {"humanoid_type": "smpl", "has_upright_start": True}, "smplx": {"humanoid_type": "smplx", "has_upright_start": False},
+          "smplh": {"humanoid_type": "smplh", "has_upright_start": False}}
 
 
 def agent_config(name, **overrides):
@@ -117,14 +124,18 @@ def agent_config(name, **overrides):
     cfg.update({"horizon_length": c["horizon_length"], "minibatch_size": c["minibatch_size"], "network": net})
     cfg.update(c.get("extra", {}))
     cfg.update(overrides)
-    cfg["_env_kind"], cfg["_agent_kind"] = c.get("env", "im"), c.get("agent", "common")
+    cfg["_env_kind"], cfg["_agent_kind"], cfg["_humanoid"] = c.get("env", "im"), c.get("agent", "common"), c.get("humanoid", "smpl")
     return cfg, c["num_envs"]
 
 
-def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kind="im", reference="recorded", env_overrides=None):
-    """``reference``: 'recorded' = pre-recorded rigid-body / reference frames (RecordedRollout, what the CPU oracle agent replays);
+def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kind="im", reference="recorded", env_overrides=None, humanoid="smpl"):
+    """``humanoid``: 'smpl' (24 bodies) | 'smplx' / 'smplh' (52 bodies) -- the robot config handed to the task as cfg.robot.
+    ``reference``: 'recorded' = pre-recorded rigid-body / reference frames (RecordedRollout, what the CPU oracle agent replays);
     'motion_lib' = reference motion queried from the HBM-resident MotionLib every step, physics stand-in tracking it."""
-    from .env.humanoid_im import HumanoidIm, VecTaskPythonWrapper
+    from .env.humanoid_im import HumanoidIm, VecTaskPythonWrapper, check_humanoid_options
+    if humanoid not in ROBOTS:
+        raise NotImplementedError(f"humanoid {humanoid!r}: 'smpl', 'smplh' and 'smplx' are built")
+    robot = dict(ROBOTS[humanoid])
     if env_kind in ("speed_z", "reach_z", "strike_z", "terrain_z"):
         # HumanoidSpeedZ & co: synthetic task physics, the frozen decoder initialised from a (random-init) PULSE checkpoint
         import torch
@@ -136,7 +147,7 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
         sim = HT.SyntheticTaskSim(num_envs, horizon + 1, device, seed=seed, rank=rank, xy_offset=(13.0, 15.0) if env_kind == "terrain_z" else (0.0, 0.0))
         cls = {"speed_z": HT.HumanoidSpeedZ, "reach_z": HT.HumanoidReachZ, "strike_z": HT.HumanoidStrikeZ,
                "terrain_z": HT.HumanoidPedestrianTerrainZ}[env_kind]
-        task = cls({"env": env_cfg}, sim, device=device)
+        task = cls({"env": env_cfg} if humanoid == "smpl" else {"env": env_cfg, "robot": robot}, sim, device=device)
         znet = AMPZNetwork(NETWORK_Z, actions_num=69, self_obs_size=task.get_self_obs_size(), task_obs_size=576,
                            task_obs_size_detail={"embedding_size": 32, "z_type": "vae", "use_vae_prior": True, "use_vae_clamped_prior": True,
                                                  "vae_var_clamp_max": 2}, device=device)
@@ -153,24 +164,28 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
         from . import synthetic as syn
         from .env.motion_lib import MotionLib
         from .env.sim import KinematicSim, PdSim
-        tables = syn.synthetic_motion_library(syn.make_generator(seed + 5, rank), min(num_envs, 1024))
+        cfg = {"env": env_cfg} if humanoid == "smpl" else {"env": env_cfg, "robot": robot}
+        check_humanoid_options(cfg)                     # an unbuilt combination raises by name before anything is allocated
+        tables = syn.synthetic_motion_library(syn.make_generator(seed + 5, rank), min(num_envs, 1024), humanoid=humanoid)
         motion = MotionLib.from_tables(tables, device)
         sim_cls = PdSim if env_cfg.pop("physics", "tracking") == "pd" else KinematicSim        # "pd": action-dependent stand-in
-        sim = sim_cls(num_envs, horizon + 1, device, seed=seed, rank=rank)
-        task = HumanoidIm({"env": env_cfg}, sim, motion, device=device)
+        sim = sim_cls(num_envs, horizon + 1, device, seed=seed, rank=rank, humanoid=humanoid)
+        task = HumanoidIm(cfg, sim, motion, device=device)
         return VecTaskPythonWrapper(task, rl_device=device), None
     from .env.sim import RecordedMotion, RecordedRollout, RecordedSim
+    cfg = {"env": env_cfg} if humanoid == "smpl" else {"env": env_cfg, "robot": robot}
+    check_humanoid_options(cfg)
     if rollout is None:
-        rollout = RecordedRollout(num_envs, horizon + 1, seed=seed, rank=rank)
+        rollout = RecordedRollout(num_envs, horizon + 1, seed=seed, rank=rank, humanoid=humanoid)
     rollout.to(device)
     sim = RecordedSim(rollout)
     motion = RecordedMotion(rollout, sim)
-    task = HumanoidIm({"env": env_cfg}, sim, motion, device=device)
+    task = HumanoidIm(cfg, sim, motion, device=device)
     task.progress_buf.copy_(rollout.init_progress)
     return VecTaskPythonWrapper(task, rl_device=device), rollout
 
 
-def make_agent(name="cfg2", device="cuda:0", seed=1234, rank=0, rollout=None, reference="recorded", env_overrides=None, **overrides):
+def make_agent(name="cfg2", device="cuda:0", seed=1234, rank=0, rollout=None, reference="recorded", env_overrides=None, humanoid=None, **overrides):
     from .learning.amp_agent import AMPAgent
     from .learning.common_agent import CommonAgent
     num_envs_override = overrides.pop("num_envs_override", None)
@@ -178,7 +193,7 @@ def make_agent(name="cfg2", device="cuda:0", seed=1234, rank=0, rollout=None, re
     if num_envs_override is not None:
         num_envs = int(num_envs_override)
     vec_env, rollout = make_env(num_envs, cfg["horizon_length"], device, seed=seed, rank=rank, rollout=rollout, env_kind=cfg["_env_kind"],
-                                reference=reference, env_overrides=env_overrides)
+                                reference=reference, env_overrides=env_overrides, humanoid=humanoid if humanoid is not None else cfg["_humanoid"])
     cfg.update({"vec_env": vec_env, "device": device, "seed": seed})
     cls = AMPAgent if cfg["_agent_kind"] == "amp" else CommonAgent
     return cls("pulse_amd", cfg), rollout

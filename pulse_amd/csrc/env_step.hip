@@ -8,12 +8,13 @@
 // (each of which is O(30-70) elementwise launches in the reference's GPU pipeline).
 //
 // Mapping (MI355X-first, HBM/launch bound: ~8 KB algorithmic traffic per env-step):
-//   * one 32-lane half-wave per environment, lane b <-> body b (24 of 32 lanes active);
-//     ENVS_PER_BLOCK environments per workgroup, so N=4096 gives 1024 workgroups (>> 256 CUs);
+//   * one LB-lane group per environment and role, lane b <-> body b: LB = 32 (a half-wave, 24 of 32 lanes active for SMPL) up to 32
+//     bodies, LB = 64 (a whole wave, 52 of 64 lanes for SMPL-X) for 33 .. 64 bodies; E environments per workgroup (4 / 2), so N=4096
+//     gives 1024 / 2048 workgroups (>> 256 CUs);
 //   * the env's 13-float AoS rigid-body records and both reference frames (t and t+1) are
 //     staged into LDS with coalesced 16-byte loads, then read back at a 13-float lane stride
 //     (odd stride -> conflict-free ds_read_b32);
-//   * per-env reductions (4 reward errors, power, any-body-fell) are 32-lane butterfly shuffles;
+//   * per-env reductions (4 reward errors, power, any-body-fell) are LB-lane butterfly shuffles;
 //   * the 934-float observation row is assembled in LDS and written with full-line 16-byte
 //     stores straight into the caller's row pitch (e.g. a 960-float GEMM-ready pitch, pad zeroed).
 // Compiled with -ffp-contract=off so products/sums round exactly like the eager reference.
@@ -24,7 +25,10 @@
 
 namespace pulse {
 
-constexpr int kLanesPerEnv = 32;
+constexpr int kImMaxBodies = 64;      // one wave: the widest lane group
+// the power term is summed by the first 32 lanes of the group at a stride of 32 in BOTH group widths, so the sum associates the same way
+// whichever width a launch takes (the upper half of a 64-lane group adds exact zeros in the first butterfly step)
+constexpr int kPowerLanes = 32;
 
 struct ObsLayout {
     int self_w;      // width of the self observation (all history steps / force-sensor rows included)
@@ -69,14 +73,16 @@ __device__ __forceinline__ int task_off(int v, int blk, int Jt, int T, int t, in
     return base[blk] * Jt * T + w * (t * Jt + j);
 }
 
+template <int LB>
 __device__ __forceinline__ float group_sum(float v) {
 #pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, kLanesPerEnv);
+    for (int o = LB / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, LB);
     return v;
 }
+template <int LB>
 __device__ __forceinline__ int group_or(int v) {
 #pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v |= __shfl_xor(v, o, kLanesPerEnv);
+    for (int o = LB / 2; o > 0; o >>= 1) v |= __shfl_xor(v, o, LB);
     return v;
 }
 
@@ -95,12 +101,14 @@ __device__ __forceinline__ void stage(float* __restrict__ dst, const float* __re
 
 __device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// R = half-waves per env.  R = 1: the 32 lanes of an env do everything in turn.  R = 2 (64 lanes per env): the env's two half-waves share the
+// LB = lanes per group (32: a half-wave, up to 32 bodies; 64: a whole wave, up to 64 bodies), lane = body.  At J <= 32 the wide form does the
+// same arithmetic as the narrow one: lanes J .. LB - 1 feed exact zeros into every butterfly, whose first step (offset 32) then adds 0.
+// R = groups per env.  R = 1: the LB lanes of an env do everything in turn.  R = 2 (2 LB lanes per env): the env's two groups share the
 // staging copies and split the arithmetic -- half 0: reference blend at t, self observation, reward, reset; half 1: reference blend(s) at
 // t + 1, task observation -- so the dependent chain of a step (the launch is latency-bound: every env's waves are resident at once) is about
 // half as long and the chip holds twice the waves.  Same operations on the same operands per output element: results are bit-identical.
-template <int E, int R>
-__global__ void __launch_bounds__(E * R * kLanesPerEnv) im_step_kernel(const pulse_im_step_args a) {
+template <int E, int R, int LB>
+__global__ void __launch_bounds__(E * R * LB) im_step_kernel(const pulse_im_step_args a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int J = a.num_bodies;
     const int J13 = J * 13;
@@ -121,16 +129,16 @@ __global__ void __launch_bounds__(E * R * kLanesPerEnv) im_step_kernel(const pul
     const int tid = threadIdx.x;
     if (a.what & PULSE_IM_DEBUG_POISON_LDS) {      // debug aid: a read of LDS nobody wrote shows up as NaN in the outputs
         const int total = E * ((2 + T) * J13p + 3 * ndp + colsp);
-        for (int i = tid; i < total; i += E * R * kLanesPerEnv) smem[i] = __int_as_float(0x7fc00000);
+        for (int i = tid; i < total; i += E * R * LB) smem[i] = __int_as_float(0x7fc00000);
         __syncthreads();
     }
-    constexpr int NL = R * kLanesPerEnv;           // lanes per env
+    constexpr int NL = R * LB;                     // lanes per env
     // the two half-waves of an env sit in DIFFERENT waves (a wave holds the same half of two envs): a wave never diverges between the halves'
-    // code paths.  Threads [0, 32 E) are half 0 of envs 0 .. E-1, threads [32 E, 64 E) half 1.
-    const int role = tid / (E * kLanesPerEnv);     // which half-wave of the env
-    const int slot = (tid % (E * kLanesPerEnv)) / kLanesPerEnv;
-    const int lane = tid % kLanesPerEnv;           // body / joint index inside the half-wave
-    const int lane_all = role * kLanesPerEnv + lane;   // cooperative copies: every lane of the env
+    // code paths.  Threads [0, LB E) are group 0 of envs 0 .. E-1, threads [LB E, 2 LB E) group 1.
+    const int role = tid / (E * LB);               // which group of the env
+    const int slot = (tid % (E * LB)) / LB;
+    const int lane = tid % LB;                     // body / joint index inside the group
+    const int lane_all = role * LB + lane;         // cooperative copies: every lane of the env
     const bool r_now = role == 0, r_next = role == R - 1;      // who blends / computes what (R = 1: one half-wave does both)
     const int count = a.env_ids ? a.num_ids : a.num_envs;
     const int idx = blockIdx.x * E + slot;
@@ -338,13 +346,13 @@ __global__ void __launch_bounds__(E * R * kLanesPerEnv) im_step_kernel(const pul
                 }
             }
             if (a.self_obs_version == 3)                            // force-sensor readings appended (humanoid.py:1838)
-                for (int c = lane; c < a.force_sensor_width; c += kLanesPerEnv)
+                for (int c = lane; c < a.force_sensor_width; c += LB)
                     obs_e[L.self_step + c] = a.force_sensor[e * a.force_sensor_width + c];
             if (a.smpl_params)                                      // has_smpl_params, then has_limb_weight_params (humanoid.py:1724-1728)
-                for (int c = lane; c < a.smpl_params_width; c += kLanesPerEnv)
+                for (int c = lane; c < a.smpl_params_width; c += LB)
                     obs_e[L.self_step + fs_w + c] = a.smpl_params[e * a.smpl_params_stride + c];
             if (a.limb_weights)
-                for (int c = lane; c < a.limb_weights_width; c += kLanesPerEnv)
+                for (int c = lane; c < a.limb_weights_width; c += LB)
                     obs_e[L.self_step + fs_w + (a.smpl_params ? a.smpl_params_width : 0) + c] = a.limb_weights[e * a.limb_weights_stride + c];
         }
 
@@ -442,12 +450,13 @@ __global__ void __launch_bounds__(E * R * kLanesPerEnv) im_step_kernel(const pul
                 dx = x[J * 10 + 3 * b] - r[10]; dy = x[J * 10 + 3 * b + 1] - r[11]; dz = x[J * 10 + 3 * b + 2] - r[12];
                 e_ang = (dx * dx + dy * dy + dz * dz) / 3.0f;
             }
-            e_pos = group_sum(e_pos); e_rot = group_sum(e_rot);
-            e_vel = group_sum(e_vel); e_ang = group_sum(e_ang);
+            e_pos = group_sum<LB>(e_pos); e_rot = group_sum<LB>(e_rot);
+            e_vel = group_sum<LB>(e_vel); e_ang = group_sum<LB>(e_ang);
             float pw = 0.f;
             if (a.specs.power_reward) {
-                for (int d = lane; d < nd; d += kLanesPerEnv) pw += fabsf(df_e[d] * dv_e[d]);
-                pw = group_sum(pw);
+                if (lane < kPowerLanes)
+                    for (int d = lane; d < nd; d += kPowerLanes) pw += fabsf(df_e[d] * dv_e[d]);
+                pw = group_sum<LB>(pw);
             }
             if (lane == 0) {
                 const float fn = (float)nb;
@@ -498,10 +507,10 @@ __global__ void __launch_bounds__(E * R * kLanesPerEnv) im_step_kernel(const pul
             }
             int fallen;
             if (a.reset_use_mean) {
-                const float m = group_sum(dist) / (float)a.num_reset;
+                const float m = group_sum<LB>(dist) / (float)a.num_reset;
                 fallen = m > a.term_dist[a.reset_ids[0]];
             } else {
-                fallen = group_or(fell);
+                fallen = group_or<LB>(fell);
             }
             if (lane == 0) {
                 const bool pt = pass_time;
@@ -568,7 +577,7 @@ int pulse_im_step(const pulse_im_step_args* args, pulse_stream_t s) {
     const int count = a.env_ids ? a.num_ids : a.num_envs;
     if (count == 0 || (a.what & 15u) == 0) return PULSE_OK;
     PULSE_REQUIRE(a.rb != nullptr, "pulse_im_step: null rb");
-    PULSE_REQUIRE(a.num_bodies >= 1 && a.num_bodies <= kLanesPerEnv, "pulse_im_step: num_bodies %d not in [1,32]", a.num_bodies);
+    PULSE_REQUIRE(a.num_bodies >= 1 && a.num_bodies <= kImMaxBodies, "pulse_im_step: num_bodies %d not in [1,64]", a.num_bodies);
     PULSE_REQUIRE(a.rb_env_stride >= (int64_t)a.num_bodies * 13, "pulse_im_step: rb_env_stride too small");
     PULSE_REQUIRE(a.time_steps >= 1, "pulse_im_step: time_steps < 1");
     const bool do_obs = a.what & (PULSE_IM_SELF_OBS | PULSE_IM_TASK_OBS);
@@ -617,7 +626,7 @@ int pulse_im_step(const pulse_im_step_args* args, pulse_stream_t s) {
     if (a.what & PULSE_IM_RESET) {
         PULSE_REQUIRE(a.reset && a.terminate && a.term_dist, "pulse_im_step: null reset inputs/outputs");
         PULSE_REQUIRE(a.pass_time || a.clock_motion_len || a.cycle_motion, "pulse_im_step: reset needs pass_time or the in-kernel clock");
-        PULSE_REQUIRE(a.reset_ids && a.num_reset >= 1 && a.num_reset <= kLanesPerEnv, "pulse_im_step: bad reset ids");
+        PULSE_REQUIRE(a.reset_ids && a.num_reset >= 1 && a.num_reset <= kImMaxBodies, "pulse_im_step: bad reset ids (1 .. 64 of them)");
     }
     if (a.zero_out_far) {
         PULSE_REQUIRE(a.time_steps == 1, "pulse_im_step: zero_out_far takes one reference sample (the reference broadcasts (N, 3) against (N T, 3))");
@@ -631,6 +640,7 @@ int pulse_im_step(const pulse_im_step_args* args, pulse_stream_t s) {
         const int ov = a.obs_version;
         PULSE_REQUIRE(!(a.what & PULSE_IM_TASK_OBS) || ov == 6 || ov == 7 || ov == 8 || ov == 9,
                       "pulse_im_step: occl_bits is defined for obs_version 6 | 7 | 8 | 9 (humanoid_im.py:778,827), not %d", ov);
+        PULSE_REQUIRE(a.num_bodies <= 32, "pulse_im_step: occl_bits is one 32-bit word per env: num_bodies %d > 32", a.num_bodies);
         PULSE_REQUIRE(a.time_steps == 1, "pulse_im_step: occl_bits takes one reference sample (an (N, Jt) mask indexes an (N T, Jt, .) reference in the reference)");
         PULSE_REQUIRE(!a.occl_reset || a.num_track == a.num_bodies, "pulse_im_step: occl_reset indexes the mask by body id: every body must be tracked, in order");
     }
@@ -645,17 +655,24 @@ int pulse_im_step(const pulse_im_step_args* args, pulse_stream_t s) {
         PULSE_REQUIRE((a.track_dof_pos == nullptr) == (a.track_dof_vel == nullptr), "pulse_im_step: track_dof_pos / track_dof_vel go together");
         PULSE_REQUIRE(a.track_rb == nullptr || a.track_rb_stride >= 13 * a.num_bodies, "pulse_im_step: track_rb_stride too small");
     }
-    constexpr int E = 4;
+    // lane-group width: a half-wave per role up to 32 bodies, a whole wave for 33 .. 64 (or when the caller forces it: PULSE_IM_FORCE_WIDE)
+    const bool wide = a.num_bodies > 32 || ((a.what & PULSE_IM_RESET) && a.num_reset > 32) || (a.what & PULSE_IM_FORCE_WIDE);
+    // envs per workgroup: 4 narrow; 2 wide, so that the largest supported row (64 bodies, v6 over 3 samples: 10 304 floats per env) stays
+    // at 80.5 KiB of LDS and the SMPL-X row of env_pulsex_amp.yaml (4 544 floats, 35.5 KiB per workgroup) leaves room for 4 workgroups per CU
+    const int E = wide ? 2 : 4;
     const int J13p = (a.num_bodies * 13 + 3) & ~3;
     const int ndp = (a.num_dof + 3) & ~3;
     const int colsp = do_obs ? ((a.obs_cols + 3) & ~3) : 0;
     const size_t lds = sizeof(float) * (size_t)E * ((2 + a.time_steps) * J13p + 3 * ndp + colsp);
     PULSE_REQUIRE(lds <= 160 * 1024, "pulse_im_step: LDS request %zu > 160 KiB", lds);
     const unsigned grid = (unsigned)((count + E - 1) / E);
-    // a whole wave per env when both halves have work (task observation beside self observation / reward / reset): see the kernel's note
+    // two groups per env when both have work (task observation beside self observation / reward / reset): see the kernel's note
     const bool two = (a.what & PULSE_IM_TASK_OBS) && (a.what & (PULSE_IM_SELF_OBS | PULSE_IM_REWARD | PULSE_IM_RESET)) && g_im_two_roles;
-    const hipError_t e = two ? launch_dyn_lds<im_step_kernel<E, 2>>(dim3(grid), dim3(E * 2 * kLanesPerEnv), lds, as_stream(s), a)
-                             : launch_dyn_lds<im_step_kernel<E, 1>>(dim3(grid), dim3(E * kLanesPerEnv), lds, as_stream(s), a);
+    hipError_t e;
+    if (wide) e = two ? launch_dyn_lds<im_step_kernel<2, 2, 64>>(dim3(grid), dim3(2 * 2 * 64), lds, as_stream(s), a)
+                      : launch_dyn_lds<im_step_kernel<2, 1, 64>>(dim3(grid), dim3(2 * 64), lds, as_stream(s), a);
+    else e = two ? launch_dyn_lds<im_step_kernel<4, 2, 32>>(dim3(grid), dim3(4 * 2 * 32), lds, as_stream(s), a)
+                 : launch_dyn_lds<im_step_kernel<4, 1, 32>>(dim3(grid), dim3(4 * 32), lds, as_stream(s), a);
     if (e != hipSuccess) return fail(PULSE_ERR_LAUNCH, "pulse_im_step: cannot raise LDS limit: %s", hipGetErrorString(e));
     return check_launch("pulse_im_step");
 }

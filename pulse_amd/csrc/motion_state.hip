@@ -5,8 +5,9 @@
 // lerp of position (+ per-env offset), velocity and angular velocity, slerp of the global rotation, and for every
 // dof joint slerp of the LOCAL rotation -> exp-map (dof_pos) and lerp of the dof velocity.
 //
-// Mapping: a 32-lane half-wave per query (8 queries per 256-thread block); lane j <-> body j and dof joint j (= body
-// j+1).  The two frame records are contiguous 1920-B rows of the packed table (include/pulse_hip.h section 2b), so the
+// Mapping: a 32-lane half-wave per query (8 queries per 256-thread block) up to 32 bodies, a whole wave per query (4 per
+// block) for 33 .. 64; lane j <-> body j and dof joint j (= body j+1).  The two frame records are contiguous rows of the
+// packed table (1920 B for SMPL, 4160 B for SMPL-X; include/pulse_hip.h section 2b), so the
 // per-field reads of adjacent lanes are adjacent addresses: the gather costs whole cache lines of two rows instead of
 // twelve scattered table rows.  Irregular-gather / HBM bound: 2 x 1908 B read, <= 1.85 KB written per query.
 // Compiled with -ffp-contract=off (reference operation order: (1-b)*x0 + b*x1 [+ offset]).
@@ -14,8 +15,8 @@
 
 namespace pulse {
 
-constexpr int kMsLanes = 32;
-constexpr int kMsQueries = 8;
+constexpr int kMsThreads = 256;
+constexpr int kMsMaxBodies = 64;
 
 __device__ __forceinline__ float query_time(const pulse_motion_state_args& a, long long i, long long e) {
     if (a.motion_times) return a.motion_times[i];
@@ -26,9 +27,11 @@ __device__ __forceinline__ float query_time(const pulse_motion_state_args& a, lo
     return t;
 }
 
-__global__ void __launch_bounds__(kMsQueries * kMsLanes) motion_state_kernel(const pulse_motion_state_args a) {
-    const int slot = threadIdx.x / kMsLanes, lane = threadIdx.x % kMsLanes;
-    const long long i = (long long)blockIdx.x * kMsQueries + slot;
+// LB lanes per query (32 | 64), kMsThreads / LB queries per block; every lane works on its own body: no cross-lane traffic
+template <int LB>
+__global__ void __launch_bounds__(kMsThreads) motion_state_kernel(const pulse_motion_state_args a) {
+    const int slot = threadIdx.x / LB, lane = threadIdx.x % LB;
+    const long long i = (long long)blockIdx.x * (kMsThreads / LB) + slot;
     if (i >= a.n) return;
     const pulse_motion_tables& T = a.tab;
     const long long e = a.motion_times ? i : i / (a.time_steps > 1 ? a.time_steps : 1);     // per-env arrays in clock mode
@@ -108,7 +111,7 @@ extern "C" int pulse_motion_state(const pulse_motion_state_args* args, pulse_str
     PULSE_REQUIRE(a.n >= 0, "pulse_motion_state: negative query count");
     if (a.n == 0) return PULSE_OK;
     PULSE_REQUIRE(T.frames && T.motion_lengths && T.motion_dt && T.motion_num_frames && T.length_starts, "pulse_motion_state: null table pointer");
-    PULSE_REQUIRE(T.num_bodies >= 1 && T.num_bodies <= kMsLanes, "pulse_motion_state: num_bodies must be in [1, 32]");
+    PULSE_REQUIRE(T.num_bodies >= 1 && T.num_bodies <= kMsMaxBodies, "pulse_motion_state: num_bodies %d not in [1,64]", T.num_bodies);
     PULSE_REQUIRE(T.frame_stride % 4 == 0 && T.off_grs % 4 == 0 && T.off_lrs % 4 == 0, "pulse_motion_state: record pitch / quaternion fields must be 16-B aligned");
     PULSE_REQUIRE(T.off_gts >= 0 && T.off_grs >= 0 && T.off_lrs >= 0 && T.off_gvs >= 0 && T.off_gavs >= 0 && T.off_dvs >= 0, "pulse_motion_state: negative field offset");
     PULSE_REQUIRE(a.motion_ids != nullptr, "pulse_motion_state: null motion_ids");
@@ -117,7 +120,9 @@ extern "C" int pulse_motion_state(const pulse_motion_state_args* args, pulse_str
     PULSE_REQUIRE(!a.root_only || a.root_pos != nullptr, "pulse_motion_state: root_only needs root_pos");
     PULSE_REQUIRE(a.motion_times != nullptr || a.time_steps <= 1 || a.n % a.time_steps == 0, "pulse_motion_state: n must be num_envs * time_steps");
     PULSE_REQUIRE(a.rb_records == nullptr || a.rb_query_stride >= 13 * T.num_bodies, "pulse_motion_state: rb_query_stride too small");
-    const long long blocks = (a.n + kMsQueries - 1) / kMsQueries;
-    hipLaunchKernelGGL(motion_state_kernel, dim3((unsigned)blocks), dim3(kMsQueries * kMsLanes), 0, as_stream(s), a);
+    const int per_block = kMsThreads / (T.num_bodies > 32 ? 64 : 32);
+    const long long blocks = (a.n + per_block - 1) / per_block;
+    if (T.num_bodies > 32) hipLaunchKernelGGL(motion_state_kernel<64>, dim3((unsigned)blocks), dim3(kMsThreads), 0, as_stream(s), a);
+    else hipLaunchKernelGGL(motion_state_kernel<32>, dim3((unsigned)blocks), dim3(kMsThreads), 0, as_stream(s), a);
     return check_launch("pulse_motion_state");
 }

@@ -46,11 +46,55 @@ class Box:
         self.high = np.full(self.shape, high, dtype=np.float32)
 
 
+def _env_dict(cfg):
+    env = cfg.get("env", cfg)
+    if "env" in env and isinstance(env["env"], dict):                           # legacy layout (phc_*_iccv.yaml): options nested under env:
+        env = env["env"]
+    return env
+
+
+def check_humanoid_options(cfg, task="HumanoidIm"):
+    """``cfg.robot.humanoid_type`` (humanoid.py:247-248; default 'smpl') and what is built for it.  Returns the humanoid type; raises
+    NotImplementedError by name for a humanoid or a combination that is not built.  Needs no device: HumanoidIm, HumanoidImGetup and the
+    downstream tasks call it first thing (the amp_z network checks its own latent width, learning/network_z.py).
+    SMPL-X / SMPL-H (52 bodies, 153 dofs; robot/smplx_humanoid.yaml, env_pulsex_amp.yaml) run the imitation step and the motion query; the
+    rest of the 52-body surface raises here."""
+    robot = cfg.get("robot", None) if isinstance(cfg, dict) else None
+    robot = robot if isinstance(robot, dict) else {}
+    ht = robot.get("humanoid_type", "smpl")
+    syn.skeleton(ht)                                                            # unknown type: NotImplementedError naming it
+    if ht == "smpl":
+        return ht
+    env = _env_dict(cfg)
+    opt = lambda k, d=False: env.get(k, robot.get(k, d))
+    not_built = lambda what, why: NotImplementedError(f"humanoid_type {ht!r} with {what}: not built -- {why}")
+    if task != "HumanoidIm":
+        raise not_built(task, "the get-up task (humanoid_im_getup.py) and the downstream tasks of env/humanoid_tasks.py (humanoid_speed.py, "
+                              "humanoid_reach.py, humanoid_strike.py, humanoid_pedestrian_terrain.py) are built for the 24-body SMPL humanoid")
+    if opt("enable_amp_obs"):
+        raise not_built("enable_amp_obs", "the AMP frame kernel maps lane = body inside 32 lanes and the 10-step window of the 52-body frame "
+                                          "(4 840 columns, humanoid_amp.py:91-118, 925-969) exceeds amp_obs.hip's kAmpMaxW and the normaliser's 3072 columns")
+    if opt("occl_training"):
+        raise not_built("occl_training", "the reference's mask update indexes columns 9 .. 23 (humanoid_im.py:1046-1058) and the step kernel "
+                                         "packs the mask into one 32-bit word per env")
+    for k in ("has_shape_obs", "has_weight_obs"):
+        if opt(k):
+            raise not_built(k, "the shape / limb-weight rows (humanoid.py:266-268, 657-661, 739-878) are filled from SMPL assets")
+    if opt("distill") or opt("save_kin_info"):
+        raise not_built("distill / save_kin_info", "the distillation teacher (humanoid_im_distill.py:44-63, 143-231) is a 24-body PHC policy")
+    if env.get("z_type") is not None or "embedding_size" in env:
+        raise not_built("z_type / embedding_size (the amp_z network)", "PULSE-X uses 48 latents (env_pulsex_amp.yaml; amp_network_z_builder.py:32) and vae_head.hip holds "
+                                                                       "embedding_size <= 32")
+    return ht
+
+
 class HumanoidIm:
     def __init__(self, cfg, sim, motion_lib, device="cuda:0"):
-        env = cfg.get("env", cfg)
-        if "env" in env and isinstance(env["env"], dict):                       # legacy layout (phc_*_iccv.yaml): options nested under env:
-            env = env["env"]
+        # cfg.robot.humanoid_type is read from the robot dict directly (not merged into the env options, whose keys are audited below)
+        getup = any(c.__name__ == "HumanoidImGetup" for c in type(self).__mro__)          # (any other subclass is the imitation task)
+        self.humanoid_type = check_humanoid_options(cfg, "HumanoidImGetup" if getup else "HumanoidIm")
+        self.skeleton = sk = syn.skeleton(self.humanoid_type)
+        env = _env_dict(cfg)
         if isinstance(cfg.get("robot", None), dict):                            # robot/*.yaml switches (humanoid.py:266-280 reads cfg.robot)
             env = dict({k: v for k, v in cfg["robot"].items() if k in ("has_upright_start", "has_dof_subset", "has_shape_obs", "has_weight_obs")}, **env)
         env_keys.audit(env, type(self).__name__)                               # every key is honoured, inert by contract, or raises by name
@@ -60,7 +104,13 @@ class HumanoidIm:
         self.num_envs = sim.num_envs
         if "num_envs" in env and int(env["num_envs"]) != self.num_envs:
             raise ValueError(f"env.num_envs = {env['num_envs']} but the injected simulator has {self.num_envs} envs")
-        self.num_bodies = syn.NUM_BODIES
+        self.num_bodies = sk["num_bodies"]
+        self._body_names = names = sk["body_names"]
+        sim_bodies = getattr(sim, "rigid_body_state", None)
+        if sim_bodies is not None and sim_bodies.shape[-2] != self.num_bodies:
+            raise ValueError(f"humanoid_type {self.humanoid_type!r} has {self.num_bodies} bodies but the injected simulator has {sim_bodies.shape[-2]}")
+        if getattr(motion_lib, "num_bodies", self.num_bodies) != self.num_bodies:
+            raise ValueError(f"humanoid_type {self.humanoid_type!r} has {self.num_bodies} bodies but the motion library has {motion_lib.num_bodies}")
         self.dt = int(env.get("controlFrequencyInv", 2)) / 60.0                 # base_task.py:92-93: control_freq_inv * sim dt (1 / 60 s, sim/default_sim.yaml)
         self.obs_v = int(env.get("obs_v", 6))
         self.self_obs_v = int(env.get("self_obs_v", 1))
@@ -132,12 +182,12 @@ class HumanoidIm:
         if env.get("stateInit", "Random") not in ("Random", "Start"):
             raise NotImplementedError(f"stateInit {env.get('stateInit')!r}: Random and Start are built (Default / Hybrid need the simulator's "
                                       "default pose, humanoid_amp.py:447-505)")
-        track = env.get("trackBodies", syn.SMPL_BODY_NAMES)
-        reset = env.get("reset_bodies", syn.RESET_BODY_NAMES)
-        self._track_bodies_id = torch.tensor([syn.SMPL_BODY_NAMES.index(b) for b in track], dtype=torch.int32, device=self.device)
-        self._reset_bodies_id = torch.tensor([syn.SMPL_BODY_NAMES.index(b) for b in reset], dtype=torch.int32, device=self.device)
+        track = env.get("trackBodies", sk["track_bodies"])
+        reset = env.get("reset_bodies", sk["reset_bodies"])
+        self._track_bodies_id = torch.tensor([names.index(b) for b in track], dtype=torch.int32, device=self.device)
+        self._reset_bodies_id = torch.tensor([names.index(b) for b in reset], dtype=torch.int32, device=self.device)
         self._termination_distances = torch.full((self.num_bodies,), float(env.get("terminationDistance", 0.25)), device=self.device)
-        self._dof_size = syn.NUM_DOF
+        self._dof_size = sk["num_dof"]
         self._pd_action_offset = torch.zeros(self._dof_size, device=self.device)
         self._pd_action_scale = torch.ones(self._dof_size, device=self.device)
         self.clip_obs = float("inf")                                            # parse_task.py:68
@@ -231,16 +281,15 @@ class HumanoidIm:
         if self._enable_amp_obs:
             self._num_amp_obs_steps = int(env.get("numAMPObsSteps", 10))
             self._amp_root_height_obs = bool(env.get("ampRootHeightObs", env.get("root_height_obs", True)))
-            self._key_body_ids = torch.tensor([syn.SMPL_BODY_NAMES.index(b) for b in env.get("key_bodies", ["R_Ankle", "L_Ankle", "R_Wrist", "L_Wrist"])],
+            self._key_body_ids = torch.tensor([names.index(b) for b in env.get("key_bodies", sk["key_bodies"])],
                                               dtype=torch.int32, device=dev)
             # dof_subset (humanoid.py:396-421): every joint but L_Hand / R_Hand / L_Toe / R_Toe; applied when the robot config says
             # has_dof_subset (True in robot/smpl_humanoid.yaml:6) -> 19 joints, 196 floats per frame, 1960 per window.  For SMPL the
             # subset tensor always exists, so the in-place zeroing of the toe / hand dofs (humanoid_amp.py:636-639, guarded by
             # ``dof_subset is None``) never runs on this humanoid.
             self._has_dof_subset = bool(env.get("has_dof_subset", True))
-            removed = {syn.SMPL_BODY_NAMES.index(b) - 1 for b in ("L_Hand", "R_Hand", "L_Toe", "R_Toe")}
-            nj = syn.NUM_DOF // 3
-            self._amp_joint_ids = [j for j in range(nj) if j not in removed] if self._has_dof_subset else None
+            nj = self._dof_size // 3
+            self._amp_joint_ids = [d // 3 for d in sk["dof_subset"][::3]] if self._has_dof_subset else None
             self._amp_zero_joints = ()
             self._num_amp_obs_per_step = ops.amp_obs_width(len(self._amp_joint_ids) if self._has_dof_subset else nj, self._key_body_ids.numel(),
                                                            self._amp_root_height_obs)
@@ -257,7 +306,6 @@ class HumanoidIm:
             self.kin_dict = {"gt_action": torch.zeros(n, self.num_actions, device=dev),
                              "progress_buf": torch.zeros(n, dtype=torch.int64, device=dev)}
         self._teacher = None
-        self.humanoid_type = "smpl"
         self.has_task = True
         self.viewer = None
 

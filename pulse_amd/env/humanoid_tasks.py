@@ -29,6 +29,8 @@ class HumanoidTask:
     TASK = None
 
     def __init__(self, cfg, sim, device="cuda:0"):
+        from .humanoid_im import check_humanoid_options
+        check_humanoid_options(cfg, type(self).__name__)     # cfg.robot.humanoid_type: the downstream tasks are built for SMPL (raises by name otherwise)
         env = cfg.get("env", cfg)
         env_keys.audit(env, type(self).__name__)             # every key is honoured, inert by contract, or raises by name
         self.cfg, self.sim = cfg, sim
@@ -302,6 +304,8 @@ class HumanoidTraj(HumanoidTask):
     TERRAIN_OBS = False
 
     def __init__(self, cfg, sim, device="cuda:0"):
+        from .humanoid_im import check_humanoid_options
+        check_humanoid_options(cfg, type(self).__name__)     # before the height points go to the device
         env = cfg.get("env", cfg)
         self._num_traj_samples = int(env.get("numTrajSamples", 10))
         self._traj_sample_timestep = float(env.get("trajSampleTimestep", 0.5))

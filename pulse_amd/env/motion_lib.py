@@ -34,6 +34,18 @@ def _round4(n):
 class MotionLib:
     FIELDS = ("gts", "grs", "lrs", "gvs", "gavs", "dvs")
 
+    @staticmethod
+    def record_layout(num_bodies):
+        """(offsets, frame_stride) of the packed frame record of a ``num_bodies`` humanoid, in floats.  Quaternion fields first, so that they
+        sit on 16-B boundaries for any body count: [grs | lrs | gts | gvs | gavs | dvs | pad to a multiple of 4]."""
+        j = num_bodies
+        widths = {"grs": j * 4, "lrs": j * 4, "gts": j * 3, "gvs": j * 3, "gavs": j * 3, "dvs": (j - 1) * 3}
+        offsets, off = {}, 0
+        for k, w in widths.items():
+            offsets[k] = off
+            off += w
+        return offsets, _round4(off), widths
+
     def __init__(self, tables, device="cuda:0"):
         dev = torch.device(device)
         if dev.type != "cuda":
@@ -43,14 +55,8 @@ class MotionLib:
         total, j = gts.shape[0], gts.shape[1]
         self.num_bodies = j
         self.num_dof = (j - 1) * 3
-        widths = {"gts": j * 3, "grs": j * 4, "lrs": j * 4, "gvs": j * 3, "gavs": j * 3, "dvs": (j - 1) * 3}
-        # quaternion fields on 16-B boundaries: order [grs | lrs | gts | gvs | gavs | dvs] keeps them aligned for any J
-        order = ("grs", "lrs", "gts", "gvs", "gavs", "dvs")
-        self.offsets, off = {}, 0
-        for k in order:
-            self.offsets[k] = off
-            off += widths[k]
-        self.frame_stride = _round4(off)
+        self.offsets, self.frame_stride, widths = self.record_layout(j)
+        order = tuple(widths)
         frames = torch.zeros(total, self.frame_stride, dtype=torch.float32, device=dev)
         for k in order:
             t = tables[k]

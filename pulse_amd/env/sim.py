@@ -18,9 +18,11 @@ from .. import synthetic as syn
 class RecordedRollout:
     """frames[f] for f in 0..num_frames-1: everything one env step reads."""
 
-    def __init__(self, num_envs, num_frames, seed=1234, rank=0, done_rate=0.02):
+    def __init__(self, num_envs, num_frames, seed=1234, rank=0, done_rate=0.02, humanoid="smpl"):
         g = syn.make_generator(seed, rank)
         self.num_envs, self.num_frames = num_envs, num_frames
+        self.skeleton = sk = syn.skeleton(humanoid)
+        nb, nd, head = sk["num_bodies"], sk["num_dof"], sk["body_names"].index("Head")
         n = num_envs
         keys = ("rb", "reset_rb", "dof_force", "dof_vel", "gt_action", "dof_pos")
         self.data = {k: [] for k in keys}
@@ -28,7 +30,7 @@ class RecordedRollout:
         self.ref_next = {k: [] for k in ("pos", "rot", "vel", "ang")}
         self.ref_next_reset = {k: [] for k in ("pos", "rot", "vel", "ang")}
         for _ in range(num_frames):
-            d = syn.env_step_inputs(g, n, edge_cases=False)
+            d = syn.env_step_inputs(g, n, edge_cases=False, humanoid=sk)
             self.data["rb"].append(d["rb"])
             self.data["dof_force"].append(d["dof_force"])
             self.data["dof_vel"].append(d["dof_vel"])
@@ -37,9 +39,9 @@ class RecordedRollout:
                 self.ref_next[k].append(d["ref_next"][k])
             # stand-in for the frozen PHC teacher's action on this frame (humanoid_im_distill.py:143-231; needs released
             # checkpoints, so the distillation target is synthetic)
-            self.data["gt_action"].append((0.4 * torch.randn(n, syn.NUM_DOF, generator=g)).clamp(-1, 1))
-            self.data["dof_pos"].append(0.5 * torch.randn(n, syn.NUM_DOF, generator=g))       # exp-map joint angles
-            rrb = syn.rigid_body_state(g, n)
+            self.data["gt_action"].append((0.4 * torch.randn(n, nd, generator=g)).clamp(-1, 1))
+            self.data["dof_pos"].append(0.5 * torch.randn(n, nd, generator=g))       # exp-map joint angles
+            rrb = syn.rigid_body_state(g, n, nb)
             self.data["reset_rb"].append(rrb)
             rr = syn.reference_frame(g, rrb)
             for k in self.ref_next_reset:
@@ -55,7 +57,7 @@ class RecordedRollout:
         self.init_progress = torch.randint(0, 40, (n,), generator=g, dtype=torch.int64)
         # some envs drift far from their reference -> early termination
         far = torch.rand(num_frames, n, generator=g) < done_rate / 2
-        self.ref_now["pos"][:, :, 13, :] += far[..., None].float() * 1.0
+        self.ref_now["pos"][:, :, head, :] += far[..., None].float() * 1.0
 
     def to(self, device):
         self.data = {k: v.to(device) for k, v in self.data.items()}
@@ -81,7 +83,8 @@ class RecordedSim:
         self.dof_force = rollout.data["dof_force"][0].clone()
         self.dof_vel = rollout.data["dof_vel"][0].clone()
         self.dof_pos = rollout.data["dof_pos"][0].clone()
-        self.pd_targets = torch.zeros(n, syn.NUM_DOF, device=dev)
+        self.skeleton = rollout.skeleton
+        self.pd_targets = torch.zeros(n, self.skeleton["num_dof"], device=dev)
 
     @property
     def gt_action(self):
@@ -128,13 +131,14 @@ class RecordedMotion:
         """Synthetic stand-in for the motion-library states behind fetch_amp_obs_demo (humanoid_amp.py:215-284):
         ``count`` random reference poses -> (rb records (count, 24, 13), dof_pos, dof_vel), drawn on the device."""
         dev, g = self.rollout.data["rb"].device, self._demo_gen
-        rb = torch.randn(count, syn.NUM_BODIES, syn.RB_WIDTH, device=dev, generator=g)
+        sk = self.rollout.skeleton
+        rb = torch.randn(count, sk["num_bodies"], syn.RB_WIDTH, device=dev, generator=g)
         rb[..., 0:3] *= 0.3
         rb[:, :, 2] += 0.9
         q = rb[..., 3:7]
         rb[..., 3:7] = q / q.norm(dim=-1, keepdim=True)
-        dof_pos = 0.4 * torch.randn(count, syn.NUM_DOF, device=dev, generator=g)
-        dof_vel = 0.8 * torch.randn(count, syn.NUM_DOF, device=dev, generator=g)
+        dof_pos = 0.4 * torch.randn(count, sk["num_dof"], device=dev, generator=g)
+        dof_vel = 0.8 * torch.randn(count, sk["num_dof"], device=dev, generator=g)
         return rb, dof_pos, dof_vel
 
     def now(self):
@@ -157,9 +161,10 @@ class KinematicSim:
     (humanoid_amp.py:447-488, humanoid_im.py:966-986) writes the motion state unperturbed.  Same tensor surface as
     RecordedSim.  The noise bank is generated on the CPU (pulse_amd/synthetic.py generator) so a CPU twin can replay it."""
 
-    def __init__(self, num_envs, bank_frames, device, seed=1234, rank=0, drift_rate=0.01):
+    def __init__(self, num_envs, bank_frames, device, seed=1234, rank=0, drift_rate=0.01, humanoid="smpl"):
         g = syn.make_generator(seed + 17, rank)
-        n, j, f = num_envs, syn.NUM_BODIES, bank_frames
+        self.skeleton = sk = syn.skeleton(humanoid)
+        n, j, f, nd = num_envs, sk["num_bodies"], bank_frames, sk["num_dof"]
         self.num_envs, self.bank_frames = n, f
         noise = torch.randn(f, n, j, syn.RB_WIDTH, generator=g)
         noise[..., 0:3] *= 0.03
@@ -167,18 +172,18 @@ class KinematicSim:
         noise[..., 7:10] *= 0.15
         noise[..., 10:13] *= 0.3
         far = torch.rand(f, n, generator=g) < drift_rate          # some envs lose their reference -> early termination
-        noise[:, :, 13, 0:3] += far[..., None].float() * 1.0
-        self.bank = {"rb": noise, "dof_force": 50.0 * torch.randn(f, n, syn.NUM_DOF, generator=g),
-                     "dof_pos": 0.02 * torch.randn(f, n, syn.NUM_DOF, generator=g), "dof_vel": 0.1 * torch.randn(f, n, syn.NUM_DOF, generator=g),
-                     "gt_action": (0.4 * torch.randn(f, n, syn.NUM_DOF, generator=g)).clamp(-1, 1)}
+        noise[:, :, sk["body_names"].index("Head"), 0:3] += far[..., None].float() * 1.0
+        self.bank = {"rb": noise, "dof_force": 50.0 * torch.randn(f, n, nd, generator=g),
+                     "dof_pos": 0.02 * torch.randn(f, n, nd, generator=g), "dof_vel": 0.1 * torch.randn(f, n, nd, generator=g),
+                     "gt_action": (0.4 * torch.randn(f, n, nd, generator=g)).clamp(-1, 1)}
         self.bank = {k: v.to(device) for k, v in self.bank.items()}
         self.frame = 0
         self.rigid_body_state = torch.zeros(n, j, syn.RB_WIDTH, device=device)
         self.rigid_body_state[..., 6] = 1.0
         self.dof_force = self.bank["dof_force"][0].clone()
-        self.dof_vel = torch.zeros(n, syn.NUM_DOF, device=device)
-        self.dof_pos = torch.zeros(n, syn.NUM_DOF, device=device)
-        self.pd_targets = torch.zeros(n, syn.NUM_DOF, device=device)
+        self.dof_vel = torch.zeros(n, nd, device=device)
+        self.dof_pos = torch.zeros(n, nd, device=device)
+        self.pd_targets = torch.zeros(n, nd, device=device)
         self._target = None
 
     @property
@@ -210,14 +215,15 @@ class PdSim(KinematicSim):
     by the return-parity experiment (tools/return_parity.py) -- the bench keeps KinematicSim.  The CPU twin is
     oracle/pd_sim_oracle.py; both draw the disturbance bank with the same generator recipe."""
 
-    def __init__(self, num_envs, bank_frames, device, seed=1234, rank=0):
-        super().__init__(num_envs, bank_frames, device, seed=seed, rank=rank)
+    def __init__(self, num_envs, bank_frames, device, seed=1234, rank=0, humanoid="smpl"):
+        super().__init__(num_envs, bank_frames, device, seed=seed, rank=rank, humanoid=humanoid)
         g = syn.make_generator(seed + 23, rank)
-        self.bank["acc"] = (syn.PD_SIM["noise_acc"] * torch.randn(bank_frames, num_envs, syn.NUM_DOF, generator=g)).to(device)
-        sag, u = syn.pd_sim_tables()
+        nd = self.skeleton["num_dof"]
+        self.bank["acc"] = (syn.PD_SIM["noise_acc"] * torch.randn(bank_frames, num_envs, nd, generator=g)).to(device)
+        sag, u = syn.pd_sim_tables(self.skeleton)
         self._sag, self._lever_dir = sag.to(device), u.to(device).contiguous()
-        self.err = torch.zeros(num_envs, syn.NUM_DOF, device=device)
-        self.err_vel = torch.zeros(num_envs, syn.NUM_DOF, device=device)
+        self.err = torch.zeros(num_envs, nd, device=device)
+        self.err_vel = torch.zeros(num_envs, nd, device=device)
         self.dt = 2.0 / 60.0
         self._reset_mask = torch.zeros(num_envs, dtype=torch.uint8, device=device)
 
@@ -226,7 +232,7 @@ class PdSim(KinematicSim):
         self.frame = (self.frame + 1) % self.bank_frames
         t, c = self._target, syn.PD_SIM
         a = _lib.PdSimArgs()
-        a.num_envs, a.num_bodies = self.num_envs, syn.NUM_BODIES
+        a.num_envs, a.num_bodies = self.num_envs, self.skeleton["num_bodies"]
         a.target_rb, a.target_dof_pos, a.target_dof_vel = t["rb_records"].data_ptr(), t["dof_pos"].data_ptr(), t["dof_vel"].data_ptr()
         act = self.pd_targets.contiguous()
         a.action, a.noise_acc = act.data_ptr(), self.bank["acc"][self.frame].data_ptr()

@@ -31,6 +31,9 @@ class AMPZNetwork:
         self.device = torch.device(device)
         d = task_obs_size_detail
         self.embedding_size = int(d.get("embedding_size", 32))
+        if self.embedding_size > 32:
+            raise NotImplementedError(f"amp_z with embedding_size {self.embedding_size}: the VAE head kernels map lane = latent inside 32 lanes "
+                                      "(vae_head.hip: embedding_size <= 32); PULSE-X's 48 latents (env_pulsex_amp.yaml) are not built")
         self.z_type = d.get("z_type", "vae")
         if self.z_type != "vae":
             raise NotImplementedError("only z_type 'vae' (the shipped PULSE configuration) is built")

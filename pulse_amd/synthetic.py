@@ -30,6 +30,46 @@ RESET_BODY_IDS = [SMPL_BODY_NAMES.index(n) for n in RESET_BODY_NAMES]
 VR_TRACK_BODY_IDS = [SMPL_BODY_NAMES.index(n) for n in ('Head', 'L_Hand', 'R_Hand')]  # env_pulse_im.yaml:71-72
 
 
+# SMPL-X / SMPL-H: 52 bodies, 153 dofs (humanoid.py:376-377, robot/smplx_humanoid.yaml).  The reference takes the list from smpl_sim
+# (SMPLH_MUJOCO_NAMES); here the names are written in the order in which the reference itself spells them (humanoid.py:406-411,
+# humanoid_im.py:628).  The order matters only for name-to-index lookups (track / reset / key bodies): the kernels see indices.
+_FINGERS = [f"{f}{k}" for f in ("Index", "Middle", "Pinky", "Ring", "Thumb") for k in (1, 2, 3)]
+SMPLX_BODY_NAMES = (['Pelvis', 'L_Hip', 'L_Knee', 'L_Ankle', 'L_Toe', 'R_Hip', 'R_Knee', 'R_Ankle', 'R_Toe',
+                     'Torso', 'Spine', 'Chest', 'Neck', 'Head', 'L_Thorax', 'L_Shoulder', 'L_Elbow', 'L_Wrist'] + ["L_" + f for f in _FINGERS] +
+                    ['R_Thorax', 'R_Shoulder', 'R_Elbow', 'R_Wrist'] + ["R_" + f for f in _FINGERS])
+
+
+def _smplx_parents():
+    """Legs, spine chain and arms as in the SMPL tree; every finger a chain of three rooted at the wrist."""
+    par = [-1, 0, 1, 2, 3, 0, 5, 6, 7, 0, 9, 10, 11, 12]
+    for _ in ("L", "R"):
+        base = len(par)                                   # the thorax
+        par += [11, base, base + 1, base + 2]
+        wrist = base + 3
+        for f in range(5):
+            first = wrist + 1 + 3 * f
+            par += [wrist, first, first + 1]
+    return par
+
+
+def _skeleton(names, parents, dof_removed, reset_excluded):
+    return {"body_names": list(names), "parents": list(parents), "num_bodies": len(names), "num_dof": 3 * (len(names) - 1),
+            # dof_subset (humanoid.py:396-421): the dofs of every joint but the removed ones
+            "dof_subset": [3 * (i - 1) + k for i, b in enumerate(names) if i > 0 and b not in dof_removed for k in range(3)],
+            "track_bodies": list(names),                                                   # full-body tracking
+            "reset_bodies": [b for b in names if b not in reset_excluded],                 # every body except the ankles / toes
+            "key_bodies": ["R_Ankle", "L_Ankle", "R_Wrist", "L_Wrist"]}
+
+
+def skeleton(humanoid="smpl"):
+    """The description of a humanoid: a key of SKELETONS ('smpl' | 'smplh' | 'smplx') or a description dict itself."""
+    if isinstance(humanoid, dict):
+        return humanoid
+    if humanoid not in SKELETONS:
+        raise NotImplementedError(f"humanoid_type {humanoid!r}: 'smpl', 'smplh' and 'smplx' are built (humanoid.py:374-377)")
+    return SKELETONS[humanoid]
+
+
 def make_generator(seed=1234, rank=0):
     g = torch.Generator(device="cpu")
     g.manual_seed(seed + rank)
@@ -86,13 +126,14 @@ def reference_frame(g, rb, pos_sigma=0.05, max_angle=0.3, vel_sigma=0.1):
     }
 
 
-def env_step_inputs(g, n, edge_cases=True):
+def env_step_inputs(g, n, edge_cases=True, humanoid="smpl"):
     """All inputs of one HumanoidIm.post_physics_step for n envs."""
-    rb = rigid_body_state(g, n)
+    sk = skeleton(humanoid)
+    rb = rigid_body_state(g, n, sk["num_bodies"])
     ref_now = reference_frame(g, rb)
     ref_next = reference_frame(g, rb)
-    dof_force = 50.0 * _randn(g, n, NUM_DOF)
-    dof_vel = _randn(g, n, NUM_DOF)
+    dof_force = 50.0 * _randn(g, n, sk["num_dof"])
+    dof_vel = _randn(g, n, sk["num_dof"])
     progress = torch.randint(0, 300, (n,), generator=g, dtype=torch.int64)
     pass_time = _rand(g, n) < 0.02
     if edge_cases and n >= 8:
@@ -136,6 +177,12 @@ def rollout_scalars(g, t, n, done_p=0.02):
 # (forward kinematics over SMPL_PARENTS), velocities by finite differences like SkeletonMotion does.
 # ---------------------------------------------------------------------------------------------------------------------
 SMPL_PARENTS = [-1, 0, 1, 2, 3, 0, 5, 6, 7, 0, 9, 10, 11, 12, 11, 14, 15, 16, 17, 11, 19, 20, 21, 22]
+SMPLX_PARENTS = _smplx_parents()
+
+_ANKLES_TOES = ("L_Ankle", "L_Toe", "R_Ankle", "R_Toe")
+SKELETONS = {"smpl": _skeleton(SMPL_BODY_NAMES, SMPL_PARENTS, ("L_Hand", "R_Hand", "L_Toe", "R_Toe"), _ANKLES_TOES),
+             "smplx": _skeleton(SMPLX_BODY_NAMES, SMPLX_PARENTS, ("L_Toe", "R_Toe"), _ANKLES_TOES)}       # humanoid.py:404-405
+SKELETONS["smplh"] = SKELETONS["smplx"]                                                                  # humanoid.py:376: the same 52 bodies
 
 
 def _exp_map_to_quat_xyzw(e):
@@ -151,9 +198,12 @@ def _quat_rotate_xyzw(q, v):
     return v + w * t + torch.cross(qv, t, dim=-1)
 
 
-def synthetic_motion_library(g, num_motions, min_frames=45, max_frames=180, fps=30.0):
-    """dict of CPU tensors in the reference's table layout; frame f of motion m sits at length_starts[m] + f."""
-    m, j = num_motions, NUM_BODIES
+def synthetic_motion_library(g, num_motions, min_frames=45, max_frames=180, fps=30.0, humanoid="smpl"):
+    """dict of CPU tensors in the reference's table layout; frame f of motion m sits at length_starts[m] + f.  ``humanoid``: a key of
+    SKELETONS or a description dict (``parents`` is all that is read: any tree whose parents precede their children)."""
+    sk = skeleton(humanoid)
+    parents = sk["parents"]
+    m, j = num_motions, len(parents)
     num_frames = torch.randint(min_frames, max_frames + 1, (m,), generator=g, dtype=torch.int64)
     starts = torch.cumsum(num_frames, 0) - num_frames
     total = int(num_frames.sum())
@@ -180,7 +230,7 @@ def synthetic_motion_library(g, num_motions, min_frames=45, max_frames=180, fps=
     grs = torch.empty(total, j, 4)
     gts = torch.empty(total, j, 3)
     for b in range(j):
-        p = SMPL_PARENTS[b]
+        p = parents[b]
         if p < 0:
             grs[:, b], gts[:, b] = lrs[:, b], root
         else:
@@ -222,12 +272,13 @@ def synthetic_motion_library(g, num_motions, min_frames=45, max_frames=180, fps=
 PD_SIM = {"kp": 400.0, "kd": 40.0, "substeps": 2, "action_scale": 0.25, "lever": 0.3, "noise_acc": 2.0}
 
 
-def pd_sim_tables():
-    """(sag (69,), lever_dir (24, 3)): a constant per-joint offset of the PD set point the policy has to learn to cancel, and the unit
-    'bone' directions that turn a joint-angle error into a body displacement.  Deterministic (no RNG state involved)."""
-    j = torch.arange(NUM_DOF, dtype=torch.float32)
+def pd_sim_tables(humanoid="smpl"):
+    """(sag (num_dof,), lever_dir (num_bodies, 3)): a constant per-joint offset of the PD set point the policy has to learn to cancel, and the
+    unit 'bone' directions that turn a joint-angle error into a body displacement.  Deterministic (no RNG state involved)."""
+    sk = skeleton(humanoid)
+    j = torch.arange(sk["num_dof"], dtype=torch.float32)
     sag = 0.25 * torch.sin(0.7 * (j + 1.0))
-    b = torch.arange(NUM_BODIES, dtype=torch.float32)
+    b = torch.arange(sk["num_bodies"], dtype=torch.float32)
     u = torch.stack([torch.cos(1.3 * b), torch.sin(1.3 * b) * torch.cos(0.9 * b + 0.4), torch.sin(1.3 * b) * torch.sin(0.9 * b + 0.4)], dim=-1)
     return sag, u / u.norm(dim=-1, keepdim=True)
 

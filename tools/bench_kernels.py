@@ -138,6 +138,55 @@ for n_big in (32768,):                                           # (at 4096 envs
               reset=torch.zeros(n_big, dtype=torch.int64, device=dev), terminate=torch.zeros(n_big, dtype=torch.int64, device=dev))
     t = timeit(lambda: ops.im_step(rbb, **kw))
     report("im_step_kernel (recorded reference frames, reward+reset+obs)", n_big * 8080, t, f"{n_big} envs (SURVEY 8d: 8 080 B per env-step)")
+# ---- the 52-body SMPL-X / SMPL-H humanoid (64-lane groups): the same three launches at 4096 envs.  Algorithmic bytes per env-step from the shapes:
+# rigid-body records J * 52, dof force + velocity 2 * nd * 4, observation row (pitch) * 4, reward 4 + raw 20, flags 16, clock 24; library mode
+# reads two frame records per blended time (t, t + 1 -> 4 records) and writes the tracked state (records + dof position / velocity);
+# arrays mode reads the two reference frames (2 * J * 52).  motion_state: 2 records in, records' worth of fields + dofs out, ids / times 20.
+def im_step_bytes(j, nd, pitch, frame_stride=None):
+    common = j * 52 + 2 * nd * 4 + pitch * 4 + 24 + 16 + 24
+    if frame_stride is None:
+        return common + 2 * j * 52
+    return common + 4 * frame_stride * 4 + j * 52 + 2 * nd * 4
+
+
+def motion_state_bytes(j, nd, frame_stride):
+    return 2 * frame_stride * 4 + j * 52 + 2 * nd * 4 + 20
+
+
+def humanoid_rows(humanoid, n_env=4096):
+    sk = syn.skeleton(humanoid)
+    j, nd = sk["num_bodies"], sk["num_dof"]
+    env, _ = configs.make_env(n_env, 8, dev, seed=1, reference="motion_lib", humanoid=humanoid)
+    tk = env.task
+    env.reset()
+    for _ in range(3):
+        tk.step(torch.zeros(n_env, nd, device=dev))
+    t_lib = timeit(lambda: tk._im_step(full, inc=0))
+    stride = tk._motion_lib.frame_stride
+    report(f"im_step_kernel ({humanoid}, {j} bodies, library mode)", n_env * im_step_bytes(j, nd, tk.obs_pitch, stride), t_lib, f"{n_env} envs")
+    tms = torch.rand(n_env, device=dev) * tk._motion_len_env
+    o = {}
+    t_ms = timeit(lambda: tk._motion_lib.query(tk._sampled_motion_ids, tms, tk._global_offset, out=o))
+    report(f"motion_state_kernel ({humanoid}, {j} bodies)", n_env * motion_state_bytes(j, nd, stride), t_ms, f"{n_env} queries")
+    dd = syn.env_step_inputs(syn.make_generator(5), n_env, humanoid=humanoid)
+    to_ = lambda x: x.to(dev)
+    kw_ = dict(what=full, ref_now={k: to_(v) for k, v in dd["ref_now"].items()}, ref_next={k: to_(v) for k, v in dd["ref_next"].items()},
+               dof_force=to_(dd["dof_force"]), dof_vel=to_(dd["dof_vel"]), progress=to_(dd["progress"]), pass_time=to_(dd["pass_time"]),
+               track_ids=tk._track_bodies_id, reset_ids=tk._reset_bodies_id, term_dist=tk._termination_distances, upright=tk._has_upright_start,
+               obs=torch.zeros(n_env, tk.obs_pitch, device=dev), obs_cols=tk.obs_pitch, rew=torch.zeros(n_env, device=dev),
+               rew_raw=torch.zeros(n_env, 5, device=dev), reset=torch.zeros(n_env, dtype=torch.int64, device=dev),
+               terminate=torch.zeros(n_env, dtype=torch.int64, device=dev))
+    rb_ = to_(dd["rb"])
+    cache = {}
+    t_arr = timeit(lambda: ops.im_step(rb_, cache=cache, **kw_))
+    report(f"im_step_kernel ({humanoid}, {j} bodies, arrays mode)", n_env * im_step_bytes(j, nd, tk.obs_pitch), t_arr, f"{n_env} envs")
+    return {"lib": (t_lib, im_step_bytes(j, nd, tk.obs_pitch, stride)), "arrays": (t_arr, im_step_bytes(j, nd, tk.obs_pitch)),
+            "motion_state": (t_ms, motion_state_bytes(j, nd, stride))}
+
+
+h24, h52 = humanoid_rows("smpl"), humanoid_rows("smplx")
+for k in h24:
+    rows.append(f"| SMPL-X / SMPL `{k}` | time ratio {h52[k][0] / h24[k][0]:.2f} | byte ratio {h52[k][1] / h24[k][1]:.2f} | | | |")
 # ---- round 3: terrain / trajectory step (height-map gather), PULSE VAE head kernels, downstream-task step
 from pulse_amd._lib import TASK_OBS, TASK_REWARD, TASK_RESET  # noqa: E402
 try:
