@@ -36,7 +36,7 @@ extern "C" {
 #define PULSE_ERR_LAUNCH (-2)
 #define PULSE_ERR_UNSUPPORTED (-3)
 
-#define PULSE_ABI_VERSION 30
+#define PULSE_ABI_VERSION 31
 
 typedef void* pulse_stream_t; /* hipStream_t */
 
@@ -292,8 +292,9 @@ int pulse_sizeof_task_step_args(void);
 int pulse_task_obs_size(int task);    /* 3 / 3 / 15 */
 int pulse_task_step(const pulse_task_step_args* args, pulse_stream_t s);
 
-/* AMP per-frame observation: build_amp_observations_smpl (phc/env/tasks/humanoid_amp.py:925-969) +
- * dof_to_obs_smpl (phc/env/tasks/humanoid.py:1436-1446). */
+/* AMP per-frame observation: build_amp_observations_smpl / build_amp_observations_smpl_v2 (phc/env/tasks/humanoid_amp.py:925-969,
+ * 973-1017) + dof_to_obs_smpl (phc/env/tasks/humanoid.py:1436-1446).  Columns:
+ *   [root_h?, rot6, vel3, angvel3, 6 Jd, 3 Jd, 3 Kb, (version 2: 3 Kb heading-local key-body velocities), num_shape, num_limb]. */
 typedef struct pulse_amp_obs_args {
     const float* rb; int64_t rb_env_stride;  /* (num_envs, bodies, 13); root = body 0 */
     const float* dof_pos; const float* dof_vel; int32_t num_dof;   /* (num_envs, num_dof) exp-map dofs, 3 per joint */
@@ -309,20 +310,33 @@ typedef struct pulse_amp_obs_args {
        frame into slot 0 (HumanoidAMP.post_physics_step, :194-210) and, if window_out != NULL, copies the finished window to
        window_out + e * window_stride (the experience-buffer slot, amp_agent.py:377). */
     int32_t hist_steps; float* window_out; int64_t window_stride;
+    /* any W: the three copies run as float4 loops when W, both pitches and both bases are multiples of 16 bytes, as scalar loops otherwise */
+    int32_t upright_start;                             /* 0: root_rot := remove_base_rot(root_rot) first (humanoid_amp.py:929-930, humanoid.py:1414-1419) */
+    int32_t version;                                   /* 1 | 2 (amp_obs_v, humanoid_amp.py:300-303, 670-675) */
+    /* has_shape_obs_disc / has_limb_weight_obs_disc rows (humanoid_amp.py:311-314, 963-966), optional, indexed by env: the caller passes the
+       truncated view of humanoid_shapes (``[:, :-6]``, :672: pitch 17, 11 columns) */
+    const float* shape_params; int64_t shape_stride; int32_t num_shape;
+    const float* limb_weights; int64_t limb_stride; int32_t num_limb;
 } pulse_amp_obs_args;
 int pulse_sizeof_amp_obs_args(void);
-int pulse_amp_obs_width(int num_joints, int num_key_bodies, int root_height_obs);
+int pulse_amp_obs_width(int num_joints, int num_key_bodies, int root_height_obs);      /* version 1, no shape / limb rows */
+/* _num_amp_obs_per_step of the SMPL humanoids (humanoid_amp.py:299-314) */
+int pulse_amp_obs_width_v(int num_joints, int num_key_bodies, int root_height_obs, int version, int num_shape, int num_limb);
 int pulse_amp_obs(const pulse_amp_obs_args* args, pulse_stream_t s);
 
 /* _init_amp_obs_ref (phc/env/tasks/humanoid_amp.py:531-563) for the masked envs: history slot k + 1 (k = 0 .. hist_steps - 2) of env e :=
  * build_amp_observations_smpl of the env's motion at start_times[e] - dt * (k + 1) (MotionLibBase.get_motion_state, motion_lib_base.py:
- * 434-517, no root offset; no zeroed joints).  hist[e * env_stride + slot * step_stride + c]. */
+ * 434-517, no root offset; no zeroed joints).  hist[e * env_stride + slot * step_stride + c].  upright_start / version as pulse_amp_obs_args;
+ * the shape / limb rows are the MOTION's (motion_bodies / motion_limb_weights, humanoid_amp.py:243-250, 548-555): indexed by motion_ids[e]. */
 typedef struct pulse_amp_hist_args {
     pulse_motion_tables tab; const int64_t* motion_ids; const float* start_times; float dt;
     int32_t num_envs; const uint8_t* env_mask; int32_t hist_steps;
     const int32_t* joint_ids; int32_t num_joints; const int32_t* key_body_ids; int32_t num_key_bodies;
     int32_t local_root_obs, root_height_obs;
     float* hist; int64_t env_stride, step_stride;
+    int32_t upright_start, version;
+    const float* shape_params; int64_t shape_stride; int32_t num_shape;
+    const float* limb_weights; int64_t limb_stride; int32_t num_limb;
 } pulse_amp_hist_args;
 int pulse_sizeof_amp_hist_args(void);
 int pulse_amp_hist_init(const pulse_amp_hist_args* args, pulse_stream_t s);

@@ -12,7 +12,7 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int6
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PULSE_HIP_LIB: another build of the SAME library (tools/im_step_repro.py compares compile variants); default = the in-tree build
 LIB_PATH = os.environ.get("PULSE_HIP_LIB") or os.path.join(_HERE, "csrc", "libpulse_hip.so")
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 PULSE_IM_SELF_OBS = 1
 PULSE_IM_TASK_OBS = 2
@@ -95,7 +95,10 @@ class AmpObsArgs(Structure):
                 ("joint_ids", c_void_p), ("num_joints", c_int32), ("zero_joint_mask", c_uint32),
                 ("key_body_ids", c_void_p), ("num_key_bodies", c_int32), ("local_root_obs", c_int32), ("root_height_obs", c_int32),
                 ("out", c_void_p), ("out_stride", c_int64),
-                ("hist_steps", c_int32), ("window_out", c_void_p), ("window_stride", c_int64)]
+                ("hist_steps", c_int32), ("window_out", c_void_p), ("window_stride", c_int64),
+                ("upright_start", c_int32), ("version", c_int32),
+                ("shape_params", c_void_p), ("shape_stride", c_int64), ("num_shape", c_int32),
+                ("limb_weights", c_void_p), ("limb_stride", c_int64), ("num_limb", c_int32)]
 
 
 class B16Transpose(Structure):
@@ -108,7 +111,10 @@ class AmpHistArgs(Structure):
                 ("num_envs", c_int32), ("env_mask", c_void_p), ("hist_steps", c_int32),
                 ("joint_ids", c_void_p), ("num_joints", c_int32), ("key_body_ids", c_void_p), ("num_key_bodies", c_int32),
                 ("local_root_obs", c_int32), ("root_height_obs", c_int32),
-                ("hist", c_void_p), ("env_stride", c_int64), ("step_stride", c_int64)]
+                ("hist", c_void_p), ("env_stride", c_int64), ("step_stride", c_int64),
+                ("upright_start", c_int32), ("version", c_int32),
+                ("shape_params", c_void_p), ("shape_stride", c_int64), ("num_shape", c_int32),
+                ("limb_weights", c_void_p), ("limb_stride", c_int64), ("num_limb", c_int32)]
 
 
 class MotionStateArgs(Structure):
@@ -270,6 +276,7 @@ SIGNATURES = {
     "pulse_gemm_x3_mode": (c_int, []),
     "pulse_sizeof_amp_obs_args": (c_int, []),
     "pulse_amp_obs_width": (c_int, [c_int, c_int, c_int]),
+    "pulse_amp_obs_width_v": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "pulse_amp_obs": (c_int, [POINTER(AmpObsArgs), P]),
     "pulse_sizeof_amp_hist_args": (c_int, []),
     "pulse_amp_hist_init": (c_int, [POINTER(AmpHistArgs), P]),

@@ -166,7 +166,8 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
         from .env.sim import KinematicSim, PdSim
         cfg = {"env": env_cfg} if humanoid == "smpl" else {"env": env_cfg, "robot": robot}
         check_humanoid_options(cfg)                     # an unbuilt combination raises by name before anything is allocated
-        tables = syn.synthetic_motion_library(syn.make_generator(seed + 5, rank), min(num_envs, 1024), humanoid=humanoid)
+        disc_rows = any(bool(dict(robot if humanoid != "smpl" else {}, **env_cfg).get(k, False)) for k in ("has_shape_obs_disc", "has_weight_obs_disc"))
+        tables = syn.synthetic_motion_library(syn.make_generator(seed + 5, rank), min(num_envs, 1024), humanoid=humanoid, shape_rows=disc_rows)
         motion = MotionLib.from_tables(tables, device)
         sim_cls = PdSim if env_cfg.pop("physics", "tracking") == "pd" else KinematicSim        # "pd": action-dependent stand-in
         sim = sim_cls(num_envs, horizon + 1, device, seed=seed, rank=rank, humanoid=humanoid)

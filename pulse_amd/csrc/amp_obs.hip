@@ -5,7 +5,10 @@
 //   [root_h (1)?, 6-D heading-local root rot, local root lin vel (3), local root ang vel (3),
 //    6-D rotation of every (selected) dof joint from its exp-map (6 Jd), dof velocities (3 Jd),
 //    heading-local key-body positions (3 Kb)]
-// = 232 floats for the 23 SMPL joints / 4 key bodies (196 for the 19-joint subset).
+// = 232 floats for the 23 SMPL joints / 4 key bodies (196 for the 19-joint subset), and its configured variants:
+//   * version 2 (build_amp_observations_smpl_v2, :973-1017): + heading-local key-body velocities (3 Kb) behind the positions;
+//   * has_shape_obs_disc / has_limb_weight_obs_disc (:963-966): + the env's (the motion's, for reference frames) shape / limb rows, copied;
+//   * has_upright_start False (:929-930): the root rotation goes through remove_base_rot (humanoid.py:1617-1620) before anything reads it.
 //
 // Same mapping as the fused env step: a 32-lane half-wave per env, lane j <-> joint j / key body j, inputs
 // read straight from the 13-float rigid-body records and the (N, 69) dof tensors, the feature row assembled
@@ -24,14 +27,45 @@ constexpr int kAmpMaxW = 320;
 
 constexpr int kAmpMaxHist = 9;      // history frames behind the current one (numAMPObsSteps - 1)
 
+// column offsets of one frame: [h?, rot6, vel3, angvel3, 6 Jd, 3 Jd, 3 Kb, (v2: 3 Kb), num_shape, num_limb]
+struct AmpLayout { int h0, off_vel, off_ang, off_dof, off_dvel, off_key, off_kvel, off_shape, off_limb, W; };
+
+__host__ __device__ inline AmpLayout amp_layout(int Jd, int Kb, int root_height_obs, int version, int num_shape, int num_limb) {
+    AmpLayout L;
+    L.h0 = root_height_obs ? 1 : 0;
+    L.off_vel = L.h0 + 6; L.off_ang = L.off_vel + 3; L.off_dof = L.off_ang + 3; L.off_dvel = L.off_dof + 6 * Jd; L.off_key = L.off_dvel + 3 * Jd;
+    L.off_kvel = L.off_key + 3 * Kb;
+    L.off_shape = L.off_kvel + (version == 2 ? 3 * Kb : 0);
+    L.off_limb = L.off_shape + num_shape;
+    L.W = L.off_limb + num_limb;
+    return L;
+}
+
+// remove_base_rot (humanoid.py:1617-1620): quat_mul(q, conj(0.5, 0.5, 0.5, 0.5)), the expression of the fused env step
+__device__ __forceinline__ Q4 amp_root_rot(Q4 q, int upright_start) {
+    return upright_start ? q : qmul(q, Q4{-0.5f, -0.5f, -0.5f, 0.5f});
+}
+
+// the shape / limb rows behind everything else (copied, never computed)
+__device__ __forceinline__ void amp_copy_rows(float* o, const AmpLayout& L, int lane, const float* shape, int num_shape, const float* limb, int num_limb) {
+    for (int c = lane; c < num_shape; c += kAmpLanes) o[L.off_shape + c] = shape[c];
+    for (int c = lane; c < num_limb; c += kAmpLanes) o[L.off_limb + c] = limb[c];
+}
+
 // HIST: ``out`` is slot 0 of the env's (hist_steps, W) history window (HumanoidAMP._amp_obs_buf, humanoid_amp.py:296-314).  The launch
 // then does the whole per-step update of HumanoidAMP.post_physics_step (:194-210) for the env: _update_hist_amp_obs (frames 0 .. S-2 move
 // to 1 .. S-1, :622-631), the current frame into slot 0, and -- window_out -- the finished window copied to the caller's row (the
 // experience-buffer slot of this rollout step: amp_agent.py:377).  Four device copies of the (N, S W) window become none.
-template <bool HIST>
-__global__ void __launch_bounds__(kAmpEnvs * kAmpLanes) amp_obs_kernel(const pulse_amp_obs_args a) {
-    __shared__ float s_out[kAmpEnvs][kAmpMaxW];
-    __shared__ float s_hist[HIST ? kAmpEnvs : 1][HIST ? kAmpMaxHist * kAmpMaxW : 1];
+// vec4 (uniform over the launch, set by the launcher): W, both pitches and both bases are multiples of 16 bytes, so the three copies of the
+// history run as float4 loops; otherwise (e.g. W = 207, the shape-aware 19-joint frame) the same copies run float by float.
+// PLAIN: the upright, version-1 frame without rows on aligned windows -- the shipped SMPL configuration -- with the variant switches folded at
+// compile time (measured: as runtime flags they cost the fused cfg5 launch 0.6 us of 46, profiles/amp_obs_variants_ab.txt).
+template <bool HIST, bool PLAIN>
+__global__ void __launch_bounds__(kAmpEnvs * kAmpLanes) amp_obs_kernel(const pulse_amp_obs_args a, const int vec4_arg) {
+    const int vec4 = PLAIN ? 1 : vec4_arg, version = PLAIN ? 1 : a.version, upright_start = PLAIN ? 1 : a.upright_start;
+    const int num_shape = PLAIN ? 0 : a.num_shape, num_limb = PLAIN ? 0 : a.num_limb;
+    __shared__ __align__(16) float s_out[kAmpEnvs][kAmpMaxW];
+    __shared__ __align__(16) float s_hist[HIST ? kAmpEnvs : 1][HIST ? kAmpMaxHist * kAmpMaxW : 1];
     const int slot = threadIdx.x / kAmpLanes, lane = threadIdx.x % kAmpLanes;
     const int idx = blockIdx.x * kAmpEnvs + slot;
     const int count = a.env_ids ? a.num_ids : a.num_envs;
@@ -42,21 +76,25 @@ __global__ void __launch_bounds__(kAmpEnvs * kAmpLanes) amp_obs_kernel(const pul
         if (a.env_mask && a.env_mask[e] == 0) valid = false;
     }
     const int Jd = a.num_joints, Kb = a.num_key_bodies;
-    const int h0 = a.root_height_obs ? 1 : 0;
-    const int off_vel = h0 + 6, off_ang = off_vel + 3, off_dof = off_ang + 3, off_dvel = off_dof + 6 * Jd, off_key = off_dvel + 3 * Jd;
-    const int W = off_key + 3 * Kb;
+    const AmpLayout L = amp_layout(Jd, Kb, a.root_height_obs, version, num_shape, num_limb);   // counts are 0 without a pointer (launcher)
+    const int h0 = L.h0, off_vel = L.off_vel, off_ang = L.off_ang, off_dof = L.off_dof, off_dvel = L.off_dvel, off_key = L.off_key, W = L.W;
     float* o = s_out[slot];
     if constexpr (HIST) {
         if (valid) {                                                     // the frames that move down one slot (read before anything is written)
             const float* h = a.out + e * a.out_stride;
-            const int n4 = (a.hist_steps - 1) * W / 4;                   // W and the window base are multiples of 4 floats (checked by the launcher)
-            for (int c = lane; c < n4; c += kAmpLanes) reinterpret_cast<float4*>(s_hist[slot])[c] = reinterpret_cast<const float4*>(h)[c];
+            const int nh = (a.hist_steps - 1) * W;
+            if (vec4) {
+                const int n4 = nh / 4;
+                for (int c = lane; c < n4; c += kAmpLanes) reinterpret_cast<float4*>(s_hist[slot])[c] = reinterpret_cast<const float4*>(h)[c];
+            } else {
+                for (int c = lane; c < nh; c += kAmpLanes) s_hist[slot][c] = h[c];
+            }
         }
     }
     if (valid) {
         const float* rb = a.rb + e * a.rb_env_stride;
         const V3 root_p{rb[0], rb[1], rb[2]};
-        const Q4 root_q{rb[3], rb[4], rb[5], rb[6]};
+        const Q4 root_q = amp_root_rot(Q4{rb[3], rb[4], rb[5], rb[6]}, upright_start);
         const Q4 hinv = heading_quat(root_q, true);
         if (lane == 0) {
             if (a.root_height_obs) o[0] = root_p.z;
@@ -86,22 +124,38 @@ __global__ void __launch_bounds__(kAmpEnvs * kAmpLanes) amp_obs_kernel(const pul
             const float* kb = rb + 13 * a.key_body_ids[lane];
             const V3 lp = qrot(hinv, V3{kb[0] - root_p.x, kb[1] - root_p.y, kb[2] - root_p.z});
             o[off_key + 3 * lane] = lp.x; o[off_key + 3 * lane + 1] = lp.y; o[off_key + 3 * lane + 2] = lp.z;
+            if (version == 2) {                                        // key-body velocities, floats 7..9 of the body's record (:999)
+                const V3 lkv = qrot(hinv, V3{kb[7], kb[8], kb[9]});
+                o[L.off_kvel + 3 * lane] = lkv.x; o[L.off_kvel + 3 * lane + 1] = lkv.y; o[L.off_kvel + 3 * lane + 2] = lkv.z;
+            }
         }
+        amp_copy_rows(o, L, lane, a.shape_params + e * a.shape_stride, num_shape, a.limb_weights + e * a.limb_stride, num_limb);
     }
     __syncthreads();
     if (valid) {
         float* g = a.out + e * a.out_stride;
         for (int c = lane; c < W; c += kAmpLanes) g[c] = o[c];
         if constexpr (HIST) {
-            const int n4 = (a.hist_steps - 1) * W / 4, w4 = W / 4;
-            float4* gh = reinterpret_cast<float4*>(g + W);
-            const float4* sh = reinterpret_cast<const float4*>(s_hist[slot]);
-            for (int c = lane; c < n4; c += kAmpLanes) gh[c] = sh[c];
-            if (a.window_out) {
-                float* wo = a.window_out + e * a.window_stride;
-                for (int c = lane; c < w4; c += kAmpLanes) reinterpret_cast<float4*>(wo)[c] = reinterpret_cast<const float4*>(o)[c];
-                float4* wh = reinterpret_cast<float4*>(wo + W);
-                for (int c = lane; c < n4; c += kAmpLanes) wh[c] = sh[c];
+            const int nh = (a.hist_steps - 1) * W;
+            if (vec4) {
+                const int n4 = nh / 4, w4 = W / 4;
+                float4* gh = reinterpret_cast<float4*>(g + W);
+                const float4* sh = reinterpret_cast<const float4*>(s_hist[slot]);
+                for (int c = lane; c < n4; c += kAmpLanes) gh[c] = sh[c];
+                if (a.window_out) {
+                    float* wo = a.window_out + e * a.window_stride;
+                    for (int c = lane; c < w4; c += kAmpLanes) reinterpret_cast<float4*>(wo)[c] = reinterpret_cast<const float4*>(o)[c];
+                    float4* wh = reinterpret_cast<float4*>(wo + W);
+                    for (int c = lane; c < n4; c += kAmpLanes) wh[c] = sh[c];
+                }
+            } else {
+                const float* sh = s_hist[slot];
+                for (int c = lane; c < nh; c += kAmpLanes) g[W + c] = sh[c];
+                if (a.window_out) {
+                    float* wo = a.window_out + e * a.window_stride;
+                    for (int c = lane; c < W; c += kAmpLanes) wo[c] = o[c];
+                    for (int c = lane; c < nh; c += kAmpLanes) wo[W + c] = sh[c];
+                }
             }
         }
     }
@@ -121,16 +175,16 @@ __global__ void __launch_bounds__(kAmpEnvs * kAmpLanes) amp_hist_init_kernel(con
     const int k = valid ? (int)(idx - e * Hs) : 0;
     if (valid && a.env_mask && a.env_mask[e] == 0) valid = false;
     const int Jd = a.num_joints, Kb = a.num_key_bodies;
-    const int h0 = a.root_height_obs ? 1 : 0;
-    const int off_vel = h0 + 6, off_ang = off_vel + 3, off_dof = off_ang + 3, off_dvel = off_dof + 6 * Jd, off_key = off_dvel + 3 * Jd;
-    const int W = off_key + 3 * Kb;
+    const AmpLayout L = amp_layout(Jd, Kb, a.root_height_obs, a.version, a.num_shape, a.num_limb);   // counts are 0 without a pointer (launcher)
+    const int h0 = L.h0, off_vel = L.off_vel, off_ang = L.off_ang, off_dof = L.off_dof, off_dvel = L.off_dvel, off_key = L.off_key, W = L.W;
     float* o = s_out[slot];
     if (valid) {
         const pulse_motion_tables& T = a.tab;
         // times = start_times[:, None] + (-dt * (arange(S - 1) + 1))   (fp32, the reference's op order)
         const float t = a.start_times[e] + (float)(k + 1) * (-a.dt);
         const FramePair fp = frame_pair(T, a.motion_ids[e], t);
-        const BodyState root = blend_body(T, fp.r0, fp.r1, fp.blend, 0, nullptr);
+        BodyState root = blend_body(T, fp.r0, fp.r1, fp.blend, 0, nullptr);
+        root.q = amp_root_rot(root.q, a.upright_start);
         const Q4 hinv = heading_quat(root.q, true);
         if (lane == 0) {
             if (a.root_height_obs) o[0] = root.p.z;
@@ -157,13 +211,30 @@ __global__ void __launch_bounds__(kAmpEnvs * kAmpLanes) amp_hist_init_kernel(con
             const V3 kp = lerp3(fp.r0 + T.off_gts + 3 * b, fp.r1 + T.off_gts + 3 * b, fp.blend);
             const V3 lp = qrot(hinv, V3{kp.x - root.p.x, kp.y - root.p.y, kp.z - root.p.z});
             o[off_key + 3 * lane] = lp.x; o[off_key + 3 * lane + 1] = lp.y; o[off_key + 3 * lane + 2] = lp.z;
+            if (a.version == 2) {                                      // body_vel[:, key] (:553), blended as blend_body does
+                const V3 kv = lerp3(fp.r0 + T.off_gvs + 3 * b, fp.r1 + T.off_gvs + 3 * b, fp.blend);
+                const V3 lkv = qrot(hinv, kv);
+                o[L.off_kvel + 3 * lane] = lkv.x; o[L.off_kvel + 3 * lane + 1] = lkv.y; o[L.off_kvel + 3 * lane + 2] = lkv.z;
+            }
         }
+        const long long m = a.motion_ids[e];                           // the motion's rows (motion_bodies / motion_limb_weights, :548-555)
+        amp_copy_rows(o, L, lane, a.shape_params + m * a.shape_stride, a.num_shape, a.limb_weights + m * a.limb_stride, a.num_limb);
     }
     __syncthreads();
     if (valid) {
         float* g = a.hist + e * a.env_stride + (long long)(k + 1) * a.step_stride;
         for (int c = lane; c < W; c += kAmpLanes) g[c] = o[c];
     }
+}
+
+// the checks both entries share: version, row pointers / counts / pitches
+template <class Args>
+int amp_check_variant(const Args& a, const char* name) {
+    PULSE_REQUIRE(a.version == 1 || a.version == 2, "%s: version must be 1 or 2", name);
+    PULSE_REQUIRE(a.num_shape >= 0 && a.num_limb >= 0 && (a.shape_params || a.num_shape == 0) && (a.limb_weights || a.num_limb == 0) &&
+                  (!a.shape_params || a.shape_stride >= a.num_shape) && (!a.limb_weights || a.limb_stride >= a.num_limb),
+                  "%s: shape / limb rows need a pointer, a count >= 0 and a pitch >= the count", name);
+    return PULSE_OK;
 }
 
 }  // namespace pulse
@@ -178,6 +249,10 @@ int pulse_amp_obs_width(int num_joints, int num_key_bodies, int root_height_obs)
     return (root_height_obs ? 1 : 0) + 12 + 9 * num_joints + 3 * num_key_bodies;
 }
 
+int pulse_amp_obs_width_v(int num_joints, int num_key_bodies, int root_height_obs, int version, int num_shape, int num_limb) {
+    return amp_layout(num_joints, num_key_bodies, root_height_obs, version, num_shape, num_limb).W;
+}
+
 int pulse_amp_obs(const pulse_amp_obs_args* args, pulse_stream_t s) {
     PULSE_REQUIRE(args != nullptr, "pulse_amp_obs: null args");
     const pulse_amp_obs_args& a = *args;
@@ -188,18 +263,24 @@ int pulse_amp_obs(const pulse_amp_obs_args* args, pulse_stream_t s) {
     PULSE_REQUIRE(a.num_joints >= 1 && a.num_joints <= kAmpLanes && a.num_key_bodies >= 0 && a.num_key_bodies <= kAmpLanes,
                   "pulse_amp_obs: joints / key bodies must fit 32 lanes");
     PULSE_REQUIRE(a.num_dof >= 3 * a.num_joints || a.joint_ids, "pulse_amp_obs: num_dof too small");
-    const int w = pulse_amp_obs_width(a.num_joints, a.num_key_bodies, a.root_height_obs);
+    if (const int rc = amp_check_variant(a, "pulse_amp_obs")) return rc;
+    const int w = pulse_amp_obs_width_v(a.num_joints, a.num_key_bodies, a.root_height_obs, a.version, a.num_shape, a.num_limb);
     PULSE_REQUIRE(w <= kAmpMaxW && a.out_stride >= w, "pulse_amp_obs: width %d exceeds %d or the output pitch", w, kAmpMaxW);
+    const bool plain = a.upright_start && a.version == 1 && a.num_shape == 0 && a.num_limb == 0;
+    const dim3 grid((unsigned)((count + kAmpEnvs - 1) / kAmpEnvs)), block(kAmpEnvs * kAmpLanes);
     if (a.hist_steps > 1) {
-        PULSE_REQUIRE(a.hist_steps - 1 <= kAmpMaxHist && (w % 4) == 0 && (a.out_stride % 4) == 0 && a.out_stride >= (int64_t)a.hist_steps * w &&
-                      (reinterpret_cast<uintptr_t>(a.out) & 15) == 0,
-                      "pulse_amp_obs: history mode needs hist_steps <= %d, W and the window pitch multiples of 4 floats, a 16-byte aligned window", kAmpMaxHist + 1);
-        PULSE_REQUIRE(!a.window_out || ((a.window_stride % 4) == 0 && a.window_stride >= (int64_t)a.hist_steps * w && (reinterpret_cast<uintptr_t>(a.window_out) & 15) == 0),
-                      "pulse_amp_obs: window_out rows must be 16-byte aligned and hold hist_steps * W floats");
-        hipLaunchKernelGGL(amp_obs_kernel<true>, dim3((unsigned)((count + kAmpEnvs - 1) / kAmpEnvs)), dim3(kAmpEnvs * kAmpLanes), 0, as_stream(s), a);
+        PULSE_REQUIRE(a.hist_steps - 1 <= kAmpMaxHist && a.out_stride >= (int64_t)a.hist_steps * w,
+                      "pulse_amp_obs: history mode needs hist_steps <= %d and a window pitch of hist_steps * W floats", kAmpMaxHist + 1);
+        PULSE_REQUIRE(!a.window_out || a.window_stride >= (int64_t)a.hist_steps * w, "pulse_amp_obs: window_out rows must hold hist_steps * W floats");
+        // float4 copies when every row of both windows starts on 16 bytes and W is a multiple of 4 floats; float by float otherwise
+        const int vec4 = (w % 4) == 0 && (a.out_stride % 4) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0 &&
+                         (!a.window_out || ((a.window_stride % 4) == 0 && (reinterpret_cast<uintptr_t>(a.window_out) & 15) == 0));
+        if (plain && vec4) hipLaunchKernelGGL((amp_obs_kernel<true, true>), grid, block, 0, as_stream(s), a, 1);
+        else hipLaunchKernelGGL((amp_obs_kernel<true, false>), grid, block, 0, as_stream(s), a, vec4);
     } else {
         PULSE_REQUIRE(a.window_out == nullptr, "pulse_amp_obs: window_out goes with hist_steps > 1");
-        hipLaunchKernelGGL(amp_obs_kernel<false>, dim3((unsigned)((count + kAmpEnvs - 1) / kAmpEnvs)), dim3(kAmpEnvs * kAmpLanes), 0, as_stream(s), a);
+        if (plain) hipLaunchKernelGGL((amp_obs_kernel<false, true>), grid, block, 0, as_stream(s), a, 0);
+        else hipLaunchKernelGGL((amp_obs_kernel<false, false>), grid, block, 0, as_stream(s), a, 0);
     }
     return check_launch("pulse_amp_obs");
 }
@@ -218,7 +299,8 @@ int pulse_amp_hist_init(const pulse_amp_hist_args* args, pulse_stream_t s) {
     PULSE_REQUIRE(a.motion_ids && a.start_times && a.hist && a.key_body_ids, "pulse_amp_hist_init: null pointer");
     PULSE_REQUIRE(a.num_joints >= 1 && a.num_joints <= kAmpLanes && (a.joint_ids || a.num_joints <= T.num_bodies - 1) &&
                   a.num_key_bodies >= 0 && a.num_key_bodies <= kAmpLanes, "pulse_amp_hist_init: joints / key bodies must fit 32 lanes and the skeleton");
-    const int w = pulse_amp_obs_width(a.num_joints, a.num_key_bodies, a.root_height_obs);
+    if (const int rc = amp_check_variant(a, "pulse_amp_hist_init")) return rc;
+    const int w = pulse_amp_obs_width_v(a.num_joints, a.num_key_bodies, a.root_height_obs, a.version, a.num_shape, a.num_limb);
     PULSE_REQUIRE(w <= kAmpMaxW && a.step_stride >= w && a.env_stride >= (int64_t)a.hist_steps * a.step_stride, "pulse_amp_hist_init: bad pitches");
     const long long total = (long long)a.num_envs * (a.hist_steps - 1);
     hipLaunchKernelGGL(amp_hist_init_kernel, dim3((unsigned)((total + kAmpEnvs - 1) / kAmpEnvs)), dim3(kAmpEnvs * kAmpLanes), 0, as_stream(s), a);

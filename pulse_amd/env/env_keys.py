@@ -30,7 +30,7 @@ HONOURED = {
     # zero_out_far (humanoid.py:311-329)
     "zero_out_far", "zero_out_far_train", "zero_out_far_steps", "close_distance", "far_distance",
     # robot switches the env dict may carry (robot/*.yaml merged by the caller)
-    "has_upright_start", "has_dof_subset", "has_shape_obs", "has_weight_obs",
+    "has_upright_start", "has_dof_subset", "has_shape_obs", "has_weight_obs", "has_shape_obs_disc", "has_weight_obs_disc",
     # AMP observations
     "enable_amp_obs", "numAMPObsSteps", "ampRootHeightObs", "key_bodies", "add_amp_input_noise",
     # PULSE / distillation attributes the agent reads off the task (amp_agent.py:59-63, 773-832)
@@ -79,7 +79,9 @@ INERT = {
 UNBUILT = {
     "addInputNoise": ((False,), "vec_task / task input noise"),
     "remove_disc_rot": ((False,), "humanoid.py:413-416 (discriminator dof subset without global rotation)"),
-    "amp_obs_v": ((1,), "humanoid_amp.py:300-314, 670-680 (build_amp_observations_smpl_v2)"),
+    # amp_obs_v 2 (build_amp_observations_smpl_v2) is built in the AMP frame (amp_obs.hip, HumanoidIm with enable_amp_obs); the reference's task
+    # chain builds that frame unconditionally, so an env dict that asks for it where no AMP frame is built would drop it silently: it raises
+    "amp_obs_v": ((1, "2 with enable_amp_obs"), "humanoid_amp.py:300-314, 670-680 (the v2 AMP frame: built by HumanoidIm's AMP observation, enable_amp_obs)"),
     "numAMPEncObsSteps": ("==numAMPObsSteps", "humanoid_amp.py:94, 834-880 (CALM encoder windows)"),
     "enableHistObs": ((False,), "humanoid_amp.py:320, 509-517"),
     "is_discrete": ((False,), "base_task.py:90; amp_agent.py:42-44 (discrete action heads)"),
@@ -104,6 +106,8 @@ def _inactive(key, value, env):
     ok, _ = UNBUILT[key]
     if ok == "==numAMPObsSteps":
         return int(value) == int(env.get("numAMPObsSteps", 10))
+    if key == "amp_obs_v":
+        return value == 1 or (value == 2 and bool(env.get("enable_amp_obs", False)))
     return any(value == v for v in ok)
 
 

@@ -88,6 +88,27 @@ def check_humanoid_options(cfg, task="HumanoidIm"):
     return ht
 
 
+def check_amp_options(env, motion_lib=None):
+    """The AMP frame's variant switches of an env dict (robot switches merged in): amp_obs_v (humanoid.py:292; humanoid_amp.py:300-303, 670-675),
+    has_shape_obs_disc / has_weight_obs_disc (humanoid.py:267-269).  Returns amp_obs_v; raises by name for what cannot be built.  Needs no
+    device.  ``motion_lib``: the reference source, if it is a motion library (has ``query``) it must carry the rows the frame appends."""
+    v = env.get("amp_obs_v", 1)
+    if v not in (1, 2):
+        raise ValueError(f"amp_obs_v = {v!r}: the reference builds 1 and 2 (humanoid_amp.py:300-303, 670-675)")
+    if not env.get("enable_amp_obs", False):
+        return int(v)
+    if v == 2 and env.get("has_shape_obs_disc", False):
+        raise NotImplementedError("amp_obs_v 2 with has_shape_obs_disc: the reference hands the untruncated 17-column humanoid_shapes to "
+                                  "build_amp_observations_smpl_v2 (humanoid_amp.py:675) but sizes the frame for 11 (humanoid_amp.py:312), so its own "
+                                  "assignment into the AMP buffer cannot succeed")
+    if hasattr(motion_lib, "query"):
+        for key, attr in (("has_shape_obs_disc", "motion_bodies"), ("has_weight_obs_disc", "motion_limb_weights")):
+            if env.get(key, False) and getattr(motion_lib, attr, None) is None:
+                raise ValueError(f"{key}: the motion library carries no {attr} (MotionLib.from_tables takes them with the tables; "
+                                 "motion_lib_base.py:515-516)")
+    return int(v)
+
+
 class HumanoidIm:
     def __init__(self, cfg, sim, motion_lib, device="cuda:0"):
         # cfg.robot.humanoid_type is read from the robot dict directly (not merged into the env options, whose keys are audited below)
@@ -96,7 +117,9 @@ class HumanoidIm:
         self.skeleton = sk = syn.skeleton(self.humanoid_type)
         env = _env_dict(cfg)
         if isinstance(cfg.get("robot", None), dict):                            # robot/*.yaml switches (humanoid.py:266-280 reads cfg.robot)
-            env = dict({k: v for k, v in cfg["robot"].items() if k in ("has_upright_start", "has_dof_subset", "has_shape_obs", "has_weight_obs")}, **env)
+            env = dict({k: v for k, v in cfg["robot"].items() if k in ("has_upright_start", "has_dof_subset", "has_shape_obs", "has_weight_obs",
+                                                                     "has_shape_obs_disc", "has_weight_obs_disc")}, **env)
+        self.amp_obs_v = check_amp_options(env, motion_lib)                    # (first: an amp_obs_v that does not exist is a ValueError)
         env_keys.audit(env, type(self).__name__)                               # every key is honoured, inert by contract, or raises by name
         self.cfg = cfg
         self.device = torch.device(device)
@@ -243,7 +266,10 @@ class HumanoidIm:
             self._force_sensor = torch.zeros(n, self._force_sensor_width, device=dev)
         # humanoid_shapes (N, 17) = [gender, 10 betas, 6 unused] and humanoid_limb_and_weights (N, 10) are filled while the robot assets are
         # built (humanoid.py:739-878: smpl_sim, out of scope); the sim stand-in may provide them, otherwise a fixed synthetic draw per env
-        if self._has_shape_obs or self._has_limb_weight_obs:
+        # the discriminator's copies of the two switches (humanoid.py:267-269; robot/smpl_humanoid_shape.yaml, or the env dict of the legacy files)
+        self._has_shape_obs_disc = bool(env.get("has_shape_obs_disc", False))
+        self._has_limb_weight_obs_disc = bool(env.get("has_weight_obs_disc", False))
+        if self._has_shape_obs or self._has_limb_weight_obs or self._has_shape_obs_disc or self._has_limb_weight_obs_disc:
             g = torch.Generator().manual_seed(int(env.get("shape_seed", 99)))
             shapes = getattr(sim, "humanoid_shapes", None)
             limbs = getattr(sim, "humanoid_limb_and_weights", None)
@@ -291,8 +317,19 @@ class HumanoidIm:
             nj = self._dof_size // 3
             self._amp_joint_ids = [d // 3 for d in sk["dof_subset"][::3]] if self._has_dof_subset else None
             self._amp_zero_joints = ()
+            # the frame's shape / limb rows (humanoid_amp.py:311-314, 963-966): the env's for simulated frames, the motion's for reference frames
+            self._amp_shape_rows = self.humanoid_shapes[:, :-6] if self._has_shape_obs_disc else None            # smpl_params[:, :-6], :672
+            self._amp_limb_rows = self.humanoid_limb_and_weights if self._has_limb_weight_obs_disc else None
+            self._amp_motion_shape_rows = self._amp_motion_limb_rows = None
+            if self._use_motion_lib:
+                if self._has_shape_obs_disc:
+                    self._amp_motion_shape_rows = motion_lib.motion_bodies[:, :-6]
+                if self._has_limb_weight_obs_disc:
+                    self._amp_motion_limb_rows = motion_lib.motion_limb_weights
+            self._amp_variant = {"upright": self._has_upright_start, "version": self.amp_obs_v}
             self._num_amp_obs_per_step = ops.amp_obs_width(len(self._amp_joint_ids) if self._has_dof_subset else nj, self._key_body_ids.numel(),
-                                                           self._amp_root_height_obs)
+                                                           self._amp_root_height_obs, version=self.amp_obs_v,
+                                                           num_shape=11 * self._has_shape_obs_disc, num_limb=10 * self._has_limb_weight_obs_disc)
             if self._amp_joint_ids is not None:
                 self._amp_joint_ids = torch.tensor(self._amp_joint_ids, dtype=torch.int32, device=dev)
             self._amp_obs_buf = torch.zeros(n, self._num_amp_obs_steps, self._num_amp_obs_per_step, device=dev)
@@ -400,7 +437,8 @@ class HumanoidIm:
         """humanoid_amp.py:632-667 -> current frame into slot 0 of the history."""
         ops.build_amp_observations_smpl(self.sim.rigid_body_state, self.sim.dof_pos, self.sim.dof_vel, self._key_body_ids,
                                         joint_ids=self._amp_joint_ids, zero_joints=self._amp_zero_joints, local_root_obs=self._local_root_obs,
-                                        root_height_obs=self._amp_root_height_obs, out=self._curr_amp_obs_buf, env_mask=env_mask)
+                                        root_height_obs=self._amp_root_height_obs, out=self._curr_amp_obs_buf, env_mask=env_mask,
+                                        shape_params=self._amp_shape_rows, limb_weights=self._amp_limb_rows, **self._amp_variant)
 
     def _init_amp_obs(self, mask):
         """_init_amp_obs (humanoid_amp.py:519-563) for the masked envs.  Slot 0 is the current simulated frame.  With the motion
@@ -411,20 +449,29 @@ class HumanoidIm:
         s = self._num_amp_obs_steps - 1
         if self._use_motion_lib and self._amp_fused:
             ops.amp_hist_init(self._motion_lib, self._sampled_motion_ids, self._motion_start_times, self.dt, mask, self._amp_obs_buf, self._key_body_ids,
-                              joint_ids=self._amp_joint_ids, local_root_obs=self._local_root_obs, root_height_obs=self._amp_root_height_obs)
+                              joint_ids=self._amp_joint_ids, local_root_obs=self._local_root_obs, root_height_obs=self._amp_root_height_obs,
+                              shape_params=self._amp_motion_shape_rows, limb_weights=self._amp_motion_limb_rows, **self._amp_variant)
             return
         if self._use_motion_lib:
             steps = -self.dt * (torch.arange(0, s, device=self.device) + 1)
             times = (self._motion_start_times.unsqueeze(-1) + steps).view(-1)
             n = self.num_envs
             bufs = self._ref_bufs.setdefault("hist", {})
-            res = self._motion_lib.query(self._sampled_motion_ids.repeat_interleave(s), times, out=bufs, fields=("rb_records", "dof_pos", "dof_vel"))
+            ids = self._sampled_motion_ids.repeat_interleave(s)
+            res = self._motion_lib.query(ids, times, out=bufs, fields=("rb_records", "dof_pos", "dof_vel"))
             hist = ops.build_amp_observations_smpl(res["rb_records"], res["dof_pos"], res["dof_vel"], self._key_body_ids, joint_ids=self._amp_joint_ids, zero_joints=(),
-                                                   local_root_obs=self._local_root_obs, root_height_obs=self._amp_root_height_obs)
+                                                   local_root_obs=self._local_root_obs, root_height_obs=self._amp_root_height_obs,
+                                                   **self._amp_motion_rows(ids), **self._amp_variant)
             hist = hist.view(n, s, self._num_amp_obs_per_step)
         else:
             hist = self._curr_amp_obs_buf.unsqueeze(1).expand(-1, s, -1)
         self._hist_amp_obs_buf.copy_(torch.where(mask[:, None, None], hist, self._hist_amp_obs_buf))
+
+    def _amp_motion_rows(self, motion_ids):
+        """The shape / limb rows of reference-motion frames: motion_bodies[ids][:, :-6] / motion_limb_weights[ids] (humanoid_amp.py:243-250,
+        548-555, 672), one row per queried frame."""
+        return {"shape_params": self._amp_motion_shape_rows[motion_ids] if self._amp_motion_shape_rows is not None else None,
+                "limb_weights": self._amp_motion_limb_rows[motion_ids] if self._amp_motion_limb_rows is not None else None}
 
     def fetch_amp_obs_demo(self, num_samples):
         """humanoid_amp.py:215-284: AMP observation windows of reference motion (synthetic poses here)."""
@@ -441,10 +488,15 @@ class HumanoidIm:
             res = lib.query(ids.repeat_interleave(s), times, out=bufs, with_records=True)
             self._ref_bufs["demo"] = res
             rb, dp, dv = res["rb_records"], res["dof_pos"], res["dof_vel"]
+            rows = self._amp_motion_rows(ids.repeat_interleave(s))
         else:
             rb, dp, dv = self._motion_lib.sample_demo_states(num_samples * s)
+            # recorded frames have no motions to take rows from: the synthetic demo poses wear the envs' own rows, one body per window
+            body = (torch.arange(num_samples, device=self.device) % self.num_envs).repeat_interleave(s)
+            rows = {"shape_params": self._amp_shape_rows[body] if self._amp_shape_rows is not None else None,
+                    "limb_weights": self._amp_limb_rows[body] if self._amp_limb_rows is not None else None}
         out = ops.build_amp_observations_smpl(rb, dp, dv, self._key_body_ids, joint_ids=self._amp_joint_ids, zero_joints=(), local_root_obs=self._local_root_obs,
-                                              root_height_obs=self._amp_root_height_obs)
+                                              root_height_obs=self._amp_root_height_obs, **rows, **self._amp_variant)
         out = out.view(num_samples, s * self._num_amp_obs_per_step)
         if self._add_amp_input_noise:                      # build_amp_obs_demo's last statement (humanoid_amp.py:281-283)
             self._last_amp_noise = torch.randn(out.shape, device=self.device, generator=self._clock_gen if self._use_motion_lib else None)
@@ -687,14 +739,15 @@ class HumanoidIm:
         self.extras["terminate"] = self._terminate_buf
         self.extras["reward_raw"] = self.reward_raw
         if self._enable_amp_obs:                      # HumanoidAMP.post_physics_step (humanoid_amp.py:194-210)
-            if self._amp_fused and self._num_amp_obs_per_step % 4 == 0:
+            if self._amp_fused:
                 # history shift + current frame (+ the finished window straight into the caller's row, e.g. the experience-buffer slot
                 # the agent registered with set_amp_obs_sink) in ONE launch
                 sink = self._amp_obs_sink
                 ops.build_amp_observations_smpl(self.sim.rigid_body_state, self.sim.dof_pos, self.sim.dof_vel, self._key_body_ids,
                                                 joint_ids=self._amp_joint_ids, zero_joints=self._amp_zero_joints, local_root_obs=self._local_root_obs,
                                                 root_height_obs=self._amp_root_height_obs, out=self._curr_amp_obs_buf,
-                                                hist_steps=self._num_amp_obs_steps, window_out=sink)
+                                                hist_steps=self._num_amp_obs_steps, window_out=sink,
+                                                shape_params=self._amp_shape_rows, limb_weights=self._amp_limb_rows, **self._amp_variant)
                 self._amp_obs_sink = None
                 self.extras["amp_obs"] = sink[:, :self.get_num_amp_obs()] if sink is not None else self._amp_obs_buf.view(-1, self.get_num_amp_obs())
             else:

@@ -82,6 +82,18 @@ class MotionLib:
         keys = tables.get("motion_data_keys")
         self._motion_data_keys = list(keys) if keys is not None else [str(i) for i in range(self._num_motions)]
         self._termination_history = torch.zeros(self._num_unique_motions, device=dev)
+        # optional per-motion body-shape rows (motion_lib_base.py:289, 294, 515-516: _motion_bodies (M, 17), _motion_limb_weights (M, 10)); the
+        # AMP frames of reference motion carry them under has_shape_obs_disc / has_weight_obs_disc (humanoid_amp.py:243-250, 548-555)
+        self.motion_bodies = self._shape_rows(tables, "motion_bodies", 17)
+        self.motion_limb_weights = self._shape_rows(tables, "motion_limb_weights", 10)
+
+    def _shape_rows(self, tables, key, width):
+        t = tables.get(key)
+        if t is None:
+            return None
+        if tuple(t.shape) != (self._num_motions, width) or t.dtype != torch.float32:
+            raise ValueError(f"table {key}: expected ({self._num_motions}, {width}) float32")
+        return t.to(self._device).contiguous()
 
     @classmethod
     def from_tables(cls, tables, device="cuda:0"):

@@ -662,15 +662,39 @@ def task_step(task, rb, *, what, prev_root_pos=None, dt=1.0 / 30.0, tar_speed=No
 # --------------------------------------------------------------------------- #
 # AMP observation
 # --------------------------------------------------------------------------- #
-def amp_obs_width(num_joints, num_key_bodies, root_height_obs=True):
-    return _lib.load().pulse_amp_obs_width(num_joints, num_key_bodies, int(root_height_obs))
+def amp_obs_width(num_joints, num_key_bodies, root_height_obs=True, *, version=1, num_shape=0, num_limb=0):
+    """_num_amp_obs_per_step of the SMPL humanoids (humanoid_amp.py:299-314)."""
+    if version not in (1, 2):
+        raise ValueError(f"amp_obs_width: version must be 1 or 2, got {version!r}")
+    return _lib.load().pulse_amp_obs_width_v(num_joints, num_key_bodies, int(root_height_obs), int(version), int(num_shape), int(num_limb))
+
+
+def _amp_variant(a, fn, rows, upright, version, shape_params, limb_weights, dev, keep):
+    """The fields pulse_amp_obs_args and pulse_amp_hist_args share: upright_start, version, the optional shape / limb rows (``rows`` of them)."""
+    if version not in (1, 2):
+        raise ValueError(f"{fn}: version must be 1 or 2, got {version!r}")
+    a.upright_start, a.version = int(bool(upright)), int(version)
+    for name, t in (("shape_params", shape_params), ("limb_weights", limb_weights)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != rows:
+            raise TypeError(f"{fn}: {name} must be a ({rows}, k) float32 tensor on {dev} with unit column stride")
+        keep.append(t)
+        if name == "shape_params":
+            a.shape_params, a.shape_stride, a.num_shape = t.data_ptr(), t.stride(0), t.shape[1]
+        else:
+            a.limb_weights, a.limb_stride, a.num_limb = t.data_ptr(), t.stride(0), t.shape[1]
+    return a.num_shape, a.num_limb
 
 
 def build_amp_observations_smpl(rb, dof_pos, dof_vel, key_body_ids, *, joint_ids=None, zero_joints=(), local_root_obs=True,
-                                root_height_obs=True, out=None, env_ids=None, env_mask=None, hist_steps=0, window_out=None):
-    """phc/env/tasks/humanoid_amp.py:925-969 on the (N, bodies, 13) rigid-body records (root = body 0) and the
+                                root_height_obs=True, out=None, env_ids=None, env_mask=None, hist_steps=0, window_out=None,
+                                upright=True, version=1, shape_params=None, limb_weights=None):
+    """phc/env/tasks/humanoid_amp.py:925-969 (``version`` 2: :973-1017) on the (N, bodies, 13) rigid-body records (root = body 0) and the
     (N, num_dof) dof tensors.  ``joint_ids`` = dof_subset expressed in joints; ``zero_joints`` = joints whose dofs
-    read as zero (:636-639).  Writes the first W columns of ``out`` rows (any row pitch) and returns ``out``."""
+    read as zero (:636-639); ``upright`` False: remove_base_rot first (:929-930); ``shape_params`` (N, k) / ``limb_weights`` (N, k) rows are
+    appended (has_shape_obs_disc / has_limb_weight_obs, :963-966; pass the truncated view ``humanoid_shapes[:, :-6]``).
+    Writes the first W columns of ``out`` rows (any row pitch) and returns ``out``."""
     lib = _lib.load()
     rb = _dev(rb, "rb")
     n = rb.shape[0]
@@ -679,13 +703,14 @@ def build_amp_observations_smpl(rb, dof_pos, dof_vel, key_body_ids, *, joint_ids
     kb = _ids32(key_body_ids, dev)
     ji = _ids32(joint_ids, dev) if joint_ids is not None else None
     nj = ji.numel() if ji is not None else dof_pos.shape[-1] // 3
-    w = lib.pulse_amp_obs_width(nj, kb.numel(), int(root_height_obs))
+    a = AmpObsArgs()
+    keep = [kb, ji, dof_pos, dof_vel]
+    ns, nl = _amp_variant(a, "build_amp_observations_smpl", n, upright, version, shape_params, limb_weights, dev, keep)
+    w = lib.pulse_amp_obs_width_v(nj, kb.numel(), int(root_height_obs), int(version), ns, nl)
     if out is None:
         out = torch.empty(n, w, dtype=torch.float32, device=dev)
-    a = AmpObsArgs()
     a.rb, a.rb_env_stride = rb.data_ptr(), rb.stride()[0]
     a.dof_pos, a.dof_vel, a.num_dof, a.num_envs = dof_pos.data_ptr(), dof_vel.data_ptr(), dof_pos.shape[-1], n
-    keep = [kb, ji, dof_pos, dof_vel]
     if env_ids is not None:
         env_ids = _c(env_ids, "env_ids", torch.int64)
         keep.append(env_ids)
@@ -713,9 +738,11 @@ def build_amp_observations_smpl(rb, dof_pos, dof_vel, key_body_ids, *, joint_ids
     return out
 
 
-def amp_hist_init(motion_lib, motion_ids, start_times, dt, env_mask, hist, key_body_ids, *, joint_ids=None, local_root_obs=True, root_height_obs=True):
+def amp_hist_init(motion_lib, motion_ids, start_times, dt, env_mask, hist, key_body_ids, *, joint_ids=None, local_root_obs=True, root_height_obs=True,
+                  upright=True, version=1, shape_params=None, limb_weights=None):
     """_init_amp_obs_ref (humanoid_amp.py:531-563) for the masked envs: slots 1 .. S-1 of ``hist`` (N, S, W) := the AMP frames of each env's
-    motion at start_times - dt * (k + 1), in one launch (pulse_amp_hist_init)."""
+    motion at start_times - dt * (k + 1), in one launch (pulse_amp_hist_init).  ``shape_params`` / ``limb_weights`` hold one row per MOTION
+    (motion_bodies[:, :-6] / motion_limb_weights, :548-555); ``upright`` / ``version`` as build_amp_observations_smpl."""
     lib = _lib.load()
     dev = hist.device
     if hist.dtype != torch.float32 or hist.dim() != 3 or hist.stride(2) != 1 or not hist.is_cuda:
@@ -730,9 +757,11 @@ def amp_hist_init(motion_lib, motion_ids, start_times, dt, env_mask, hist, key_b
     kb = _ids32(key_body_ids, dev)
     ji = _ids32(joint_ids, dev) if joint_ids is not None else None
     nj = ji.numel() if ji is not None else motion_lib.num_bodies - 1
-    if lib.pulse_amp_obs_width(nj, kb.numel(), int(root_height_obs)) != w:
-        raise ValueError("amp_hist_init: the history's frame width does not match the joint / key-body selection")
     a = _lib.AmpHistArgs()
+    keep = []
+    ns, nl = _amp_variant(a, "amp_hist_init", motion_lib.num_motions(), upright, version, shape_params, limb_weights, dev, keep)
+    if lib.pulse_amp_obs_width_v(nj, kb.numel(), int(root_height_obs), int(version), ns, nl) != w:
+        raise ValueError("amp_hist_init: the history's frame width does not match the joint / key-body selection, version and rows")
     motion_lib.fill_tables(a.tab)
     a.motion_ids, a.start_times, a.dt = ids.data_ptr(), st.data_ptr(), float(dt)
     a.num_envs, a.env_mask, a.hist_steps = n, m.data_ptr(), s_

@@ -198,9 +198,19 @@ def _quat_rotate_xyzw(q, v):
     return v + w * t + torch.cross(qv, t, dim=-1)
 
 
-def synthetic_motion_library(g, num_motions, min_frames=45, max_frames=180, fps=30.0, humanoid="smpl"):
+def motion_shape_rows(g, num_motions):
+    """Per-motion body-shape rows as the reference's motion library carries them (motion_lib_base.py:289, 294: _motion_bodies (M, 17) = [gender, 10 betas,
+    6 unused], _motion_limb_weights (M, 10)); every column non-constant.  Draws from ``g`` only."""
+    bodies = torch.cat([torch.randint(0, 2, (num_motions, 1), generator=g).float(), _randn(g, num_motions, 10), _rand(g, num_motions, 6)], dim=-1)
+    limb = _rand(g, num_motions, 10) + 0.5
+    return bodies.contiguous(), limb.contiguous()
+
+
+def synthetic_motion_library(g, num_motions, min_frames=45, max_frames=180, fps=30.0, humanoid="smpl", shape_rows=False, shape_seed=7117):
     """dict of CPU tensors in the reference's table layout; frame f of motion m sits at length_starts[m] + f.  ``humanoid``: a key of
-    SKELETONS or a description dict (``parents`` is all that is read: any tree whose parents precede their children)."""
+    SKELETONS or a description dict (``parents`` is all that is read: any tree whose parents precede their children).
+    ``shape_rows``: also ``motion_bodies`` (M, 17) / ``motion_limb_weights`` (M, 10), drawn from a generator of their own (``shape_seed``) so
+    that the tables are the same draw for draw with and without them."""
     sk = skeleton(humanoid)
     parents = sk["parents"]
     m, j = num_motions, len(parents)
@@ -257,12 +267,15 @@ def synthetic_motion_library(g, num_motions, min_frames=45, max_frames=180, fps=
 
     gvs, gavs = fdiff(gts), ang_vel(grs)
     dvs = ang_vel(lrs)[:, 1:]
-    return {
+    tables = {
         "gts": gts.contiguous(), "grs": grs.contiguous(), "lrs": lrs.contiguous(), "gvs": gvs.contiguous(),
         "gavs": gavs.contiguous(), "dvs": dvs.contiguous(),
         "motion_num_frames": num_frames, "motion_fps": torch.full((m,), fps), "motion_dt": torch.full((m,), dt),
         "motion_lengths": ((1.0 / fps) * (num_frames - 1).double()).float(), "length_starts": starts,   # curr_len, motion_lib_base.py:263
     }
+    if shape_rows:
+        tables["motion_bodies"], tables["motion_limb_weights"] = motion_shape_rows(make_generator(shape_seed), m)
+    return tables
 
 
 # --------------------------------------------------------------------------- #
