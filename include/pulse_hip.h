@@ -36,7 +36,7 @@ extern "C" {
 #define PULSE_ERR_LAUNCH (-2)
 #define PULSE_ERR_UNSUPPORTED (-3)
 
-#define PULSE_ABI_VERSION 31
+#define PULSE_ABI_VERSION 32
 
 typedef void* pulse_stream_t; /* hipStream_t */
 
@@ -762,6 +762,27 @@ int pulse_vae_head_backward(const pulse_vae_head_bwd_args* args, pulse_stream_t 
 int pulse_sizeof_vae_embed_args(void);
 int pulse_sizeof_vae_kin_args(void);
 int pulse_sizeof_vae_head_bwd_args(void);
+
+/* ------------------------------------------------------------------------- *
+ * 4e. The MCP composer stage of PHC (v32): the policy's action is a weight vector over num_prim <= 32 frozen PNN primitives.
+ * ------------------------------------------------------------------------- */
+/* HumanoidImMCP.step, phc/env/tasks/humanoid_im_mcp.py:56-67:
+ *   actions[e * actions_stride + a] = sum_k w[e][k] * x[e * x_stride + k * a_pitch + a],  a < num_actions, k < num_prim
+ * (torch.sum(weights[:, :, None] * x_all, dim=1): every product rounded to fp32, summed with k ascending).  x is the primitives' outputs side by
+ * side, (rows, num_prim, a_pitch) with row stride x_stride >= num_prim * a_pitch.  discrete != 0: the weight row is first replaced by the one-hot of
+ * its first maximum (torch.argmax + one_hot(..).float(), :56-58).  rows == 0 is a no-op. */
+int pulse_mcp_compose(const float* weights, int64_t w_stride, const float* x, int64_t x_stride, int32_t a_pitch, int32_t rows, int32_t num_prim,
+                      int32_t num_actions, int32_t discrete, float* actions, int64_t actions_stride, pulse_stream_t s);
+/* AMPMCPBuilder.Network, phc/learning/amp_network_mcp_builder.py:53-55, 69, 81: the nn.Softmax(dim=1) appended to the composer when has_softmax;
+ *   mu[r][j] = exp(h[r][j] - max_k h[r][k]) / sum_k exp(h[r][k] - max), j < num_prim, h = the composer's activated output. */
+int pulse_mcp_head_forward(const float* h, int64_t h_stride, int32_t rows, int32_t num_prim, float* mu, int64_t mu_stride, pulse_stream_t s);
+/* The backward of that tail (autograd of amp_network_mcp_builder.py:41-55, 64-86 down to the last Linear's output z):
+ *   dh[j] = mu[j] * (dmu[j] - sum_k mu[k] dmu[k])   (mu != NULL: the softmax ran)      dh = dmu   (mu == NULL)
+ *   dz[j] = dh[j] * act'(z[j]) with the derivative taken from aux:  PULSE_ACT_NONE 1;  PULSE_ACT_RELU aux = the activated output, aux > 0;
+ *           PULSE_ACT_SILU aux = the pre-activation z, s (1 + z (1 - s));  PULSE_ACT_SILU_D aux = the derivative a PULSE_ACT_SILU_D forward stored.
+ * dz may alias dmu.  The last layer's weight-gradient and input-gradient GEMMs read dz. */
+int pulse_mcp_head_backward(const float* dmu, int64_t dmu_stride, const float* mu, int64_t mu_stride, const float* aux, int64_t aux_stride,
+                            int32_t activation, int32_t rows, int32_t num_prim, float* dz, int64_t dz_stride, pulse_stream_t s);
 
 /* out[i] = scale * sum_s slabs[s*slab_stride + i]  (deterministic split-K / partial-sum reduction) */
 int pulse_reduce_slabs(const float* slabs, int32_t num_slabs, int64_t slab_stride, int64_t count, float* out,

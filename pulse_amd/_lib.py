@@ -12,7 +12,7 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int6
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PULSE_HIP_LIB: another build of the SAME library (tools/im_step_repro.py compares compile variants); default = the in-tree build
 LIB_PATH = os.environ.get("PULSE_HIP_LIB") or os.path.join(_HERE, "csrc", "libpulse_hip.so")
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 PULSE_IM_SELF_OBS = 1
 PULSE_IM_TASK_OBS = 2
@@ -302,6 +302,9 @@ SIGNATURES = {
     "pulse_sizeof_vae_embed_args": (c_int, []),
     "pulse_sizeof_vae_kin_args": (c_int, []),
     "pulse_sizeof_vae_head_bwd_args": (c_int, []),
+    "pulse_mcp_compose": (c_int, [P, c_int64, P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, P, c_int64, P]),
+    "pulse_mcp_head_forward": (c_int, [P, c_int64, c_int32, c_int32, P, c_int64, P]),
+    "pulse_mcp_head_backward": (c_int, [P, c_int64, P, c_int64, P, c_int64, c_int32, c_int32, c_int32, P, c_int64, P]),
     "pulse_sizeof_gemm_x3p_desc": (c_int, []),
     "pulse_split_planes": (c_int, [P, c_int64, c_int32, c_int32, P, c_int64, c_int32, c_int32, P, P]),
     "pulse_reduce_slabs": (c_int, [P, c_int32, c_int64, c_int64, P, c_float, P]),

@@ -56,6 +56,23 @@ NETWORK_SEPT = {          # phc/data/cfg/learning/pulse_z_terrain.yaml:12-51 (ne
     "task_mlp": {"units": [512, 256], "activation": "silu", "d2rl": False, "initializer": {"name": "default"}},
 }
 
+NETWORK_MCP = {           # phc/data/cfg/learning/im_mcp.yaml:11-45 (network: amp_mcp; ending_act is read by nothing in the reference)
+    "name": "amp_mcp", "separate": True, "discrete": False, "has_softmax": False, "ending_act": True,
+    "space": {"continuous": {"mu_activation": "None", "sigma_activation": "None", "mu_init": {"name": "default"},
+                             "sigma_init": {"name": "const_initializer", "val": -2.9}, "fixed_sigma": True, "learn_sigma": False}},
+    "mlp": {"units": [1024, 512], "activation": "relu", "d2rl": False, "initializer": {"name": "default"}},
+    "disc": {"units": [1024, 512], "activation": "relu", "initializer": {"name": "default"}},
+}
+
+# phc/data/cfg/env/phc_kp_mcp_iccv.yaml:23-80 (task HumanoidImMCPGetup): the switches this package reads; ``models`` is the synthetic PNN
+# checkpoint make_env builds (the shipped file names output/phc_kp_pnn_iccv/Humanoid.pth)
+ENV_MCP = {"fut_tracks": False, "obs_v": 7, "has_pnn": True, "fitting": True, "num_prim": 4, "training_prim": 2, "actors_to_load": 4,
+           "has_lateral": False, "zero_out_far": True, "zero_out_far_train": False, "cycle_motion": False, "getup_udpate_epoch": 95000,
+           "getup_schedule": True, "recoverySteps": 90, "zero_out_far_steps": 90, "recoveryEpisodeProb": 0.5, "fallInitProb": 0.3,
+           "power_reward": True, "power_coefficient": 0.00005, "shape_resampling_interval": 500, "controlFrequencyInv": 2, "stateInit": "Random",
+           "enableEarlyTermination": True, "terminationDistance": 0.25, "numTrajSamples": 3, "trajSampleTimestepInv": 3, "enableTaskObs": True,
+           "episode_length": 300}
+
 ENV_TERRAIN_Z = {"local_root_obs": True, "root_height_obs": True, "enableEarlyTermination": True, "episode_length": 300, "enableTaskObs": True,
                  "numTrajSamples": 10, "trajSampleTimestep": 0.5, "speedMin": 0.0, "speedMax": 3.0, "accelMax": 2.0, "sharpTurnProb": 0.02,
                  "terrain_obs": True, "terrain_obs_type": "square", "terrain_obs_root": "head", "use_center_height": True, "power_reward": False,
@@ -91,6 +108,10 @@ CONFIGS = {
     "terrain_z": {"num_envs": 1536, "horizon_length": 32, "minibatch_size": 16384, "network": "amp_sept", "env": "terrain_z", "agent": "amp"},
     "terrain_z_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_sept", "env": "terrain_z", "agent": "amp",
                         "units": [256, 128]},
+    # PHC's second stage (learning=im_mcp, env=phc_kp_mcp_iccv): the composer over 4 frozen PNN primitives, HumanoidImMCPGetup, 1536 envs
+    "mcp": {"num_envs": 1536, "horizon_length": 32, "minibatch_size": 16384, "network": "amp_mcp", "env": "mcp", "agent": "amp"},
+    "mcp_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_mcp", "env": "mcp", "agent": "amp",
+                  "units": [256, 128]},
     # small shapes of the same graphs for tests
     "cfg3_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_z", "env": "vae", "agent": "amp",
                    "extra": {"use_seq_rl": True}},
@@ -111,6 +132,10 @@ def agent_config(name, **overrides):
         net = copy.deepcopy(NETWORK_Z)
     elif c.get("network") == "amp_sept":
         net = copy.deepcopy(NETWORK_SEPT)
+        if "units" in c:
+            net["mlp"]["units"] = list(c["units"])
+    elif c.get("network") == "amp_mcp":
+        net = copy.deepcopy(NETWORK_MCP)
         if "units" in c:
             net["mlp"]["units"] = list(c["units"])
     elif c.get("network") == "amp_z_reader":
@@ -153,6 +178,25 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
                                                  "vae_var_clamp_max": 2}, device=device)
         rms = {"running_mean": torch.zeros(934, dtype=torch.float64), "running_var": torch.ones(934, dtype=torch.float64)}
         task.initialize_z_models({"model": znet.state_dict(), "running_mean_std": rms}, NETWORK_Z)
+        return VecTaskPythonWrapper(task, rl_device=device), None
+    if env_kind == "mcp":
+        # HumanoidImMCPGetup over the motion library (the get-up task needs its reference-state init) with a synthetic PNN checkpoint of
+        # num_prim primitives sized to the env's observation
+        from . import synthetic as syn
+        from .env.humanoid_im_mcp import HumanoidImMCPGetup, check_mcp_options
+        from .env.motion_lib import MotionLib
+        from .env.sim import KinematicSim, PdSim
+        env_cfg = dict(ENV_MCP)
+        env_cfg.update(env_overrides or {})
+        cfg = {"env": env_cfg} if humanoid == "smpl" else {"env": env_cfg, "robot": robot}
+        opts = check_mcp_options(cfg, "HumanoidImMCPGetup")
+        motion = MotionLib.from_tables(syn.synthetic_motion_library(syn.make_generator(seed + 5, rank), min(num_envs, 1024)), device)
+        sim_cls = PdSim if env_cfg.pop("physics", "tracking") == "pd" else KinematicSim
+        sim = sim_cls(num_envs, horizon + 1, device, seed=seed, rank=rank)
+        # env.models given: that checkpoint (path or dict); otherwise the synthetic one, sized once the env knows its observation width
+        make = None if env_cfg.get("models") else (lambda t: syn.synthetic_pnn_checkpoint(opts["num_prim"], in_dim=t.num_obs, seed=seed + 11,
+                                                                                          has_lateral=opts["has_lateral"]))
+        task = HumanoidImMCPGetup(cfg, sim, motion, device=device, pnn_checkpoint=make)
         return VecTaskPythonWrapper(task, rl_device=device), None
     env_cfg = dict(ENV_IM_VAE) if env_kind in ("vae", "vae_ppo") else dict(ENV_IM)
     if env_kind == "vae_ppo":

@@ -56,6 +56,7 @@ SOURCES = [
     ("learner_ops.hip", NO_CONTRACT),
     ("b16_ops.hip", NO_CONTRACT),
     ("vae_head.hip", NO_CONTRACT),
+    ("mcp.hip", NO_CONTRACT),
 ]
 
 

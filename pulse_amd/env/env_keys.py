@@ -37,6 +37,8 @@ HONOURED = {
     "temp_running_mean", "kin_lr", "save_kin_info", "only_kin_loss", "distill", "z_type", "kld_coefficient", "kld_coefficient_min",
     "ar1_coefficient", "kld_anneal", "use_ar1_prior", "use_vae_prior", "use_vae_prior_regu", "embedding_size", "embedding_norm",
     "use_vae_clamped_prior", "vae_var_clamp_max", "proj_norm", "auto_pmcp", "auto_pmcp_soft", "shape_resampling_interval", "fitting", "models",
+    # MCP composer stage (humanoid_im_mcp.py:16-28): the action is a weight vector over num_prim frozen PNN primitives (env/humanoid_im_mcp.py)
+    "num_prim", "discrete_moe", "has_pnn", "has_lateral", "z_activation",
     # get-up task (humanoid_im_getup.py:42-66)
     "recoveryEpisodeProb", "recoverySteps", "fallInitProb", "getup_schedule", "getup_udpate_epoch",
     # downstream tasks (humanoid_speed.py / _reach.py / _strike.py / _traj.py / _pedestrian_terrain.py)
@@ -53,7 +55,7 @@ _SIM = "Isaac Gym scene / actor / asset creation (closed-source physics: out of 
 _LOAD = "consumed while motions are loaded (motion_lib_smpl / resample_motions: AMASS + smpl_sim, out of scope): the caller hands over a built MotionLib"
 _VIEW = "viewer / debug drawing (out of scope)"
 _DEAD = "the reference stores it in an attribute that nothing on the training path reads"
-_TEACH = "passed through get_task_obs_size_detail to the teacher / PNN network builders (learning/teacher.py takes its structure as arguments)"
+_TEACH = "steers which PNN column trains / loads (amp_network_pnn_builder.py): PNN training is not built, the primitives come frozen from a checkpoint"
 
 INERT = {
     "task": "selects the task class (utils/parse_task.py:57-70): the caller instantiates the class",
@@ -65,7 +67,7 @@ INERT = {
     "motion_file": _LOAD, "min_length": _LOAD, "max_len": _LOAD, "seq_motions": _LOAD, "hard_negative": _LOAD,
     "eval_full": _DEAD, "kin_policy": _DEAD, "partial_running_mean": _DEAD, "vae_reader": _DEAD, "z_model": _DEAD, "z_read": _DEAD,
     "z_uniform": _DEAD, "use_vae_prior_loss": _DEAD, "velocity_map": _DEAD, "tarSpeed": _DEAD,
-    "num_prim": _TEACH, "training_prim": _TEACH, "actors_to_load": _TEACH, "has_lateral": _TEACH,
+    "training_prim": _TEACH, "actors_to_load": _TEACH,
     "distill_model_config": "structure of the frozen PULSE networks: HumanoidZ.initialize_z_models takes the checkpoint and network params as arguments",
     "hybridInitProb": "only read when stateInit is Hybrid (humanoid_amp.py:490-505), which raises here",
     "dict_size": "VQ dictionary size: only read for z_type vq_vae variants, which raise here",

@@ -347,6 +347,39 @@ def vae_head_backward(zheads, dzheads, *, rows, embedding_size, horizon=1, phead
 
 
 # --------------------------------------------------------------------------- #
+# MCP composer head (include/pulse_hip.h section 4e)
+# --------------------------------------------------------------------------- #
+def _mcp_rows(t, name, rows, cols):
+    _chk(t, name)
+    if t.dim() != 2 or t.shape[0] != rows or t.shape[1] < cols:
+        raise ValueError(f"{name}: expected a ({rows}, >= {cols}) tensor, got {tuple(t.shape)}")
+    if rows > 1 and t.stride(0) < cols:
+        raise ValueError(f"{name}: row stride {t.stride(0)} does not cover {cols} columns")
+    return t.data_ptr(), (t.stride(0) if rows > 1 else max(cols, t.shape[1]))
+
+
+def mcp_head_forward(h, mu, *, rows, num_prim):
+    """mu[:, :num_prim] = softmax(h[:, :num_prim], dim=1): the nn.Softmax AMPMCPBuilder appends to the composer (amp_network_mcp_builder.py:53-55)."""
+    hp, hs = _mcp_rows(h, "h", rows, num_prim)
+    mp, ms = _mcp_rows(mu, "mu", rows, num_prim)
+    _lib.check(_lib.load().pulse_mcp_head_forward(hp, hs, rows, num_prim, mp, ms, _stream()), "pulse_mcp_head_forward")
+    return mu
+
+
+def mcp_head_backward(dmu, dz, *, rows, num_prim, mu=None, aux=None, activation=ACT_NONE):
+    """dz = (softmax backward of dmu when ``mu`` is given, else dmu) * act'(.) with the derivative taken from ``aux`` (ACT_RELU: the activated
+    output; ACT_SILU: the pre-activation; ACT_SILU_D: the stored derivative): the composer's tail down to its last Linear's output."""
+    if activation != ACT_NONE and aux is None:
+        raise ValueError("mcp_head_backward: the activation's derivative needs aux")
+    dp, ds = _mcp_rows(dmu, "dmu", rows, num_prim)
+    zp, zs = _mcp_rows(dz, "dz", rows, num_prim)
+    mp, ms = _mcp_rows(mu, "mu", rows, num_prim) if mu is not None else (None, 0)
+    ap, as_ = _mcp_rows(aux, "aux", rows, num_prim) if aux is not None else (None, 0)
+    _lib.check(_lib.load().pulse_mcp_head_backward(dp, ds, mp, ms, ap, as_, int(activation), rows, num_prim, zp, zs, _stream()), "pulse_mcp_head_backward")
+    return dz
+
+
+# --------------------------------------------------------------------------- #
 # planar ("x3p") fp32-grade GEMM: operands kept pre-split in HBM as three bf16 planes (include/pulse_hip.h section 4b)
 # --------------------------------------------------------------------------- #
 def planes_pitch(cols):

@@ -101,7 +101,9 @@ class AMPAgent(CommonAgent):
             # them, and take every network tensor whose name and shape match (load_my_state_dict, :27-33)
             if not getattr(task, "models_path", None):
                 raise ValueError("env.fitting is set but env.models names no checkpoint to take the normaliser statistics from")
-            checkpoint = torch.load(task.models_path[0], map_location=self.ppo_device)
+            checkpoint = task.models_path[0]
+            if not isinstance(checkpoint, dict):                          # (an env built from a checkpoint dict hands the dict on)
+                checkpoint = torch.load(checkpoint, map_location=self.ppo_device)
             self.set_stats_weights(checkpoint)
             self.freeze_state_weights()
             self._load_matching_state(checkpoint["model"])

@@ -134,6 +134,8 @@ class CommonAgent:
         seed = int(config.get("seed", 0)) + self.rank                       # run_hydra.py:124
         self.noise_generator = torch.Generator(device=self.ppo_device)
         self.noise_generator.manual_seed(seed)
+        if self.mixed_precision and config["network"].get("name", "amp") == "amp_mcp":
+            raise NotImplementedError("mixed_precision with network amp_mcp: the composer graph and its head kernels run fp32 (im_mcp.yaml: False)")
         self.model = self._build_model(net_config)
         if self.mixed_precision:
             if not hasattr(self.model, "mixed_precision"):
@@ -199,6 +201,13 @@ class CommonAgent:
             return AMPSeptModel(params, actions_num=net_config["actions_num"], self_obs_size=task.get_self_obs_size(),
                                 task_obs_size=task.get_task_obs_size(), task_obs_size_detail=task.get_task_obs_size_detail(),
                                 device=self.ppo_device, split_k=int(self.config.get("split_k", 8)))
+        if params.get("name", "amp") == "amp_mcp":
+            # AMPMCPBuilder.Network (amp_network_mcp_builder.py:23-87): mu = the composer's num_prim mixture weights (HumanoidImMCP blends the primitives)
+            from .network_mcp import AMPMCPModel
+            task = self.vec_env.env.task
+            return AMPMCPModel(params, actions_num=net_config["actions_num"], self_obs_size=task.get_self_obs_size(),
+                               task_obs_size=task.get_task_obs_size(), task_obs_size_detail=task.get_task_obs_size_detail(),
+                               device=self.ppo_device, split_k=int(self.config.get("split_k", 8)))
         if params.get("name", "amp") == "amp_z_reader":
             # AMPZReaderBuilder.Network (amp_network_z_reader_builder.py:21-57) IS AMPBuilder.Network -- the plain actor / critic MLP
             # whose 32-d "action" is the latent a frozen PULSE decoder turns into joint targets inside env.step -- unless

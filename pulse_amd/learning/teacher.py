@@ -41,7 +41,9 @@ class PnnTeacher:
     def __init__(self, pnn_checkpoint, composer_checkpoint, num_prim, num_envs, activation="silu", has_lateral=False, device="cuda:0"):
         if activation not in _ACTS:
             raise NotImplementedError(f"teacher activation {activation!r}: relu / silu are built")
-        pm, cm = pnn_checkpoint["model"], composer_checkpoint["model"]
+        # composer_checkpoint None: the frozen primitives alone (HumanoidImMCP loads only load_pnn(...) and the running statistics,
+        # humanoid_im_mcp.py:24-28; the composer is the policy being trained)
+        pm, cm = pnn_checkpoint["model"], (composer_checkpoint["model"] if composer_checkpoint is not None else None)
         act = _ACTS[activation]
         self.device, self.n, self.num_prim = torch.device(device), num_envs, num_prim
         self.book = ParamBook(self.device, split_k=1)
@@ -78,11 +80,13 @@ class PnnTeacher:
                 units = [s[0] for s in sizes[:-1]]
                 self._lins += g.mlp(self.book, f"a2c_network.pnn.actors.{k}", "x", self.in_dim, units, act, [f"p{k}h{i}" for i in range(len(units))],
                                     final_linear=sizes[-1][0], final_dst="acts", final_dst_col=k * self.a_pitch)
-        csizes = _layer_sizes(cm, "a2c_network.composer")
-        cunits = [s[0] for s in csizes]
-        if cunits[-1] != num_prim:
-            raise ValueError(f"composer emits {cunits[-1]} weights for {num_prim} primitives")
-        self._clins = g.mlp(self.book, "a2c_network.composer", "x", self.in_dim, cunits, act, [f"ch{i}" for i in range(len(cunits) - 1)] + ["w"])
+        self._clins = []
+        if cm is not None:
+            csizes = _layer_sizes(cm, "a2c_network.composer")
+            cunits = [s[0] for s in csizes]
+            if cunits[-1] != num_prim:
+                raise ValueError(f"composer emits {cunits[-1]} weights for {num_prim} primitives")
+            self._clins = g.mlp(self.book, "a2c_network.composer", "x", self.in_dim, cunits, act, [f"ch{i}" for i in range(len(cunits) - 1)] + ["w"])
         self.book.finalize(trainable=False)
         for lin in self._lins:
             self.book.set(lin.w.name, pm[lin.w.name])
@@ -103,13 +107,25 @@ class PnnTeacher:
     def parameters_count(self):
         return self.book.n_flat
 
+    def normalize(self, obs_store):
+        """clamp((obs - running_mean) / sqrt(running_var + 1e-5), +-5) of the env's (N, pitch) observation rows into the networks' input buffer."""
+        K.rms_normalize(obs_store, self.running_mean, self.running_var, rows=self.n, cols=self.in_dim, x_stride=obs_store.stride(0), y=self.x,
+                        y_stride=self.x.stride(0), y_cols=self.x.shape[1], clip=5.0)
+        return self.x
+
+    def primitives(self):
+        """Run the frozen networks on the normalised observation in ``self.x`` -> the primitives' outputs side by side, (N, num_prim, a_pitch)
+        (columns num_actions .. a_pitch of each primitive are padding)."""
+        self._plan.run()
+        return self.g.act_bufs["acts"].view(self.n, self.num_prim, self.a_pitch)
+
     def forward(self, obs_store):
         """obs_store: the env's (N, pitch) observation rows (first in_dim columns used) -> gt_action (N, 69)."""
+        if not self._clins:
+            raise RuntimeError("PnnTeacher.forward needs the composer (composer_checkpoint=None builds the primitives only: normalize / primitives)")
         n = self.n
-        K.rms_normalize(obs_store, self.running_mean, self.running_var, rows=n, cols=self.in_dim, x_stride=obs_store.stride(0), y=self.x,
-                        y_stride=self.x.stride(0), y_cols=self.x.shape[1], clip=5.0)
-        self._plan.run()
-        acts = self.g.act_bufs["acts"].view(n, self.num_prim, self.a_pitch)[:, :, :self.num_actions]
+        self.normalize(obs_store)
+        acts = self.primitives()[:, :, :self.num_actions]
         w = self.g.act_bufs["w"][:, :self.num_prim]
         torch.sum(w[:, :, None] * acts, dim=1, out=self.gt_action)
         return self.gt_action

@@ -924,3 +924,36 @@ def traj_step(rb, verts, progress, *, what, dt, episode_dur, num_samples=10, sam
         out["reset"], out["terminate"] = reset, terminate
     _lib.check(_lib.load().pulse_traj_step(ctypes.byref(a), _stream()), "pulse_traj_step")
     return out
+
+
+# --------------------------------------------------------------------------- #
+# MCP composer stage (include/pulse_hip.h section 4e)
+# --------------------------------------------------------------------------- #
+def _rows2d(t, name, rows, cols):
+    """A (rows, >= cols) float32 GPU view with unit column stride (the row stride is the pitch the kernel gets)."""
+    _dev(t, name)
+    if t.dim() != 2 or t.shape[0] != rows or t.shape[1] < cols or (t.numel() > 0 and (t.stride(1) != 1 or (rows > 1 and t.stride(0) < t.shape[1]))):
+        raise ValueError(f"{name}: expected a ({rows}, >= {cols}) view with unit column stride, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
+    return t
+
+
+def mcp_compose(weights, x, out=None, *, num_actions=None, discrete=False):
+    """HumanoidImMCP.step's mixture (phc/env/tasks/humanoid_im_mcp.py:56-67): ``weights`` (N, P), ``x`` (N, P, a_pitch) -- the primitives'
+    outputs side by side, rows may be pitched views -- -> actions (N, num_actions) = sum_k weights[:, k, None] * x[:, k, :num_actions].
+    ``discrete``: the weight row becomes one_hot(argmax) first (:56-58)."""
+    _dev(weights, "weights"), _dev(x, "x")
+    if x.dim() != 3 or weights.dim() != 2 or x.shape[0] != weights.shape[0] or x.shape[1] != weights.shape[1]:
+        raise ValueError(f"mcp_compose: weights (N, P) and x (N, P, a_pitch) expected, got {tuple(weights.shape)} and {tuple(x.shape)}")
+    n, p = weights.shape
+    _rows2d(weights, "weights", n, p)
+    if x.numel() > 0 and (x.stride(2) != 1 or x.stride(1) < x.shape[2] or (n > 1 and x.stride(0) < p * x.stride(1))):
+        raise ValueError(f"x: expected (N, P, a_pitch) rows with unit inner stride, got strides {tuple(x.stride())}")
+    a = int(num_actions) if num_actions is not None else x.shape[2]
+    if not 1 <= a <= x.shape[2]:
+        raise ValueError(f"mcp_compose: num_actions = {a} outside 1 .. {x.shape[2]}")
+    if out is None:
+        out = torch.empty(n, a, dtype=torch.float32, device=x.device)
+    _rows2d(out, "out", n, a)
+    _lib.check(_lib.load().pulse_mcp_compose(_ptr(weights), weights.stride(0) if n else p, _ptr(x), x.stride(0) if n else p * x.stride(1), x.stride(1),
+                                             n, p, a, int(bool(discrete)), _ptr(out), out.stride(0) if n else a, _stream()), "pulse_mcp_compose")
+    return out[:, :a]

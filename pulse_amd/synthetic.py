@@ -320,3 +320,28 @@ def center_height_points():
     x, y = torch.tensor(np.linspace(-0.1, 0.1, 3)), torch.tensor(np.linspace(-0.2, 0.2, 3))
     gx, gy = torch.meshgrid(x, y, indexing="ij")
     return torch.stack([gx.flatten(), gy.flatten()], dim=1).float()
+
+
+def synthetic_pnn_checkpoint(num_prim=4, in_dim=934, units=(96, 64), num_actions=69, seed=0, has_lateral=False):
+    """A seeded stand-in for a trained PNN checkpoint (output/phc_kp_pnn_iccv/Humanoid.pth) with the keys ``load_pnn`` reads
+    (phc/learning/network_loader.py:54-73): ``a2c_network.pnn.actors.<k>.<2i>.{weight,bias}``, with ``has_lateral`` the bias-free lateral
+    links ``a2c_network.pnn.u.<i>.<j>.{0,1}.weight`` (pnn.py:24-37), ``a2c_network.mu.bias`` (the action size) and ``running_mean_std``."""
+    g = make_generator(seed)
+    units = list(units)
+    pm = {}
+    for k in range(num_prim):
+        i = in_dim
+        for li, u in enumerate(units + [num_actions]):
+            pm[f"a2c_network.pnn.actors.{k}.{2 * li}.weight"] = _randn(g, u, i) / i ** 0.5
+            pm[f"a2c_network.pnn.actors.{k}.{2 * li}.bias"] = 0.1 * _randn(g, u)
+            i = u
+    if has_lateral:
+        if len(units) != 2:
+            raise ValueError("lateral PNN columns have exactly two hidden layers (pnn.py:96)")
+        for i in range(num_prim - 1):
+            for j in range(i + 1):
+                pm[f"a2c_network.pnn.u.{i}.{j}.0.weight"] = _randn(g, units[1], units[0]) / units[0] ** 0.5
+                pm[f"a2c_network.pnn.u.{i}.{j}.1.weight"] = _randn(g, num_actions, units[-1]) / units[-1] ** 0.5
+    pm["a2c_network.mu.weight"], pm["a2c_network.mu.bias"] = _randn(g, num_actions, units[-1]), _randn(g, num_actions)
+    rms = {"running_mean": (0.3 * _randn(g, in_dim)).double(), "running_var": (_rand(g, in_dim) + 0.5).double(), "count": torch.tensor(1e4).double()}
+    return {"model": pm, "running_mean_std": rms}
