@@ -36,7 +36,7 @@ extern "C" {
 #define PULSE_ERR_LAUNCH (-2)
 #define PULSE_ERR_UNSUPPORTED (-3)
 
-#define PULSE_ABI_VERSION 32
+#define PULSE_ABI_VERSION 33
 
 typedef void* pulse_stream_t; /* hipStream_t */
 
@@ -396,6 +396,54 @@ typedef struct pulse_motion_state_args {
 } pulse_motion_state_args;
 int pulse_sizeof_motion_state_args(void);
 int pulse_motion_state(const pulse_motion_state_args* args, pulse_stream_t s);
+
+/* ------------------------------------------------------------------------- *
+ * 2b'. Building the packed records from raw clips: what MotionLibSMPL.load_motion_with_skeleton
+ *      (phc/utils/motion_lib_smpl.py:101-174, the mesh_parsers-is-None path: fix_trans_height adds 0)
+ *      computes per clip with poselib on the CPU, for every resident clip at once:
+ *        heading randomisation (:131-140): q <- Rz(angle) q, root translation <- Rz(angle) t (in fp64, as scipy does);
+ *        lrs   SkeletonState.local_rotation (poselib skeleton3d.py:444-460): root = global rotation, body b =
+ *              quat_mul_norm(quat_inverse(g[parent]), g[b])   (rotation3d.py:15-38, 93-98, 197-202);
+ *        gts   SkeletonState.global_transformation / transform_mul (skeleton3d.py:390-426, 472-482; rotation3d.py:318-326):
+ *              root = translation, child = quat_rotate(R[parent], local_translation[b]) + t[parent] with
+ *              R[b] = quat_mul_norm(R[parent], lrs[b]) carried down the tree;
+ *        grs   the input rotations after the heading rotation;
+ *        gvs   SkeletonMotion._compute_velocity (:1100-1107): np.gradient over the clip's frames / dt, then
+ *              scipy gaussian_filter1d(sigma 2, mode "nearest": radius 8, indices clamped to the clip's ends);
+ *        gavs  SkeletonMotion._compute_angular_velocity (:1110-1118): quat_mul_norm(r[t+1], inverse(r[t])) (identity at the
+ *              last frame) -> quat_angle_axis (rotation3d.py:231-240) -> axis * angle / dt, the same filter;
+ *        dvs   compute_motion_dof_vels / local_rotation_to_dof_vel (motion_lib_base.py:47-70): torch_utils.quat_mul(conj(l[t]),
+ *              l[t+1]) -> quat_to_angle_axis -> axis * angle / dt for bodies 1 .. J-1, the last frame repeats the one before.
+ *      Two launches: per frame (heading, lrs, FK, grs; padding columns zeroed), then per (frame, body) the three velocity
+ *      fields from the first pass's records.  Output: the records of section 2b, written in place (no per-field tables).
+ *      Frame t of clip m is read from staged frame clip_src_start[m] + clip_crop_start[m] + t and written to record
+ *      clip_out_start[m] + t; no filter tap reads across a clip boundary of the packed table.
+ * ------------------------------------------------------------------------- */
+typedef struct pulse_motion_build_args {
+    /* staged raw data, device */
+    const float* src_rot;               /* (src_frames, J, 4) global rotations xyzw, 16-byte aligned */
+    const float* src_trans;             /* (src_frames, 3) root translations */
+    int64_t src_frames;
+    int32_t num_clips;                  /* M resident clips */
+    int32_t num_bodies;                 /* J in [1, 64] */
+    const int64_t* clip_src_start;      /* (M) device: first staged frame of the clip's source */
+    const int64_t* clip_crop_start;     /* (M) device, optional: frames of the source skipped at the front (max_len crop, motion_lib_smpl.py:117-126) */
+    const int64_t* clip_out_start;      /* (M + 1) device: first record of clip m; [M] = total_frames (clip m has [m+1] - [m] frames) */
+    const int64_t* clip_frames_host;    /* (M) HOST copy of the frame counts: validated (>= 2 each, sum = total_frames) before anything is launched */
+    const float* clip_dt;               /* (M) device: fp32(1 / fps) */
+    const float* clip_heading;          /* (M) device, optional: heading angle in radians (NULL under im_eval: no rotation, grs = input bit for bit) */
+    const float* local_translation;     /* (M, J, 3) device: the bone offsets of each clip's own skeleton (body shape) */
+    const int32_t* parent_indices_host; /* (J) HOST: parent of every body, -1 for body 0, parent < child (the order poselib's FK loop relies on,
+                                           skeleton3d.py:398-406); handed to the kernels by value together with the tree depth of every body */
+    /* output records (section 2b) */
+    float* frames;                      /* (total_frames, frame_stride), 16-byte aligned */
+    int64_t total_frames;
+    int64_t frame_stride;               /* floats, multiple of 4 */
+    int32_t off_gts, off_grs, off_lrs, off_gvs, off_gavs, off_dvs;   /* the six fields tile [0, 20 J - 3) without overlap; the rest of a record is padding */
+    float filter_w[9];                  /* scipy _gaussian_kernel1d(sigma 2, radius 8) weights of |tap| = 0 .. 8, computed in double on the host */
+} pulse_motion_build_args;
+int pulse_sizeof_motion_build_args(void);
+int pulse_motion_build(const pulse_motion_build_args* args, pulse_stream_t s);
 
 /* ------------------------------------------------------------------------- *
  * 2c. Per-step rollout bookkeeping of play_steps (phc/learning/amp_agent.py:372-412,

@@ -12,7 +12,7 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int6
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PULSE_HIP_LIB: another build of the SAME library (tools/im_step_repro.py compares compile variants); default = the in-tree build
 LIB_PATH = os.environ.get("PULSE_HIP_LIB") or os.path.join(_HERE, "csrc", "libpulse_hip.so")
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 PULSE_IM_SELF_OBS = 1
 PULSE_IM_TASK_OBS = 2
@@ -38,6 +38,15 @@ class MotionTables(Structure):
                 ("off_dvs", c_int32),
                 ("motion_lengths", c_void_p), ("motion_dt", c_void_p), ("motion_num_frames", c_void_p), ("length_starts", c_void_p),
                 ("num_motions", c_int32)]
+
+
+class MotionBuildArgs(Structure):
+    _fields_ = [("src_rot", c_void_p), ("src_trans", c_void_p), ("src_frames", c_int64), ("num_clips", c_int32), ("num_bodies", c_int32),
+                ("clip_src_start", c_void_p), ("clip_crop_start", c_void_p), ("clip_out_start", c_void_p), ("clip_frames_host", c_void_p),
+                ("clip_dt", c_void_p), ("clip_heading", c_void_p), ("local_translation", c_void_p), ("parent_indices_host", c_void_p),
+                ("frames", c_void_p), ("total_frames", c_int64), ("frame_stride", c_int64),
+                ("off_gts", c_int32), ("off_grs", c_int32), ("off_lrs", c_int32), ("off_gvs", c_int32), ("off_gavs", c_int32), ("off_dvs", c_int32),
+                ("filter_w", c_float * 9)]
 
 
 class ImStepArgs(Structure):
@@ -288,6 +297,8 @@ SIGNATURES = {
     "pulse_pd_sim_step": (c_int, [POINTER(PdSimArgs), P]),
     "pulse_sizeof_motion_state_args": (c_int, []),
     "pulse_motion_state": (c_int, [POINTER(MotionStateArgs), P]),
+    "pulse_sizeof_motion_build_args": (c_int, []),
+    "pulse_motion_build": (c_int, [POINTER(MotionBuildArgs), P]),
     "pulse_gae": (c_int, [P, P, P, P, c_int32, c_int32, c_int64, c_int64, c_float, c_float, P, P, P]),
     "pulse_sizeof_gemm_desc": (c_int, []),
     "pulse_gemm_f32": (c_int, [POINTER(GemmDesc), P]),

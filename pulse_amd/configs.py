@@ -156,7 +156,9 @@ def agent_config(name, **overrides):
 def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kind="im", reference="recorded", env_overrides=None, humanoid="smpl"):
     """``humanoid``: 'smpl' (24 bodies) | 'smplx' / 'smplh' (52 bodies) -- the robot config handed to the task as cfg.robot.
     ``reference``: 'recorded' = pre-recorded rigid-body / reference frames (RecordedRollout, what the CPU oracle agent replays);
-    'motion_lib' = reference motion queried from the HBM-resident MotionLib every step, physics stand-in tracking it."""
+    'motion_lib' = reference motion queried from the HBM-resident MotionLib every step, physics stand-in tracking it;
+    'motion_data' = the same, with the library built on the device from synthetic RAW clips (MotionLib.from_motion_data: one resident clip per
+    env out of min(num_envs, 1024) / 2 + 1 unique ones, re-drawn by resample_motions)."""
     from .env.humanoid_im import HumanoidIm, VecTaskPythonWrapper, check_humanoid_options
     if humanoid not in ROBOTS:
         raise NotImplementedError(f"humanoid {humanoid!r}: 'smpl', 'smplh' and 'smplx' are built")
@@ -204,15 +206,21 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
     if env_kind == "amp":
         env_cfg.update({"enable_amp_obs": True, "numAMPObsSteps": 10})
     env_cfg.update(env_overrides or {})
-    if reference == "motion_lib":
+    if reference in ("motion_lib", "motion_data"):
         from . import synthetic as syn
         from .env.motion_lib import MotionLib
         from .env.sim import KinematicSim, PdSim
         cfg = {"env": env_cfg} if humanoid == "smpl" else {"env": env_cfg, "robot": robot}
         check_humanoid_options(cfg)                     # an unbuilt combination raises by name before anything is allocated
         disc_rows = any(bool(dict(robot if humanoid != "smpl" else {}, **env_cfg).get(k, False)) for k in ("has_shape_obs_disc", "has_weight_obs_disc"))
-        tables = syn.synthetic_motion_library(syn.make_generator(seed + 5, rank), min(num_envs, 1024), humanoid=humanoid, shape_rows=disc_rows)
-        motion = MotionLib.from_tables(tables, device)
+        if reference == "motion_data":
+            g = syn.make_generator(seed + 5, rank)
+            data, trees = syn.synthetic_motion_data(g, min(num_envs, 1024) // 2 + 1, humanoid=humanoid, num_slots=num_envs)
+            bodies, limb = syn.motion_shape_rows(syn.make_generator(7117), num_envs)
+            motion = MotionLib.from_motion_data(data, trees, gender_betas=bodies, limb_weights=limb, device=device, generator=g)
+        else:
+            tables = syn.synthetic_motion_library(syn.make_generator(seed + 5, rank), min(num_envs, 1024), humanoid=humanoid, shape_rows=disc_rows)
+            motion = MotionLib.from_tables(tables, device)
         sim_cls = PdSim if env_cfg.pop("physics", "tracking") == "pd" else KinematicSim        # "pd": action-dependent stand-in
         sim = sim_cls(num_envs, horizon + 1, device, seed=seed, rank=rank, humanoid=humanoid)
         task = HumanoidIm(cfg, sim, motion, device=device)

@@ -7,7 +7,7 @@ silently ignored here would change what a shipped configuration computes without
 ``zero_out_far``).  ``audit`` therefore sorts EVERY key of an env dict into one of three classes:
 
   HONOURED   this package reads the key and does what the reference does with it;
-  INERT      the key configures a subsystem that is out of scope by contract (Isaac Gym scene / asset creation, the viewer, AMASS loading)
+  INERT      the key configures a subsystem that is out of scope by contract (Isaac Gym scene / asset creation, the viewer, reading motion files from disk)
              or is read by the reference into an attribute nothing consumes; accepted and ignored, with the reason recorded below;
   UNBUILT    the reference acts on the key, this package does not: accepted ONLY at the value(s) for which the reference's behaviour is the
              one built here, anything else raises NotImplementedError naming the key and the reference lines that implement it.
@@ -27,6 +27,8 @@ HONOURED = {
     "enableEarlyTermination", "episode_length", "cycle_motion", "trackBodies", "reset_bodies", "terminationDistance", "stateInit",
     "controlFrequencyInv", "strict_eval", "cycle_motion_xp", "fut_tracks_dropout", "add_obs_noise", "res_action",
     "occl_training", "occl_training_prob",
+    # what resample_motions hands to MotionLib.load_motions on a library built from raw motion data (humanoid_im.py:366-367)
+    "max_len", "seq_motions",
     # zero_out_far (humanoid.py:311-329)
     "zero_out_far", "zero_out_far_train", "zero_out_far_steps", "close_distance", "far_distance",
     # robot switches the env dict may carry (robot/*.yaml merged by the caller)
@@ -52,7 +54,8 @@ HONOURED = {
 }
 
 _SIM = "Isaac Gym scene / actor / asset creation (closed-source physics: out of scope, SURVEY.md section 2 #20, #36)"
-_LOAD = "consumed while motions are loaded (motion_lib_smpl / resample_motions: AMASS + smpl_sim, out of scope): the caller hands over a built MotionLib"
+_LOAD = ("consumed where the reference opens its motion file and builds the library (humanoid_im.py:320-345: joblib pickles, smpl_sim): the caller hands "
+         "over a built MotionLib -- MotionLib.from_motion_data takes the loaded data dict and min_length as arguments")
 _VIEW = "viewer / debug drawing (out of scope)"
 _DEAD = "the reference stores it in an attribute that nothing on the training path reads"
 _TEACH = "steers which PNN column trains / loads (amp_network_pnn_builder.py): PNN training is not built, the primitives come frozen from a checkpoint"
@@ -64,7 +67,7 @@ INERT = {
     "env_spacing": _SIM, "plane": _SIM, "kp_scale": _SIM, "kd_scale": _SIM, "power_scale": _SIM, "pd_control": _SIM,
     "default_humanoid_mass": _SIM, "numActions": _SIM, "numObservations": _SIM, "numStates": _SIM, "asset": _SIM,
     "enable_debug_vis": _VIEW, "show_sensors": _VIEW, "is_flag_run": _DEAD,
-    "motion_file": _LOAD, "min_length": _LOAD, "max_len": _LOAD, "seq_motions": _LOAD, "hard_negative": _LOAD,
+    "motion_file": _LOAD, "min_length": _LOAD, "hard_negative": _LOAD,
     "eval_full": _DEAD, "kin_policy": _DEAD, "partial_running_mean": _DEAD, "vae_reader": _DEAD, "z_model": _DEAD, "z_read": _DEAD,
     "z_uniform": _DEAD, "use_vae_prior_loss": _DEAD, "velocity_map": _DEAD, "tarSpeed": _DEAD,
     "training_prim": _TEACH, "actors_to_load": _TEACH,

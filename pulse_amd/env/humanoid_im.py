@@ -649,12 +649,22 @@ class HumanoidIm:
 
     def resample_motions(self):
         """HumanoidIm.resample_motions (humanoid_im.py:350-377), called by AMPAgent.pre_epoch every shape_resampling_interval epochs: the
-        reference re-draws which AMASS clips are resident (MotionLib.load_motions under the PMCP sampling weights -- AMASS loading is out of
-        scope, so a library that can reload exposes ``load_motions``; the synthetic one keeps every clip resident) and restarts every env."""
-        if hasattr(self._motion_lib, "load_motions"):
-            self._motion_lib.load_motions()
+        reference re-draws which clips are resident (MotionLib.load_motions under the PMCP sampling weights) and restarts every env.  A
+        library built from raw motion data (MotionLib.from_motion_data) does the same on the device, with ``random_sample = not seq_motions``
+        and ``max_len`` as the reference passes them (:366-367); one built from finished tables keeps every clip resident."""
+        lib = self._motion_lib
+        if hasattr(lib, "load_motions"):
+            if getattr(lib, "reloads", False):
+                env = _env_dict(self.cfg)
+                lib.load_motions(random_sample=not bool(env.get("seq_motions", False)), max_len=int(env.get("max_len", -1)))
+                if getattr(self, "_amp_motion_shape_rows", None) is not None:
+                    self._amp_motion_shape_rows = lib.motion_bodies[:, :-6]
+                if getattr(self, "_amp_motion_limb_rows", None) is not None:
+                    self._amp_motion_limb_rows = lib.motion_limb_weights
+            else:
+                lib.load_motions()
             if self._use_motion_lib:
-                self._motion_len_env = self._motion_lib.get_motion_length(self._sampled_motion_ids).contiguous()
+                self._motion_len_env = lib.get_motion_length(self._sampled_motion_ids).contiguous()
         self.reset()
 
     def _update_cycle_count(self):

@@ -4,11 +4,19 @@ What the reference does per env step (humanoid_im.py:708-735, 853-861, 950-964):
 tables (gts, grs, lrs, gvs, gavs, dvs; motion_lib_base.py:297-304) for every env, lerp / slerp them, turn the local
 rotations into exp-map dof positions and add the per-env offset -- ~60 small launches and twelve scattered gathers.
 
-Here the tables are packed ONCE at load time into one record per frame (include/pulse_hip.h section 2b:
-[gts | grs | lrs | gvs | gavs | dvs | pad], 480 floats = 1920 B for SMPL) and ``get_motion_state`` is one launch of
-``pulse_motion_state`` that reads two contiguous records per query.  Clip loading from AMASS pickles / SkeletonMotion
-construction (motion_lib_base.py:172-285, motion_lib_smpl.py) is CPU-side data preparation and stays out of scope;
-``MotionLib`` takes the finished tables (``from_tables``) -- synthetic clips here (pulse_amd/synthetic.py).
+Here the tables are packed into one record per frame (include/pulse_hip.h section 2b:
+[grs | lrs | gts | gvs | gavs | dvs | pad], 480 floats = 1920 B for SMPL) and ``get_motion_state`` is one launch of
+``pulse_motion_state`` that reads two contiguous records per query.
+
+Two ways in.  ``from_tables`` takes finished tables (pulse_amd/synthetic.py:synthetic_motion_library) and keeps every clip
+resident.  ``from_motion_data`` takes the reference's raw-data dict, key -> {pose_quat_global (F, J, 4), root_trans_offset (F, 3),
+fps, [pose_aa, beta]} (what MotionLibBase.load_data reads from its motion file, motion_lib_base.py:129-156), stages every clip on the
+device once as fp32, and ``load_motions`` (motion_lib_base.py:179-318) then draws one clip per skeleton slot from ``_sampling_prob``
+and builds the records of the drawn clips for each slot's own bone offsets with ``pulse_motion_build`` (csrc/motion_build.hip): heading
+randomisation, local rotations, forward kinematics, np.gradient + Gaussian-filtered velocities and dof velocities -- what
+MotionLibSMPL.load_motion_with_skeleton (motion_lib_smpl.py:101-174) does clip by clip with poselib in worker processes.  Out of
+scope: ``fix_trans_height`` (needs SMPL model files; the reference itself adds 0 when data/smpl is absent), reading pickles or
+directories of pickles from disk, ``real_traj`` quest data and the multi-process loader.
 
 Same names and return keys as MotionLibBase: ``get_motion_state``, ``get_root_pos_smpl``, ``get_motion_length``,
 ``get_motion_num_steps``, ``sample_motions``, ``sample_time``, ``sample_time_interval``, ``num_motions``,
@@ -16,6 +24,7 @@ Same names and return keys as MotionLibBase: ``get_motion_state``, ``get_root_po
 ``length_starts``, ``_sampling_prob``.
 """
 import ctypes
+import math
 
 import torch
 
@@ -29,6 +38,63 @@ def _stream():
 
 def _round4(n):
     return (n + 3) // 4 * 4
+
+
+# ---- host-side logic of load_data / load_motions that needs no device (pure functions)
+def filter_motion_data(data, min_length=-1, im_eval=False):
+    """MotionLibBase.load_data in file mode (motion_lib_base.py:139-149): the keys of the data set in the order the library numbers them.
+    ``min_length`` keeps the clips of at least that many frames (and then ignores ``im_eval``, as the reference's if / elif does);
+    ``im_eval`` orders them longest first (stable, like ``sorted``)."""
+    if min_length != -1:
+        return [k for k, v in data.items() if len(v["pose_quat_global"]) >= min_length]
+    if im_eval:
+        return [k for k, _ in sorted(data.items(), key=lambda entry: len(entry[1]["pose_quat_global"]), reverse=True)]
+    return list(data.keys())
+
+
+def draw_motion_ids(sampling_prob, num_slots, random_sample=True, start_idx=0, generator=None):
+    """Which clip each of ``num_slots`` skeleton slots loads (:205-208): a multinomial draw with replacement from ``sampling_prob`` (on the CPU,
+    so that a ``torch.Generator`` makes it repeatable), or the clips start_idx, start_idx + 1, ... wrapping around the data set."""
+    p = torch.as_tensor(sampling_prob).detach().cpu()
+    if random_sample:
+        return torch.multinomial(p, num_samples=num_slots, replacement=True, generator=generator)
+    return torch.remainder(torch.arange(num_slots) + start_idx, p.numel())
+
+
+def batch_sampling_prob(sampling_prob, ids):
+    """_sampling_batch_prob (:214): the data-set distribution restricted to the loaded clips, renormalised."""
+    p = sampling_prob[ids.to(sampling_prob.device)]
+    return p / p.sum()
+
+
+def crop_ranges(num_frames, max_len=-1, generator=None):
+    """(start, length) per clip as load_motion_with_skeleton crops (motion_lib_smpl.py:117-122): the whole clip when max_len is -1 or the
+    clip is shorter than max_len, otherwise max_len frames from a start drawn uniformly in [0, frames - max_len]."""
+    n = torch.as_tensor(num_frames, dtype=torch.int64)
+    if max_len == -1:
+        return torch.zeros_like(n), n.clone()
+    room = (n - max_len).clamp(min=0)
+    u = torch.rand(n.shape, dtype=torch.float64, generator=generator)
+    start = torch.minimum((u * (room + 1).double()).long(), room)
+    return start, torch.where(n < max_len, n, torch.full_like(n, max_len))
+
+
+def _parse_skeleton_trees(skeleton_trees):
+    """(parents list, local_translation (M, J, 3) float32 CPU) from one (parents, (M, J, 3)) pair or a sequence of objects that carry
+    ``parent_indices`` and ``local_translation`` (poselib's SkeletonTree does; nothing of poselib is imported)."""
+    if isinstance(skeleton_trees, tuple) and len(skeleton_trees) == 2 and not hasattr(skeleton_trees[0], "parent_indices"):
+        parents, lt = skeleton_trees
+        lt = torch.as_tensor(lt, dtype=torch.float32)
+    else:
+        parents = skeleton_trees[0].parent_indices
+        lt = torch.stack([torch.as_tensor(t.local_translation, dtype=torch.float32) for t in skeleton_trees])
+        for t in skeleton_trees:
+            if [int(p) for p in t.parent_indices] != [int(p) for p in parents]:
+                raise ValueError("skeleton_trees: every slot must have the same parent_indices (body shape changes the bone offsets only)")
+    parents = [int(p) for p in parents]
+    if lt.dim() != 3 or tuple(lt.shape[1:]) != (len(parents), 3):
+        raise ValueError(f"skeleton_trees: local_translation (M, {len(parents)}, 3) expected, got {tuple(lt.shape)}")
+    return parents, lt.contiguous()
 
 
 class MotionLib:
@@ -86,6 +152,8 @@ class MotionLib:
         # AMP frames of reference motion carry them under has_shape_obs_disc / has_weight_obs_disc (humanoid_amp.py:243-250, 548-555)
         self.motion_bodies = self._shape_rows(tables, "motion_bodies", 17)
         self.motion_limb_weights = self._shape_rows(tables, "motion_limb_weights", 10)
+        self._src = None                                   # staged raw clips: only a library built by from_motion_data reloads
+        self._generation = 0
 
     def _shape_rows(self, tables, key, width):
         t = tables.get(key)
@@ -99,6 +167,54 @@ class MotionLib:
     def from_tables(cls, tables, device="cuda:0"):
         return cls(tables, device)
 
+    @classmethod
+    def from_motion_data(cls, data, skeleton_trees, gender_betas=None, limb_weights=None, device="cuda:0", min_length=-1, im_eval=False,
+                         generator=None):
+        """A library over the reference's raw-data dict (module docstring).  ``skeleton_trees``: one tree per resident slot (env), or one
+        (parents, local_translation (M, J, 3)) pair.  ``generator``: the CPU torch.Generator every draw of this library comes from (which
+        clips load, heading angles, crop starts).  Ends with a first ``load_motions``."""
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("MotionLib lives in HBM (pulse_amd has no CPU path)")
+        self = cls.__new__(cls)
+        self._device = dev
+        keys = filter_motion_data(data, min_length, im_eval)
+        if not keys:
+            raise ValueError("from_motion_data: no clip left" + (f" with at least {min_length} frames" if min_length != -1 else ""))
+        self._motion_data_keys = keys
+        self._num_unique_motions = len(keys)
+        rot = [torch.as_tensor(data[k]["pose_quat_global"]) for k in keys]
+        j = rot[0].shape[1]
+        for k, r in zip(keys, rot):
+            t = torch.as_tensor(data[k]["root_trans_offset"])
+            if r.dim() != 3 or tuple(r.shape[1:]) != (j, 4) or tuple(t.shape) != (r.shape[0], 3):
+                raise ValueError(f"clip {k!r}: pose_quat_global (F, {j}, 4) and root_trans_offset (F, 3) expected, got {tuple(r.shape)} and {tuple(t.shape)}")
+            if r.shape[0] < 2:
+                raise ValueError(f"clip {k!r} has {r.shape[0]} frame(s): at least 2 are needed (np.gradient raises below 2)")
+        frames = torch.tensor([r.shape[0] for r in rot], dtype=torch.int64)
+        self._src = {
+            "rot": torch.cat([r.to(torch.float32) for r in rot]).contiguous().to(dev),
+            "trans": torch.cat([torch.as_tensor(data[k]["root_trans_offset"]).to(torch.float32) for k in keys]).contiguous().to(dev),
+            "start": torch.cumsum(frames, 0) - frames, "frames": frames,
+            "fps": torch.tensor([float(data[k].get("fps", 30)) for k in keys], dtype=torch.float64),             # curr_file.get("fps", 30), motion_lib_smpl.py:150
+            "has_beta": torch.tensor(["beta" in data[k] for k in keys]),
+        }
+        self.num_bodies, self.num_dof = j, (j - 1) * 3
+        self.offsets, self.frame_stride, _ = self.record_layout(j)
+        self._im_eval, self._generator = bool(im_eval), generator
+        self._sampling_prob = torch.ones(self._num_unique_motions, device=dev) / self._num_unique_motions       # setup_constants, :162-168
+        self._termination_history = torch.zeros(self._num_unique_motions, device=dev)
+        self._curr_motion_ids = None
+        self._generation = 0
+        self._last_load = {"skeleton_trees": None, "gender_betas": None, "limb_weights": None}
+        self.load_motions(skeleton_trees, gender_betas, limb_weights)
+        return self
+
+    @property
+    def reloads(self):
+        """True for a library built from raw data: ``load_motions`` re-draws which clips are resident and rebuilds the records."""
+        return self._src is not None
+
     # ---- table views (reference attribute names), strided views into the packed records
     def _field(self, k, inner):
         j = self.num_bodies if k != "dvs" else self.num_bodies - 1
@@ -110,6 +226,14 @@ class MotionLib:
     gvs = property(lambda self: self._field("gvs", 3))
     gavs = property(lambda self: self._field("gavs", 3))
     dvs = property(lambda self: self._field("dvs", 3))
+
+    def tables(self):
+        """The library's tables in the reference's layout (motion_lib_base.py:287-316), copied to the CPU: what ``from_tables`` takes."""
+        c = lambda x: x.detach().cpu().contiguous()
+        out = {k: c(getattr(self, k)) for k in self.FIELDS}
+        out.update({"motion_lengths": c(self._motion_lengths), "motion_fps": c(self._motion_fps), "motion_dt": c(self._motion_dt),
+                    "motion_num_frames": c(self._motion_num_frames), "length_starts": c(self.length_starts)})
+        return out
 
     # ---- bookkeeping queries (motion_lib_base.py:325-432)
     def num_motions(self):
@@ -158,10 +282,59 @@ class MotionLib:
             return True
         return False
 
-    def load_motions(self):
-        """The part of MotionLibBase.load_motions (:172-285) that survives when every clip is resident: the batch distribution is the
-        data-set distribution restricted to the loaded clips and renormalised (:221-222)."""
-        self._sampling_batch_prob = self._sampling_prob / self._sampling_prob.sum()
+    def load_motions(self, skeleton_trees=None, gender_betas=None, limb_weights=None, random_sample=True, start_idx=0, max_len=-1):
+        """MotionLibBase.load_motions (:179-318).  A library built from tables keeps every clip resident: what survives there is the batch
+        distribution, the data-set distribution restricted to the loaded clips and renormalised (:214).  A library built from raw data
+        (``from_motion_data``) draws one clip per skeleton slot and rebuilds the records for the slot's own skeleton on the device;
+        arguments left None reuse the ones last given."""
+        if self._src is None:
+            if skeleton_trees is not None or gender_betas is not None or limb_weights is not None or not random_sample or start_idx != 0 or max_len != -1:
+                raise ValueError("load_motions: this library was built from finished tables, every clip stays resident (from_motion_data builds one that reloads)")
+            self._sampling_batch_prob = self._sampling_prob / self._sampling_prob.sum()
+            return
+        from .. import kernels
+        dev, src, last = self._device, self._src, self._last_load
+        for name, value in (("skeleton_trees", skeleton_trees), ("gender_betas", gender_betas), ("limb_weights", limb_weights)):
+            if value is not None:
+                last[name] = value
+        if last["skeleton_trees"] is None:
+            raise ValueError("load_motions: skeleton_trees are needed once")
+        parents, lt = _parse_skeleton_trees(last["skeleton_trees"])
+        m = lt.shape[0]
+        if len(parents) != self.num_bodies:
+            raise ValueError(f"skeleton_trees have {len(parents)} bodies, the motion data {self.num_bodies}")
+        ids = draw_motion_ids(self._sampling_prob, m, random_sample, start_idx, self._generator)
+        self._curr_motion_ids = ids.to(dev)
+        self.curr_motion_keys = [self._motion_data_keys[i] for i in ids.tolist()]
+        self._sampling_batch_prob = batch_sampling_prob(self._sampling_prob, self._curr_motion_ids)
+        crop_start, num_frames = crop_ranges(src["frames"][ids], max_len, self._generator)
+        fps = src["fps"][ids]
+        dt = 1.0 / fps                                                                                    # python doubles in the reference, rounded once (:287-292)
+        self._motion_fps, self._motion_dt = fps.float().to(dev), dt.float().to(dev)
+        self._motion_lengths = (dt * (num_frames - 1).double()).float().to(dev)                           # curr_len, :263
+        self._motion_num_frames = num_frames.to(dev)
+        out_start = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(num_frames, 0)])
+        self.length_starts = out_start[:-1].to(dev).contiguous()                                          # :311-314
+        self._num_motions = m
+        self.motion_ids = torch.arange(m, dtype=torch.long, device=dev)
+        self._lengths_host = None
+        has_beta = src["has_beta"][ids]
+        betas = torch.zeros(m, 17) if last["gender_betas"] is None else torch.as_tensor(last["gender_betas"], dtype=torch.float32).reshape(m, 17).cpu()
+        self.motion_bodies = torch.where(has_beta[:, None], betas, torch.zeros(m, 17)).to(dev).contiguous()      # :266-271
+        lw = last["limb_weights"]
+        self.motion_limb_weights = None if lw is None else torch.as_tensor(lw, dtype=torch.float32).reshape(m, -1).to(dev).contiguous()   # :294
+        heading = None
+        if not self._im_eval:                                                                              # motion_lib_smpl.py:131-140
+            heading = (math.pi * (2.0 * torch.rand(m, dtype=torch.float64, generator=self._generator) - 1.0)).float().to(dev)
+        self.motion_heading = heading
+        total = int(out_start[-1])
+        frames = torch.empty(total, self.frame_stride, dtype=torch.float32, device=dev)                  # every column is written by the kernels
+        kernels.motion_build(frames, self.offsets, src_rot=src["rot"], src_trans=src["trans"], clip_src_start=src["start"][ids].to(dev),
+                             clip_crop_start=crop_start.to(dev) if max_len != -1 else None, clip_out_start=out_start.to(dev),
+                             clip_frames=num_frames.contiguous(), clip_dt=self._motion_dt, local_translation=lt.to(dev), parents=parents,
+                             clip_heading=heading)
+        self.frames = frames
+        self._generation += 1
 
     def sample_motions(self, n, generator=None):
         return torch.multinomial(self._sampling_batch_prob, num_samples=n, replacement=True, generator=generator).to(self._device)
@@ -187,7 +360,7 @@ class MotionLib:
     def launch_signature(self):
         """Identity of the device tables a cached launch points at (ops._launch_sig)."""
         return (id(self), self.frames.data_ptr(), tuple(self.frames.shape), self._motion_lengths.data_ptr(), self._motion_dt.data_ptr(),
-                self._motion_num_frames.data_ptr(), self.length_starts.data_ptr(), self._num_motions)
+                self._motion_num_frames.data_ptr(), self.length_starts.data_ptr(), self._num_motions, self._generation)
 
     def fill_tables(self, t):
         """Fill a pulse_motion_tables struct (by reference) with this library's device pointers."""

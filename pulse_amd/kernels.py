@@ -380,6 +380,54 @@ def mcp_head_backward(dmu, dz, *, rows, num_prim, mu=None, aux=None, activation=
 
 
 # --------------------------------------------------------------------------- #
+# reference-motion records from raw clips (include/pulse_hip.h section 2b')
+# --------------------------------------------------------------------------- #
+def gaussian_weights(sigma=2.0, radius=8):
+    """The weights scipy's gaussian_filter1d uses (scipy.ndimage._filters._gaussian_kernel1d, order 0), in double: |tap| = 0 .. radius."""
+    import numpy as np
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return [float(v) for v in phi[radius:]]
+
+
+def motion_build(frames, offsets, *, src_rot, src_trans, clip_src_start, clip_out_start, clip_frames, clip_dt, local_translation, parents,
+                 clip_heading=None, clip_crop_start=None):
+    """pulse_motion_build: fill ``frames`` (total, frame_stride), the packed records of ``MotionLib.record_layout``, from staged raw clips.
+    Device tensors: ``src_rot`` (S, J, 4) / ``src_trans`` (S, 3) fp32, ``clip_src_start`` (M) / ``clip_out_start`` (M + 1) /
+    ``clip_crop_start`` (M, optional) int64, ``clip_dt`` (M) / ``clip_heading`` (M, optional) / ``local_translation`` (M, J, 3) fp32.
+    Host: ``clip_frames`` (M) int64 CPU tensor (validated by the launcher), ``parents`` a sequence of J ints."""
+    a = _lib.MotionBuildArgs()
+    for name, t, dt in (("src_rot", src_rot, torch.float32), ("src_trans", src_trans, torch.float32), ("clip_src_start", clip_src_start, torch.int64),
+                        ("clip_crop_start", clip_crop_start, torch.int64), ("clip_out_start", clip_out_start, torch.int64), ("clip_dt", clip_dt, torch.float32),
+                        ("clip_heading", clip_heading, torch.float32), ("local_translation", local_translation, torch.float32), ("frames", frames, torch.float32)):
+        ptr = _chk(t, name, dt)
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name}: contiguous tensor expected, got strides {tuple(t.stride())}")
+        setattr(a, name, ptr)
+    if not isinstance(clip_frames, torch.Tensor) or clip_frames.device.type != "cpu" or clip_frames.dtype != torch.int64 or not clip_frames.is_contiguous():
+        raise TypeError("clip_frames: contiguous int64 CPU tensor expected (the launcher validates the frame counts on the host)")
+    m, j = clip_frames.numel(), len(parents)
+    if src_rot.dim() != 3 or tuple(src_rot.shape[1:]) != (j, 4) or tuple(src_trans.shape) != (src_rot.shape[0], 3):
+        raise ValueError(f"src_rot / src_trans: expected (S, {j}, 4) and (S, 3), got {tuple(src_rot.shape)} and {tuple(src_trans.shape)}")
+    for name, t, shape in (("clip_src_start", clip_src_start, (m,)), ("clip_crop_start", clip_crop_start, (m,)), ("clip_out_start", clip_out_start, (m + 1,)),
+                           ("clip_dt", clip_dt, (m,)), ("clip_heading", clip_heading, (m,)), ("local_translation", local_translation, (m, j, 3))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+    if frames.dim() != 2:
+        raise ValueError(f"frames: expected (total_frames, frame_stride), got {tuple(frames.shape)}")
+    par = (ctypes.c_int32 * j)(*[int(p) for p in parents])
+    a.src_frames, a.num_clips, a.num_bodies = src_rot.shape[0], m, j
+    a.clip_frames_host, a.parent_indices_host = clip_frames.data_ptr(), ctypes.cast(par, ctypes.c_void_p)
+    a.total_frames, a.frame_stride = frames.shape[0], frames.shape[1]
+    a.off_gts, a.off_grs, a.off_lrs = offsets["gts"], offsets["grs"], offsets["lrs"]
+    a.off_gvs, a.off_gavs, a.off_dvs = offsets["gvs"], offsets["gavs"], offsets["dvs"]
+    a.filter_w[:] = gaussian_weights()
+    _lib.check(_lib.load().pulse_motion_build(ctypes.byref(a), _stream()), "pulse_motion_build")
+    return frames
+
+
+# --------------------------------------------------------------------------- #
 # planar ("x3p") fp32-grade GEMM: operands kept pre-split in HBM as three bf16 planes (include/pulse_hip.h section 4b)
 # --------------------------------------------------------------------------- #
 def planes_pitch(cols):

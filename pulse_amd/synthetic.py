@@ -278,6 +278,49 @@ def synthetic_motion_library(g, num_motions, min_frames=45, max_frames=180, fps=
     return tables
 
 
+def synthetic_motion_data(g, num_clips, humanoid="smpl", frames=None, min_frames=45, max_frames=180, fps=30, num_slots=None):
+    """Raw motion data as the reference's motion file holds it (MotionLibBase.load_data, motion_lib_base.py:129-156), and skeleton trees to load it
+    with: ``(data, (parents, local_translation (num_slots, J, 3)))``.  ``data``: key -> {pose_quat_global (F, J, 4) float32 numpy, root_trans_offset
+    (F, 3) float32 tensor, pose_aa (F, J * 3), fps, [beta (10)]}: smooth random articulated clips (the joint trajectories of
+    ``synthetic_motion_library``), every second clip marked with ``beta``.  ``frames``: the clips' lengths (default: drawn in
+    [min_frames, max_frames]); ``fps``: one value or one per clip.  ``num_slots`` skeletons (default num_clips) share the parents and differ in
+    their bone offsets, as bodies of different shape do.  For ``MotionLib.from_motion_data``."""
+    sk = skeleton(humanoid)
+    parents = sk["parents"]
+    m, j = num_clips, len(parents)
+    num_frames = torch.randint(min_frames, max_frames + 1, (m,), generator=g, dtype=torch.int64) if frames is None else torch.as_tensor(frames, dtype=torch.int64)
+    fps_list = [fps] * m if not isinstance(fps, (list, tuple)) else list(fps)
+    if num_frames.numel() != m or len(fps_list) != m:
+        raise ValueError(f"synthetic_motion_data: {m} clips need {m} lengths and fps values")
+    data = {}
+    for c in range(m):
+        f = int(num_frames[c])
+        t = (torch.arange(f, dtype=torch.float32) / float(fps_list[c]))[:, None, None]
+        amp = 0.35 * _rand(g, j, 3, 2)
+        amp[0] *= 0.3
+        frq = 0.3 + 1.7 * _rand(g, j, 3, 2)
+        pha = 6.2831853 * _rand(g, j, 3, 2)
+        e = (amp * torch.sin(6.2831853 * frq * t[..., None] + pha)).sum(-1)                     # (F, J, 3) joint exp maps
+        e[:, 0, 2] += 6.2831853 * _rand(g, 1) + 0.8 * _randn(g, 1) * t[:, 0, 0]
+        lrs = _exp_map_to_quat_xyzw(e)
+        lrs = lrs / lrs.norm(dim=-1, keepdim=True)
+        grs = torch.empty(f, j, 4)
+        for b in range(j):
+            grs[:, b] = lrs[:, b] if parents[b] < 0 else _quat_mul_xyzw(grs[:, parents[b]], lrs[:, b])
+        grs = grs / grs.norm(dim=-1, keepdim=True)
+        root = (0.6 * _randn(g, 3) * torch.tensor([1.0, 1.0, 0.0])) * t[:, 0] + 0.05 * _randn(g, 3) * torch.sin(3.0 * t[:, 0]) + torch.tensor([0.0, 0.0, 0.9])
+        clip = {"pose_quat_global": grs.contiguous().numpy(), "root_trans_offset": root.contiguous(), "pose_aa": e.reshape(f, j * 3).contiguous().numpy(),
+                "fps": fps_list[c]}
+        if c % 2 == 0:
+            clip["beta"] = _randn(g, 10).numpy()
+        data[f"clip_{c:04d}"] = clip
+    slots = m if num_slots is None else num_slots
+    offsets = 0.08 + 0.3 * _rand(g, j, 3) * torch.tensor([0.4, 0.4, 1.0])
+    lt = offsets[None] * (1.0 + 0.1 * _randn(g, slots, 1, 1))
+    lt[:, 0] = 0.0
+    return data, (list(parents), lt.contiguous())
+
+
 # --------------------------------------------------------------------------- #
 # Action-dependent physics stand-in (return-parity experiments): constants shared by the HIP kernel's host class
 # (pulse_amd/env/sim.py:PdSim) and its CPU twin (oracle/pd_sim_oracle.py).  See include/pulse_hip.h: pulse_pd_sim_args.

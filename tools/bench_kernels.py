@@ -1,6 +1,9 @@
 """Per-kernel roofline of the HBM / latency-bound kernels at cfg2 sizes (dev tool; the official bench is bench.py).
 Each kernel is timed in isolation with HIP events on the launch stream; algorithmic bytes per launch are the ones DESIGN.md
-section 3 states.  Prints a markdown table (achieved GB/s vs the 8 TB/s HBM3E spec peak)."""
+section 3 states.  Prints a markdown table (achieved GB/s vs the 8 TB/s HBM3E spec peak).
+
+    python tools/bench_kernels.py                 every row
+    python tools/bench_kernels.py motion_build    only the motion-table reload rows (2048 clips at 24 and at 52 bodies)"""
 import os
 import sys
 
@@ -33,6 +36,40 @@ rows = []
 def report(name, nbytes, t, unit_desc):
     rows.append(f"| `{name}` | {unit_desc} | {nbytes / 1e6:.2f} | {t * 1e6:.1f} | {nbytes / t / 1e9:.0f} | {nbytes / t / PEAK:.3f} |")
 
+
+def motion_build_rows(humanoid, clips=2048):
+    """A reload of ``clips`` resident clips (45 .. 180 frames each) out of as many unique ones: the two kernels of pulse_motion_build alone, and
+    MotionLib.load_motions whole (draws, per-clip scalars, the upload of the clip tables, allocation, the kernels; synchronised).  Algorithmic
+    bytes: the staged rotations and translations of every resident frame and the bone offsets read once, 4 x frame_stride bytes written per frame."""
+    from pulse_amd import synthetic as syn
+    from pulse_amd.env.motion_lib import MotionLib
+    g = syn.make_generator(3)
+    data, trees = syn.synthetic_motion_data(g, clips, humanoid=humanoid, num_slots=clips)
+    lib = MotionLib.from_motion_data(data, trees, device=dev, generator=g)
+    j, total = lib.num_bodies, lib.frames.shape[0]
+    seen, inner = {}, K.motion_build
+    K.motion_build = lambda frames, offsets, **kw: (seen.update(frames=frames, offsets=offsets, kw=kw), inner(frames, offsets, **kw))[1]
+    lib.load_motions()
+    K.motion_build = inner
+    total = seen["frames"].shape[0]
+    nbytes = total * (j * 16 + 12) + clips * j * 12 + total * lib.frame_stride * 4
+    t = timeit(lambda: inner(seen["frames"], seen["offsets"], **seen["kw"]), iters=20, warm=3)
+    report(f"motion_build kernels ({humanoid}, {j} bodies)", nbytes, t, f"{clips} clips, {total} frames")
+
+    def reload():
+        lib.load_motions()
+        torch.cuda.synchronize()
+    t = timeit(reload, iters=10, warm=2)
+    report(f"MotionLib.load_motions, whole reload ({humanoid}, {j} bodies; host side included)", nbytes, t, f"{clips} clips, ~{total} frames")
+
+
+if sys.argv[1:] == ["motion_build"]:
+    for h in ("smpl", "smplx"):
+        motion_build_rows(h)
+    print("| kernel | units per launch | algorithmic MB per launch | us per launch | GB/s | frac of 8 TB/s |")
+    print("|---|---|---|---|---|---|")
+    print("\n".join(rows))
+    sys.exit(0)
 
 agent, _ = configs.make_agent("cfg2", device=dev, seed=1, reference="motion_lib")
 agent.init_tensors()
@@ -185,6 +222,8 @@ def humanoid_rows(humanoid, n_env=4096):
 
 
 h24, h52 = humanoid_rows("smpl"), humanoid_rows("smplx")
+for h in ("smpl", "smplx"):
+    motion_build_rows(h)
 for k in h24:
     rows.append(f"| SMPL-X / SMPL `{k}` | time ratio {h52[k][0] / h24[k][0]:.2f} | byte ratio {h52[k][1] / h24[k][1]:.2f} | | | |")
 # ---- round 3: terrain / trajectory step (height-map gather), PULSE VAE head kernels, downstream-task step
