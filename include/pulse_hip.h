@@ -36,7 +36,7 @@ extern "C" {
 #define PULSE_ERR_LAUNCH (-2)
 #define PULSE_ERR_UNSUPPORTED (-3)
 
-#define PULSE_ABI_VERSION 33
+#define PULSE_ABI_VERSION 34
 
 typedef void* pulse_stream_t; /* hipStream_t */
 
@@ -444,6 +444,44 @@ typedef struct pulse_motion_build_args {
 } pulse_motion_build_args;
 int pulse_sizeof_motion_build_args(void);
 int pulse_motion_build(const pulse_motion_build_args* args, pulse_stream_t s);
+
+/* ------------------------------------------------------------------------- *
+ * 2b''. Evaluation metrics, accumulated per control step of an evaluation batch (IMAmpAgent.eval,
+ *      phc/learning/im_amp.py:136-363).  The reference copies every env's body positions to the host on every step
+ *      (HumanoidIm.post_physics_step under flags.im_eval, phc/env/tasks/humanoid_im.py:667-673), slices them per motion to
+ *      its first num_steps - 1 frames (im_amp.py:283-287) and hands them to smpl_sim's compute_metrics_lite (:314-341).
+ *      Here one launch per step adds the step's five terms to a per-env accumulator row; nothing leaves the device.
+ *      Step ``step`` (0-based index inside the batch) counts for env e while step < num_steps[e] - 1.  With P, G the
+ *      simulated / reference positions (J, 3) of the step, in mm (factor 1000), fp64 arithmetic on the fp32 inputs:
+ *        accum[0] += mean_j |P_j - G_j|                                              mpjpe_g
+ *        accum[1] += the same after subtracting body 0 from each                     mpjpe_l
+ *        accum[2] += mean_j |a P~_j R + t - G~_j|                                    mpjpe_pa: P~, G~ root-relative, (a, R, t) the similarity
+ *                    Procrustes fit of the common p_mpjpe with X = G~ (target), Y = P~ (predicted): centre both, divide each by its
+ *                    Frobenius norm, H = X0^T Y0 = U S V^T, R = V U^T (last column of V and last singular value flipped when
+ *                    det R < 0), a = tr(S) |X| / |Y|, t = mu_X - a mu_Y R.  The SVD is a fixed-sweep one-sided Jacobi.
+ *        accum[3] += mean_j |(P_t - P_t-1) - (G_t - G_t-1)|                          vel_dist, steps >= 1
+ *        accum[4] += mean_j |(P_t - 2 P_t-1 + P_t-2) - (G_t - 2 G_t-1 + G_t-2)|      accel_dist, steps >= 2
+ *        accum[5], [6], [7] += 1                                                     frames counted for [0..2], [3], [4]
+ *      The ring holds the positions of the previous two launches and is rewritten by every launch (counted or not); it needs
+ *      no initialisation.  The caller zeroes ``accum`` at the start of a batch.  One lane group per env, lane = body (32 lanes
+ *      up to 32 bodies, 64 above); per-env sums are butterfly shuffles, no atomics.
+ * ------------------------------------------------------------------------- */
+typedef struct pulse_im_eval_args {
+    const float* rb;               /* simulated rigid-body records, env e at rb + e * rb_env_stride: (J, 13), positions in columns 0:3 */
+    int64_t rb_env_stride;         /* floats, >= 13 J */
+    const float* ref_pos;          /* reference body positions of the step, env e at ref_pos + e * ref_env_stride: (J, 3) */
+    int64_t ref_env_stride;        /* floats, >= 3 J */
+    int32_t num_envs;
+    int32_t num_bodies;            /* J in [1, 64] */
+    const int32_t* num_steps;      /* (N) MotionLibBase.get_motion_num_steps of the clip each env plays */
+    int32_t step;                  /* index of this control step inside the batch, from 0 */
+    const uint8_t* env_mask;       /* optional (N): envs whose byte is 0 are skipped entirely (ring and accumulator untouched) */
+    float* ring;                   /* (N, 2, 2, J, 3): [slot = step & 1][pred | gt] */
+    double* accum;                 /* env e at accum + e * accum_stride: 8 doubles, 8-byte aligned */
+    int64_t accum_stride;          /* doubles, >= 8 */
+} pulse_im_eval_args;
+int pulse_sizeof_im_eval_args(void);
+int pulse_im_eval_accum(const pulse_im_eval_args* args, pulse_stream_t s);
 
 /* ------------------------------------------------------------------------- *
  * 2c. Per-step rollout bookkeeping of play_steps (phc/learning/amp_agent.py:372-412,

@@ -12,7 +12,7 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int6
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PULSE_HIP_LIB: another build of the SAME library (tools/im_step_repro.py compares compile variants); default = the in-tree build
 LIB_PATH = os.environ.get("PULSE_HIP_LIB") or os.path.join(_HERE, "csrc", "libpulse_hip.so")
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 PULSE_IM_SELF_OBS = 1
 PULSE_IM_TASK_OBS = 2
@@ -47,6 +47,12 @@ class MotionBuildArgs(Structure):
                 ("frames", c_void_p), ("total_frames", c_int64), ("frame_stride", c_int64),
                 ("off_gts", c_int32), ("off_grs", c_int32), ("off_lrs", c_int32), ("off_gvs", c_int32), ("off_gavs", c_int32), ("off_dvs", c_int32),
                 ("filter_w", c_float * 9)]
+
+
+class ImEvalArgs(Structure):
+    _fields_ = [("rb", c_void_p), ("rb_env_stride", c_int64), ("ref_pos", c_void_p), ("ref_env_stride", c_int64), ("num_envs", c_int32),
+                ("num_bodies", c_int32), ("num_steps", c_void_p), ("step", c_int32), ("env_mask", c_void_p), ("ring", c_void_p),
+                ("accum", c_void_p), ("accum_stride", c_int64)]
 
 
 class ImStepArgs(Structure):
@@ -299,6 +305,8 @@ SIGNATURES = {
     "pulse_motion_state": (c_int, [POINTER(MotionStateArgs), P]),
     "pulse_sizeof_motion_build_args": (c_int, []),
     "pulse_motion_build": (c_int, [POINTER(MotionBuildArgs), P]),
+    "pulse_sizeof_im_eval_args": (c_int, []),
+    "pulse_im_eval_accum": (c_int, [POINTER(ImEvalArgs), P]),
     "pulse_gae": (c_int, [P, P, P, P, c_int32, c_int32, c_int64, c_int64, c_float, c_float, P, P, P]),
     "pulse_sizeof_gemm_desc": (c_int, []),
     "pulse_gemm_f32": (c_int, [POINTER(GemmDesc), P]),

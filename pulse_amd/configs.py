@@ -153,12 +153,13 @@ def agent_config(name, **overrides):
     return cfg, c["num_envs"]
 
 
-def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kind="im", reference="recorded", env_overrides=None, humanoid="smpl"):
+def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kind="im", reference="recorded", env_overrides=None, humanoid="smpl",
+             num_clips=None):
     """``humanoid``: 'smpl' (24 bodies) | 'smplx' / 'smplh' (52 bodies) -- the robot config handed to the task as cfg.robot.
     ``reference``: 'recorded' = pre-recorded rigid-body / reference frames (RecordedRollout, what the CPU oracle agent replays);
     'motion_lib' = reference motion queried from the HBM-resident MotionLib every step, physics stand-in tracking it;
     'motion_data' = the same, with the library built on the device from synthetic RAW clips (MotionLib.from_motion_data: one resident clip per
-    env out of min(num_envs, 1024) / 2 + 1 unique ones, re-drawn by resample_motions)."""
+    env out of ``num_clips`` unique ones -- min(num_envs, 1024) / 2 + 1 unless given -- re-drawn by resample_motions)."""
     from .env.humanoid_im import HumanoidIm, VecTaskPythonWrapper, check_humanoid_options
     if humanoid not in ROBOTS:
         raise NotImplementedError(f"humanoid {humanoid!r}: 'smpl', 'smplh' and 'smplx' are built")
@@ -215,7 +216,8 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
         disc_rows = any(bool(dict(robot if humanoid != "smpl" else {}, **env_cfg).get(k, False)) for k in ("has_shape_obs_disc", "has_weight_obs_disc"))
         if reference == "motion_data":
             g = syn.make_generator(seed + 5, rank)
-            data, trees = syn.synthetic_motion_data(g, min(num_envs, 1024) // 2 + 1, humanoid=humanoid, num_slots=num_envs)
+            data, trees = syn.synthetic_motion_data(g, min(num_envs, 1024) // 2 + 1 if num_clips is None else int(num_clips), humanoid=humanoid,
+                                                    num_slots=num_envs)
             bodies, limb = syn.motion_shape_rows(syn.make_generator(7117), num_envs)
             motion = MotionLib.from_motion_data(data, trees, gender_betas=bodies, limb_weights=limb, device=device, generator=g)
         else:

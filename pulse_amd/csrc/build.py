@@ -39,6 +39,7 @@ SOURCES = [
     ("traj_step.hip", NO_CONTRACT),
     ("motion_state.hip", NO_CONTRACT),
     ("motion_build.hip", NO_CONTRACT),
+    ("eval_metrics.hip", NO_CONTRACT),
     ("rollout_ops.hip", NO_CONTRACT),
     ("gae.hip", NO_CONTRACT),
     # MFMA accumulators in VGPR form: no v_accvgpr moves (VALU slots are what the fp32 MFMA loop is short of) and the

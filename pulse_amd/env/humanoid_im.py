@@ -26,6 +26,7 @@ kernel advances the episode clock, tests pass_time and blends its t / t+1 refere
 samples future reference frames -- HumanoidIm.{_compute_task_obs, _compute_reward, _compute_reset, _reset_ref_state_init,
 _sample_time} (humanoid_im.py:652-654, 708-919, 920-926, 1119-1192) in three launches per control step.
 """
+import contextlib
 import os
 
 import torch
@@ -88,6 +89,13 @@ def check_humanoid_options(cfg, task="HumanoidIm"):
     return ht
 
 
+def eval_body_names(body_names, humanoid_type="smpl"):
+    """Humanoid._eval_bodies (humanoid.py:381-388): every body but the toes, and but the hands for ``smpl`` (following UHC: hands and toes
+    have no reliable data).  Needs no device."""
+    drop = {"L_Toe", "R_Toe"} | ({"L_Hand", "R_Hand"} if humanoid_type == "smpl" else set())
+    return [b for b in body_names if b not in drop]
+
+
 def check_amp_options(env, motion_lib=None):
     """The AMP frame's variant switches of an env dict (robot switches merged in): amp_obs_v (humanoid.py:292; humanoid_amp.py:300-303, 670-675),
     has_shape_obs_disc / has_weight_obs_disc (humanoid.py:267-269).  Returns amp_obs_v; raises by name for what cannot be built.  Needs no
@@ -124,6 +132,12 @@ class HumanoidIm:
         self.cfg = cfg
         self.device = torch.device(device)
         self.sim, self._motion_lib = sim, motion_lib
+        # humanoid_im.py:337-341: the evaluation library covers the training library's clips under im_eval (longest first, no heading draw)
+        # and shares its staged buffers; a library that cannot reload (finished tables, recorded frames) evaluates on itself
+        self._motion_train_lib = motion_lib
+        self._motion_eval_lib = motion_lib.eval_twin() if hasattr(motion_lib, "eval_twin") else motion_lib
+        self.start_idx = 0
+        self._eval_state = None                                                 # set inside evaluation_mode()
         self.num_envs = sim.num_envs
         if "num_envs" in env and int(env["num_envs"]) != self.num_envs:
             raise ValueError(f"env.num_envs = {env['num_envs']} but the injected simulator has {self.num_envs} envs")
@@ -209,6 +223,9 @@ class HumanoidIm:
         reset = env.get("reset_bodies", sk["reset_bodies"])
         self._track_bodies_id = torch.tensor([names.index(b) for b in track], dtype=torch.int32, device=self.device)
         self._reset_bodies_id = torch.tensor([names.index(b) for b in reset], dtype=torch.int32, device=self.device)
+        # Humanoid._eval_bodies (humanoid.py:381-388): what evaluation resets on when the task resets on more than 15 bodies (im_amp.py:180-181)
+        self._eval_track_bodies_id = torch.tensor([names.index(b) for b in eval_body_names(names, self.humanoid_type)], dtype=torch.int32,
+                                                  device=self.device)
         self._termination_distances = torch.full((self.num_bodies,), float(env.get("terminationDistance", 0.25)), device=self.device)
         self._dof_size = sk["num_dof"]
         self._pd_action_offset = torch.zeros(self._dof_size, device=self.device)
@@ -667,6 +684,103 @@ class HumanoidIm:
                 self._motion_len_env = lib.get_motion_length(self._sampled_motion_ids).contiguous()
         self.reset()
 
+    # ------------------------------------------------------------------ evaluation sweep (humanoid_im.py:439-447, 667-673; im_amp.py:160-182, 223-234)
+    def begin_seq_motion_samples(self):
+        self.start_idx = 0
+        self._load_seq_motions()
+
+    def forward_motion_samples(self):
+        self.start_idx += self.num_envs
+        self._load_seq_motions()
+
+    def _load_seq_motions(self):
+        """load_motions(random_sample=False, start_idx=self.start_idx) and a reset of every env: slot e plays clip (start_idx + e) modulo the data
+        set.  A library that keeps every clip resident moves the envs over its clips instead."""
+        if not self._use_motion_lib:
+            raise NotImplementedError("the sequential sweep over the data set needs the MotionLib reference source")
+        lib = self._motion_lib
+        slots = torch.arange(self.num_envs, dtype=torch.int64, device=self.device)
+        if getattr(lib, "reloads", False):
+            lib.load_motions(random_sample=False, start_idx=self.start_idx)
+            self._sampled_motion_ids.copy_(slots % lib.num_motions())
+        else:
+            self._sampled_motion_ids.copy_((slots + self.start_idx) % lib.num_motions())
+        self._refresh_motion_rows()
+        if self._eval_state is not None:
+            self._eval_state["step"] = 0
+            self._eval_state["num_steps"] = lib.get_motion_num_steps(self._sampled_motion_ids).contiguous()
+            self._eval_state["accum"].zero_()
+        self.reset()
+
+    def _refresh_motion_rows(self):
+        """What depends on which clips are resident: the per-env motion lengths and the AMP frame's per-motion shape / limb rows."""
+        lib = self._motion_lib
+        if getattr(self, "_amp_motion_shape_rows", None) is not None:
+            self._amp_motion_shape_rows = lib.motion_bodies[:, :-6]
+        if getattr(self, "_amp_motion_limb_rows", None) is not None:
+            self._amp_motion_limb_rows = lib.motion_limb_weights
+        self._motion_len_env = lib.get_motion_length(self._sampled_motion_ids).contiguous()
+
+    def eval_curr_motion_ids(self):
+        """Data-set id of the clip every env plays (MotionLibBase._curr_motion_ids, one per env)."""
+        lib = self._motion_lib
+        curr = getattr(lib, "_curr_motion_ids", None)
+        return curr[self._sampled_motion_ids] if curr is not None else self._sampled_motion_ids
+
+    @contextlib.contextmanager
+    def evaluation_mode(self, record_positions=False):
+        """The switches IMAmpAgent.eval makes around its sweep (im_amp.py:160-182) and takes back afterwards (:223-234): termination at 0.5 m
+        of mean body distance, no motion cycling, no far masking, no recovery / fall episodes, flags.test / flags.im_eval, the evaluation
+        library, and UHC's evaluation bodies for a task that resets on more than 15.  Inside, every post_physics_step adds the step to the
+        per-env metric sums (pulse_im_eval_accum); ``record_positions`` also copies the step's positions out, as the reference does."""
+        if not self._use_motion_lib:
+            raise NotImplementedError("evaluation_mode needs the MotionLib reference source")
+        saved = {"term": self._termination_distances.clone(), "cycle_motion": self.cycle_motion, "zero_out_far": self.zero_out_far,
+                 "reset_ids": self._reset_bodies_id, "test": self.test, "im_eval": self.im_eval, "start_idx": self.start_idx}
+        getup = "_recovery_episode_prob" in self.__dict__
+        if getup:
+            saved["probs"] = (self._recovery_episode_prob, self._fall_init_prob)
+            self._recovery_episode_prob, self._fall_init_prob = 0.0, 0.0
+        self._termination_distances[:] = 0.5
+        self.cycle_motion, self.zero_out_far = False, False
+        self.test, self.im_eval = True, True
+        self._motion_lib = self._motion_eval_lib
+        if self._reset_bodies_id.numel() > 15:
+            self._reset_bodies_id = self._eval_track_bodies_id
+        ring, accum = ops.im_eval_state(self.num_envs, self.num_bodies, self.device)
+        self._eval_state = {"ring": ring, "accum": accum, "step": 0, "num_steps": None, "ref": {}, "record": [] if record_positions else None}
+        try:
+            yield self._eval_state
+        finally:
+            self._eval_state = None
+            self._termination_distances[:] = saved["term"]
+            self.cycle_motion, self.zero_out_far = saved["cycle_motion"], saved["zero_out_far"]
+            self.test, self.im_eval = saved["test"], saved["im_eval"]
+            self._motion_lib = self._motion_train_lib
+            if self._motion_eval_lib is not self._motion_train_lib:
+                self._motion_eval_lib.release()                                 # its resident records are rebuilt by the next sweep's first load
+            if getup:
+                self._recovery_episode_prob, self._fall_init_prob = saved["probs"]
+            self._reset_bodies_id = saved["reset_ids"]
+            self.start_idx = saved["start_idx"]
+            self._sampled_motion_ids.copy_(torch.arange(self.num_envs, dtype=torch.int64, device=self.device) % self._motion_lib.num_motions())
+            self._refresh_motion_rows()
+
+    def _eval_accumulate(self):
+        """humanoid_im.py:667-673 without the copies: the reference positions at the motion time the step's reward was computed against
+        (progress_buf already holds the step's + 1) and the simulated records go to the accumulation kernel."""
+        st = self._eval_state
+        if st["num_steps"] is None:
+            raise RuntimeError("evaluation_mode: call begin_seq_motion_samples() before stepping")
+        ref = self._motion_lib.query(self._sampled_motion_ids, offset=self._global_offset, progress=self.progress_buf, step_shift=0, dt=self.dt,
+                                     start_times=self._motion_start_times, start_offsets=self._motion_start_times_offset, out=st["ref"],
+                                     fields=("rg_pos",))["rg_pos"]
+        rb = self.sim.rigid_body_state
+        ops.im_eval_accum(rb, ref, st["num_steps"], st["step"], st["ring"], st["accum"])
+        if st["record"] is not None:
+            st["record"].append((rb[..., 0:3].cpu().numpy(), ref.cpu().numpy()))
+        st["step"] += 1
+
     def _update_cycle_count(self):
         """humanoid_im.py:1042-1045, called from pre_physics_step (:1112)."""
         self._cycle_counter.sub_(1).clamp_(min=0)
@@ -764,6 +878,8 @@ class HumanoidIm:
                 self._update_hist_amp_obs()
                 self._compute_amp_observations()
                 self.extras["amp_obs"] = self._amp_obs_buf.view(-1, self.get_num_amp_obs())
+        if self._eval_state is not None:
+            self._eval_accumulate()
 
     # ------------------------------------------------------------------ reset
     def reset(self, env_ids=None):
@@ -788,13 +904,14 @@ class HumanoidIm:
         if self._use_motion_lib:
             # _reset_envs -> _sample_ref_state (humanoid_im.py:966-986) for the masked envs in ONE launch: new start time
             # (phase * motion length), clock and reset / terminate flags cleared, simulator state := reference state there
-            if self._state_init_random:
+            random_start = self._state_init_random and not self.test                      # flags.test: motion_times[:] = 0 (humanoid_im.py:976-977)
+            if random_start:
                 self._reset_phase.uniform_(0.0, 1.0, generator=self._clock_gen)           # sample_time_interval's torch.rand (HumanoidIm._sample_time)
             sim = self.sim
             self._motion_lib.query(self._sampled_motion_ids, offset=self._global_offset, dt=self.dt, start_offsets=self._motion_start_times_offset,
                                    out={"rb_records": sim.rigid_body_state, "dof_pos": sim.dof_pos, "dof_vel": sim.dof_vel},
                                    fields=("rb_records", "dof_pos", "dof_vel"),
-                                   reset={"mask": mask, "phase": self._reset_phase if self._state_init_random else None, "time_interval": True,
+                                   reset={"mask": mask, "phase": self._reset_phase if random_start else None, "time_interval": True,
                                           "start_times": self._motion_start_times, "progress": self.progress_buf,
                                           "clear0": self.reset_buf, "clear1": self._terminate_buf, "clear2": self._cycle_counter,
                                           "zero_start_offsets": self._motion_start_times_offset, "zero_global_offset": self._global_offset})

@@ -210,6 +210,37 @@ class MotionLib:
         self.load_motions(skeleton_trees, gender_betas, limb_weights)
         return self
 
+    def eval_twin(self):
+        """The evaluation library of this one (humanoid_im.py:336-339: the same motion file under ``im_eval``): the same clips numbered longest
+        first (stable, as filter_motion_data orders them), no heading draw, its own sampling weights and termination history.  The staged
+        device buffers are shared, only the per-clip tables are reordered; nothing is resident until its first ``load_motions``.  A library
+        built from finished tables cannot reload and is its own twin."""
+        if self._src is None:
+            return self
+        src = self._src
+        order = sorted(range(self._num_unique_motions), key=lambda i: int(src["frames"][i]), reverse=True)
+        idx = torch.tensor(order, dtype=torch.int64)
+        twin = type(self).__new__(type(self))
+        twin._device, twin.num_bodies, twin.num_dof = self._device, self.num_bodies, self.num_dof
+        twin.offsets, twin.frame_stride = self.offsets, self.frame_stride
+        twin._motion_data_keys = [self._motion_data_keys[i] for i in order]
+        twin._num_unique_motions = self._num_unique_motions
+        twin._src = {"rot": src["rot"], "trans": src["trans"], "start": src["start"][idx], "frames": src["frames"][idx], "fps": src["fps"][idx],
+                     "has_beta": src["has_beta"][idx]}
+        twin._im_eval, twin._generator = True, self._generator
+        twin._sampling_prob = torch.ones(twin._num_unique_motions, device=self._device) / twin._num_unique_motions
+        twin._termination_history = torch.zeros(twin._num_unique_motions, device=self._device)
+        twin._curr_motion_ids, twin._generation, twin._lengths_host = None, 0, None
+        twin._last_load = dict(self._last_load)
+        twin._num_motions = self._num_motions
+        return twin
+
+    def release(self):
+        """Drop the resident records of a library that reloads (the evaluation library between two sweeps): the next ``load_motions`` builds
+        them again.  A library built from finished tables has nothing else and keeps them."""
+        if self._src is not None:
+            self.frames = None
+
     @property
     def reloads(self):
         """True for a library built from raw data: ``load_motions`` re-draws which clips are resident and rebuilds the records."""

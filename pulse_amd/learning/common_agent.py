@@ -106,6 +106,8 @@ class CommonAgent:
         self.rewards_shaper = rlg.DefaultRewardsShaper(**config.get("reward_shaper", {}))
         self.max_epochs = int(config.get("max_epochs", 1e6))
         self.save_freq = int(config.get("save_frequency", 0))
+        self.has_eval = bool(config.get("has_eval", False))                     # flags.has_eval (run_hydra.py): evaluate every save_frequency epochs
+        self.last_eval_info = {}
         self.games_to_track = int(config.get("games_to_track", 100))
         self.seq_len = int(config.get("seq_length", 4))
         self.is_rnn = False
@@ -780,8 +782,19 @@ class CommonAgent:
                 import os
                 os.makedirs(self.nn_dir, exist_ok=True)
                 self.save(os.path.join(self.nn_dir, self.config.get("name", "Humanoid")))
+            if self.has_eval and self.save_freq > 0 and epoch_num % self.save_freq == 0:       # common_agent.py:164-166 (flags.has_eval, im_amp.py:138)
+                eval_info = self.eval()
+                self.last_eval_info = eval_info
+                train_info.update(eval_info)
+                self.obs = self.env_reset()                                                     # eval() left every env reset
+                if self.rank == 0 and eval_info:
+                    print("eval: " + " ".join(f"{k}: {v:.4f}" for k, v in eval_info.items() if isinstance(v, float)), flush=True)
             if epoch_num >= max_epochs:
                 return self.game_rewards.get_mean(), epoch_num
+
+    def eval(self):
+        """common_agent.py:187-189: no evaluation routine at this level (IMAmpAgent has one)."""
+        return {}
 
     def _init_train(self):
         return

@@ -6,9 +6,12 @@ Mirrors phc/learning/im_amp.py:39-132 on top of AMPAgent:
   restore               :102-118 checkpoint + the newest termination history (failed_*.pkl) pushed into the motion library's
                                  sampling probabilities
   update_training_data  :127-132 PMCP: hard / soft re-weighting of the motion sampling from the keys that failed evaluation
-  eval                  :136-363 evaluation over the motion library.  The reference computes MPJPE-style metrics with smpl_sim's
-                                 compute_metrics_lite (a third-party dependency that is absent); here the evaluation loop reports
-                                 success rate and mean global / root-relative body-position errors from the same rigid-body tensors.
+  eval                  :136-363 the sweep over the whole motion data set in batches of num_envs clips under evaluation rules
+                                 (HumanoidIm.evaluation_mode), with _post_step_eval's batch bookkeeping (learning/eval_sweep.py).  The
+                                 reference copies every step's body positions to the host and computes smpl_sim's compute_metrics_lite
+                                 (a third-party dependency that is absent) at the end; here pulse_im_eval_accum sums the same five
+                                 per-frame terms on the device (include/pulse_hip.h 2b'' fixes their definitions).  failed_keys are
+                                 motion keys, what update_hard / soft_sampling_weight index the data set by.
 """
 import glob
 import os
@@ -74,32 +77,59 @@ class IMAmpAgent(AMPAgent):
         with open(osp.join(self.network_path, f"failed_{self.epoch_num:010d}.pkl"), "wb") as f:
             pickle.dump({"failed_keys": failed_keys, "termination_history": lib._termination_history}, f)
 
-    # ------------------------------------------------------------------ im_amp.py:136-363 (metrics: see module docstring)
-    def eval(self, max_steps=None):
-        """Every env plays its motion once with deterministic actions; returns success rate and position errors."""
+    # ------------------------------------------------------------------ im_amp.py:136-363
+    def eval(self, max_steps=None, return_positions=False):
+        """The reference's evaluation sweep: the whole data set in batches of num_envs clips under evaluation rules (HumanoidIm.evaluation_mode),
+        deterministic actions, batch bookkeeping by EvalSweep (_post_step_eval), metrics summed on the device by pulse_im_eval_accum.  Ends
+        with update_training_data(failed_keys) -- motion keys -- and the env back in training mode, every env reset.  ``max_steps`` caps a
+        batch.  The env must take its reference from a MotionLib (recorded reference frames have no data set to walk: evaluation_mode raises).
+        ``return_positions``: also copy every step's positions out and return per-motion (T_i, J, 3) pred / gt arrays (the
+        reference's pred_pos_all / gt_pos_all; tests and debugging)."""
+        from .eval_sweep import EvalSweep
         task = self.vec_env.env.task
         n = task.num_envs
         max_steps = int(max_steps or task.max_episode_length)
         self.set_eval()
-        obs = self.vec_env.reset()
-        done_once = torch.zeros(n, dtype=torch.bool, device=self.ppo_device)
-        failed = torch.zeros(n, dtype=torch.bool, device=self.ppo_device)
-        err_g = torch.zeros(n, device=self.ppo_device)
-        err_l = torch.zeros(n, device=self.ppo_device)
-        steps = torch.zeros(n, device=self.ppo_device)
-        for _ in range(max_steps):
-            act = self.get_action({"obs": obs}, is_determenistic=True)
-            obs, _, dones, infos = self.env_eval_step(self.vec_env, act)
-            live = ~done_once
-            ref = task._track["rb_records"][..., 0:3] if getattr(task, "_use_motion_lib", False) else task.sim.rigid_body_state[..., 0:3]
-            cur = task.sim.rigid_body_state[..., 0:3]
-            err_g += live * (cur - ref).norm(dim=-1).mean(-1)
-            err_l += live * ((cur - cur[:, :1]) - (ref - ref[:, :1])).norm(dim=-1).mean(-1)
-            steps += live
-            failed |= live & (infos["terminate"] > 0)
-            done_once |= dones > 0
-            obs = self.vec_env.reset_masked(dones > 0)
-        steps = steps.clamp(min=1)
-        return {"success_rate": float(1.0 - failed.float().mean()), "mpjpe_g": float((err_g / steps).mean() * 1000.0),
-                "mpjpe_l": float((err_l / steps).mean() * 1000.0), "failed_keys": torch.nonzero(failed).flatten().tolist(),
-                "num_motions": n}
+        positions = {"pred": [], "gt": []}
+        with torch.no_grad(), task.evaluation_mode(record_positions=return_positions) as st:
+            lib = task._motion_lib
+            sweep = EvalSweep(n, lib._num_unique_motions, max_steps=max_steps)
+            task.begin_seq_motion_samples()
+            obs = task.obs_buf
+            while True:
+                act = self.get_action({"obs": obs}, is_determenistic=True)
+                obs, _, dones, infos = self.env_eval_step(self.vec_env, act)
+                batch_end, end = sweep.post_step(infos["terminate"], st["num_steps"], task.eval_curr_motion_ids(), task.start_idx)
+                if batch_end:
+                    sweep.end_batch(st["accum"])
+                    if return_positions:
+                        self._slice_positions(st["record"], st["num_steps"].tolist(), positions)
+                        st["record"].clear()
+                    if end:
+                        break
+                    task.forward_motion_samples()          # done[:] = 1: the next batch of clips, every env reset
+                    obs = task.obs_buf
+                else:
+                    obs = self.vec_env.reset_masked(dones > 0)
+            keys = lib._motion_data_keys
+            failed_keys, success_keys = sweep.keys(keys)
+            info = sweep.eval_info()
+            num_motions = lib._num_unique_motions
+        self.vec_env.reset()                               # every env, back in training mode (:234)
+        self.update_training_data(failed_keys)
+        out = dict(info)
+        out.update({"success_rate": info["eval_success_rate"], "mpjpe_g": info["eval_mpjpe_all"], "mpjpe_l": info["mpjpel_all"],
+                    "failed_keys": failed_keys, "success_keys": success_keys, "num_motions": num_motions, "motion_keys": list(keys),
+                    "batch_lengths": list(sweep.batch_lengths)})
+        if return_positions:
+            out["pred_pos_all"], out["gt_pos_all"] = positions["pred"][:num_motions], positions["gt"][:num_motions]
+        return out
+
+    @staticmethod
+    def _slice_positions(record, num_steps, positions):
+        """all_body_pos_pred[:(i - 1), idx] (im_amp.py:284-287): motion idx keeps the first num_steps - 1 recorded steps of its batch."""
+        import numpy as np
+        pred, gt = np.stack([r[0] for r in record]), np.stack([r[1] for r in record])
+        for idx, i in enumerate(num_steps):
+            positions["pred"].append(pred[:max(i - 1, 0), idx])
+            positions["gt"].append(gt[:max(i - 1, 0), idx])

@@ -588,6 +588,55 @@ def compute_humanoid_im_reset(reset_buf, progress_buf, contact_buf, contact_body
 
 
 # --------------------------------------------------------------------------- #
+# evaluation metrics (IMAmpAgent.eval): one launch of pulse_im_eval_accum per control step
+# --------------------------------------------------------------------------- #
+EVAL_ACCUM_COLUMNS = ("mpjpe_g", "mpjpe_l", "mpjpe_pa", "vel_dist", "accel_dist", "frames", "vel_frames", "accel_frames")
+
+
+def im_eval_state(num_envs, num_bodies, device):
+    """The per-env state of an evaluation sweep: the two-step position ring (N, 2, 2, J, 3) float32 and the accumulator rows (N, 8)
+    float64 (EVAL_ACCUM_COLUMNS: five sums in mm, three frame counts)."""
+    return (torch.zeros(num_envs, 2, 2, num_bodies, 3, dtype=torch.float32, device=device),
+            torch.zeros(num_envs, 8, dtype=torch.float64, device=device))
+
+
+def im_eval_accum(rb, ref_pos, num_steps, step, ring, accum, *, env_mask=None):
+    """Add control step ``step`` (0-based index inside the evaluation batch) to the per-env metric sums (include/pulse_hip.h 2b'').
+    ``rb`` (N, J, 13) simulated records and ``ref_pos`` (N, J, 3) reference positions may be row-strided views (any env pitch, bodies
+    contiguous); ``num_steps`` (N) int32; ``accum`` (N, 8) float64, row-strided allowed; ``ring`` contiguous (N, 2, 2, J, 3).
+    ``env_mask`` (N) bool / uint8: envs with 0 are left alone."""
+    rb, ref_pos, ring = _dev(rb, "rb"), _dev(ref_pos, "ref_pos"), _dev(ring, "ring")
+    accum, num_steps = _dev(accum, "accum", torch.float64), _dev(num_steps, "num_steps", torch.int32)
+    if rb.dim() != 3 or rb.shape[2] != 13:
+        raise ValueError(f"rb: expected (N, J, 13), got {tuple(rb.shape)}")
+    n, j = rb.shape[0], rb.shape[1]
+    if tuple(ref_pos.shape) != (n, j, 3):
+        raise ValueError(f"ref_pos: expected shape {(n, j, 3)}, got {tuple(ref_pos.shape)}")
+    if (j > 1 and rb.stride(1) != 13) or rb.stride(2) != 1:
+        raise ValueError("rb: the (J, 13) records of an env must be contiguous (only the env pitch may be larger)")
+    if (j > 1 and ref_pos.stride(1) != 3) or ref_pos.stride(2) != 1:
+        raise ValueError("ref_pos: the (J, 3) positions of an env must be contiguous (only the env pitch may be larger)")
+    if tuple(ring.shape) != (n, 2, 2, j, 3) or not ring.is_contiguous():
+        raise ValueError(f"ring: contiguous {(n, 2, 2, j, 3)} expected, got {tuple(ring.shape)}")
+    if tuple(accum.shape) != (n, 8) or accum.stride(1) != 1:
+        raise ValueError(f"accum: expected shape {(n, 8)} with contiguous rows, got {tuple(accum.shape)}")
+    if tuple(num_steps.shape) != (n,) or not num_steps.is_contiguous():
+        raise ValueError(f"num_steps: contiguous {(n,)} expected")
+    a = _lib.ImEvalArgs()
+    a.rb, a.rb_env_stride = rb.data_ptr(), rb.stride(0) if n > 1 else 13 * j
+    a.ref_pos, a.ref_env_stride = ref_pos.data_ptr(), ref_pos.stride(0) if n > 1 else 3 * j
+    a.num_envs, a.num_bodies, a.num_steps, a.step = n, j, num_steps.data_ptr(), int(step)
+    if env_mask is not None:
+        m = env_mask.view(torch.uint8) if env_mask.dtype == torch.bool else _dev(env_mask, "env_mask", torch.uint8)
+        if not m.is_cuda or tuple(m.shape) != (n,) or not m.is_contiguous():
+            raise ValueError(f"env_mask: contiguous device {(n,)} bool / uint8 expected")
+        a.env_mask = m.data_ptr()
+    a.ring, a.accum, a.accum_stride = ring.data_ptr(), accum.data_ptr(), accum.stride(0) if n > 1 else 8
+    _lib.check(_lib.load().pulse_im_eval_accum(ctypes.byref(a), _stream()), "pulse_im_eval_accum")
+    return accum
+
+
+# --------------------------------------------------------------------------- #
 # downstream tasks (speed / reach / strike): one launch of pulse_task_step
 # --------------------------------------------------------------------------- #
 def task_step(task, rb, *, what, prev_root_pos=None, dt=1.0 / 30.0, tar_speed=None, tar_pos=None, reach_body_id=0, tar_states=None,
