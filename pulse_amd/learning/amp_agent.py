@@ -546,13 +546,9 @@ class AMPAgent(CommonAgent):
         # the critic (PPO pass only) is not visited: its gradient is written as zeros by the region reduce, which also leaves the norm clip's
         # sums of squares on one GPU (with data parallelism the norm is taken after the all-reduce)
         sqp = self._sq_slice(0)
-        fused = model.book.reduce_grads(1.0 / self.world_size, untouched=model._untouched(ws, ("dec", "enc", "prior")),
-                                        sq_partials=None if self.multi_gpu else sqp)
-        if self.multi_gpu:
-            self.dist.sync_gradients(model.grad)
+        model._reduce(1.0 / self.world_size, model._untouched(ws, ("dec", "enc", "prior")), sqp,
+                      sync=self.dist.sync_gradients if self.multi_gpu else None)
         self.kin_step += 1
-        if not fused:
-            K.sqnorm_partial(model.grad, model.n_flat, sqp)
         K.adam_step(model.flat, model.grad, self.kin_exp_avg, self.kin_exp_avg_sq, model.n_flat, lr=self.kin_lr, step=self.kin_step,
                     max_norm=self.grad_norm, sqnorm_partials=sqp, grad_norm_out=self._grad_norm)
         info["kin_loss"] = kin_loss

@@ -191,26 +191,19 @@ class CommonAgent:
 
     def _build_model(self, net_config):
         params = self.config["network"]
-        if params.get("name", "amp") == "amp_z":
+        name = params.get("name", "amp")
+        if name in ("amp_z", "amp_sept", "amp_mcp"):
+            # the graph-built networks (graph.GraphModel).  amp_mcp: AMPMCPBuilder.Network (amp_network_mcp_builder.py:23-87), mu = the composer's
+            # num_prim mixture weights (HumanoidImMCP blends the primitives)
             from .model_z import AMPZModel
-            task = self.vec_env.env.task
-            return AMPZModel(params, actions_num=net_config["actions_num"], self_obs_size=task.get_self_obs_size(),
-                             task_obs_size=task.get_task_obs_size(), task_obs_size_detail=task.get_task_obs_size_detail(),
-                             device=self.ppo_device, split_k=int(self.config.get("split_k", 8)), generator=self.noise_generator)
-        if params.get("name", "amp") == "amp_sept":
+            from .network_mcp import AMPMCPModel
             from .network_sept import AMPSeptModel
             task = self.vec_env.env.task
-            return AMPSeptModel(params, actions_num=net_config["actions_num"], self_obs_size=task.get_self_obs_size(),
-                                task_obs_size=task.get_task_obs_size(), task_obs_size_detail=task.get_task_obs_size_detail(),
-                                device=self.ppo_device, split_k=int(self.config.get("split_k", 8)))
-        if params.get("name", "amp") == "amp_mcp":
-            # AMPMCPBuilder.Network (amp_network_mcp_builder.py:23-87): mu = the composer's num_prim mixture weights (HumanoidImMCP blends the primitives)
-            from .network_mcp import AMPMCPModel
-            task = self.vec_env.env.task
-            return AMPMCPModel(params, actions_num=net_config["actions_num"], self_obs_size=task.get_self_obs_size(),
-                               task_obs_size=task.get_task_obs_size(), task_obs_size_detail=task.get_task_obs_size_detail(),
-                               device=self.ppo_device, split_k=int(self.config.get("split_k", 8)))
-        if params.get("name", "amp") == "amp_z_reader":
+            extra = {"generator": self.noise_generator} if name == "amp_z" else {}
+            return {"amp_z": AMPZModel, "amp_sept": AMPSeptModel, "amp_mcp": AMPMCPModel}[name](
+                params, actions_num=net_config["actions_num"], self_obs_size=task.get_self_obs_size(), task_obs_size=task.get_task_obs_size(),
+                task_obs_size_detail=task.get_task_obs_size_detail(), device=self.ppo_device, split_k=int(self.config.get("split_k", 8)), **extra)
+        if name == "amp_z_reader":
             # AMPZReaderBuilder.Network (amp_network_z_reader_builder.py:21-57) IS AMPBuilder.Network -- the plain actor / critic MLP
             # whose 32-d "action" is the latent a frozen PULSE decoder turns into joint targets inside env.step -- unless
             # vae_prior_policy swaps sigma for the decoder's prior log-variance (:46-55; no shipped config sets it)

@@ -29,11 +29,7 @@ import torch
 from .. import kernels as K
 from .._lib import ACT_NONE, ACT_RELU, EPI_RELU_GRAD, GEMM_OUT_CONTIG
 from . import network as _network
-from .graph import Linear, ParamBook, init_linear_, r4
-
-
-def r32(x):
-    return (x + 31) // 32 * 32
+from .graph import Linear, ParamBook, init_linear_, r4, r32
 
 
 class DiscNetwork:
@@ -72,22 +68,13 @@ class DiscNetwork:
 
     # ---- reference-named parameters
     def state_dict(self, buf=None):
-        out = {}
-        for lin in (self.l1, self.l2, self.l3):
-            out[lin.w.name] = self.book.get(lin.w.name, buf).clone()
-            out[lin.b.name] = self.book.get(lin.b.name, buf).reshape(-1).clone()
-        return out
+        return self.book.state_dict(buf)
 
     def gradients(self):
         return self.state_dict(self.book.grad)
 
     def load_state_dict(self, sd, strict=True):
-        for lin in (self.l1, self.l2, self.l3):
-            for p in (lin.w, lin.b):
-                if p.name in sd:
-                    self.book.set(p.name, sd[p.name])
-                elif strict:
-                    raise KeyError(p.name)
+        self.book.load_state_dict(sd, strict)
 
     def get_disc_logit_weights(self):
         return self.book.get(self.l3.w.name).reshape(-1)

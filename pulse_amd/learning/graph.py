@@ -37,6 +37,10 @@ def r4(x):
     return (x + 3) // 4 * 4
 
 
+def r32(x):
+    return (x + 31) // 32 * 32
+
+
 class Param:
     def __init__(self, name, rows, cols, colmap, off, pitch):
         self.name, self.rows, self.cols, self.colmap, self.off, self.pitch = name, rows, cols, colmap, off, pitch
@@ -51,14 +55,25 @@ class ParamBook:
         self.params = {}
         self._n = 0
         self.flat = None
+        self._slab_layout = {}           # parameter name -> (slabs its weight-gradient launch writes, batch that said so): note_slab_layout
+        self._reduce_cache = {}          # untouched ranges -> the pre-built region reduce (False: too many regions for one launch)
 
     def add(self, name, rows, cols, colmap=None, pitch_align=4):
         """rows x cols logical matrix (cols = 1 row vector for biases when rows == 1).  ``colmap``: list
         of physical column indices of the logical columns (default identity); physical pitch = roundup(max+1, pitch_align) (the
-        bf16-storage GEMM wants reduction-contiguous rows that are whole zero-padded 32-deep k-tiles: pitch_align 32)."""
+        bf16-storage GEMM wants reduction-contiguous rows that are whole zero-padded 32-deep k-tiles: pitch_align 32).
+        After ``finalize()`` nothing is allocated any more: the call returns the parameter registered under ``name`` (graphs for every
+        batch size are built by the same code and share one flat buffer) and raises if it does not describe that parameter."""
         phys = (max(colmap) + 1) if colmap is not None else cols
         pitch = (phys + pitch_align - 1) // pitch_align * pitch_align
-        p = Param(name, rows, cols, list(colmap) if colmap is not None else None, self._n, pitch)
+        colmap = list(colmap) if colmap is not None else None
+        if self.flat is not None:
+            p = self.params.get(name)
+            if p is None or (p.rows, p.cols, p.colmap, p.pitch) != (rows, cols, colmap, pitch):
+                was = "nothing" if p is None else f"{p.rows} x {p.cols}, pitch {p.pitch}, column map {'equal' if p.colmap == colmap else 'different'}"
+                raise ValueError(f"ParamBook: {name} ({rows} x {cols}, pitch {pitch}) after finalize(), but registered under that name: {was}")
+            return p
+        p = Param(name, rows, cols, colmap, self._n, pitch)
         self.params[name] = p
         self._n += rows * pitch
         return p
@@ -99,9 +114,27 @@ class ParamBook:
         else:
             v[:, :p.cols] = value
 
+    def logical(self, name, buf=None, rows=None):
+        """The logical view of ``name`` as the reference shapes it: bias rows flattened, ``rows`` a slice of a stacked matrix / bias."""
+        v = self.get(name, buf)
+        if name.endswith(".bias"):
+            v = v.reshape(-1)
+        return v if rows is None else v[rows]
+
+    def state_dict(self, buf=None):
+        """name -> clone of the logical view (of ``buf``: the gradients, say), in registration order."""
+        return {name: self.logical(name, buf).clone() for name in self.params}
+
+    def load_state_dict(self, sd, strict=True):
+        for name in self.params:
+            if name in sd:
+                self.set(name, sd[name])
+            elif strict:
+                raise KeyError(name)
+
     def note_slab_layout(self, name, nslabs, m):
         """Record / check the number of gradient slabs the weight-gradient launch of parameter ``name`` writes (see backward_plan)."""
-        lay = self.__dict__.setdefault("_slab_layout", {})
+        lay = self._slab_layout
         seen = lay.get(name)
         if seen is None:
             lay[name] = (nslabs, m)
@@ -122,7 +155,7 @@ class ParamBook:
         """[(offset, count, nslabs)] covering [0, n_flat): per parameter the number of slabs its weight-gradient launch writes
         (note_slab_layout; split_k for a parameter no launch registered), 0 for a parameter inside one of the ``untouched`` ranges
         [(lo, hi), ...] (no launch of this pass writes it: its gradient is zero); adjacent parameters with equal counts are merged."""
-        lay = self.__dict__.get("_slab_layout", {})
+        lay = self._slab_layout
         regions = []
         pos = 0
         for p in sorted(self.params.values(), key=lambda q: q.off):
@@ -152,11 +185,10 @@ class ParamBook:
         leaves the per-block sums of squares of the result (clip_grad_norm_ without its own pass).  Returns True when sq_partials were written."""
         if untouched is not None and REGION_REDUCE:
             key = tuple(untouched)
-            cache = self.__dict__.setdefault("_reduce_cache", {})
-            rg = cache.get(key)
+            rg = self._reduce_cache.get(key)
             if rg is None:
                 regions = self.reduce_regions(untouched)
-                rg = cache[key] = K.ReduceGrads(self.slabs, self.n_flat, [(o, c, n, 0.0) for o, c, n in regions], self.grad) if len(regions) <= 32 else False
+                rg = self._reduce_cache[key] = K.ReduceGrads(self.slabs, self.n_flat, [(o, c, n, 0.0) for o, c, n in regions], self.grad) if len(regions) <= 32 else False
             if rg:
                 rg.run(scale=scale, sq_partials=sq_partials)
                 return sq_partials is not None
@@ -233,7 +265,7 @@ class MlpGraph:
                          "tag": tag})
         return lin
 
-    def mlp(self, book, prefix, src, in_features, units, act, dst_names, src_col=0, colmap=None, first_grad_ranges=None, start_index=0,
+    def mlp(self, prefix, src, in_features, units, act, dst_names, src_col=0, colmap=None, first_grad_ranges=None, start_index=0,
             final_linear=None, final_dst=None, final_dst_col=0, tag=None):
         """nn.Sequential(Linear, act, Linear, act, ...) [+ an appended Linear without activation].  Layer i is
         named f"{prefix}.{start_index + 2 i}" like the reference's Sequential indices.  Returns the list of Linear objects."""
@@ -241,7 +273,7 @@ class MlpGraph:
         prev_act, prev_aux = None, None
         for i, u in enumerate(units):
             name = f"{prefix}.{start_index + 2 * i}"
-            lin = Linear(book, name, cur_w, u, act, colmap if i == 0 else None)
+            lin = Linear(self.book, name, cur_w, u, act, colmap if i == 0 else None)
             dst = dst_names[i]
             self.buffer(dst, u)
             if i == 0:
@@ -254,7 +286,7 @@ class MlpGraph:
             cur, cur_w, cur_col = dst, u, 0
         if final_linear is not None:
             name = f"{prefix}.{start_index + 2 * len(units)}"
-            lin = Linear(book, name, cur_w, final_linear, ACT_NONE)
+            lin = Linear(self.book, name, cur_w, final_linear, ACT_NONE)
             if final_dst not in self.act_bufs:
                 self.buffer(final_dst, final_linear)
             self.linear(lin, cur, final_dst, dst_col=final_dst_col, grad_ranges=[(0, cur_w, prev_act, prev_aux, 0)], tag=tag)
@@ -357,3 +389,175 @@ class MlpGraph:
                 p.gemm(gz, f, gx, M=m, N=c1 - c0, K=lin.n, lda=ldg, ldb=lin.w.pitch, ldc=gx.stride(0), b_layout=GEMM_OUT_CONTIG,
                        a_off=gzo, b_off=lin.w.off + c0, c_off=op["src_col"] + c0, epilogue=epi, aux=aux, ldaux=ldaux, aux_off=aux_off)
         return p
+
+
+def _concat_plans(a, b):
+    p = K.Plan()
+    p.ops = a.ops + b.ops
+    return p
+
+
+class GraphNetwork:
+    """Base of the policy networks that are one MlpGraph over one ParamBook (amp_z, amp_sept, amp_mcp).  A subclass parses its config, sets
+    its layout constants, calls this constructor LAST and describes its layers twice over:
+
+      _build(m, x=None) -> {"graph": g, "lins": lins}   the MlpGraph for m rows (start from ``_new_graph``) and its Linear objects, a dict of
+                                                        Linear / list of Linear in the reference's creation order (= the init draw order);
+      _plans(g) -> dict                                 the fwd_* / bwd_* launch plans ``graph()`` hands out.
+
+    The constructor's ``_build(1)`` registers every parameter; after ``finalize()`` the same code builds the graph of any batch size over the
+    registered parameters (ParamBook.add), so all of them share one flat buffer."""
+
+    def __init__(self, params, *, actions_num, self_obs_size, task_obs_size, device, split_k):
+        if not params.get("separate", False):
+            raise NotImplementedError("separate: True required")
+        self.device = torch.device(device)
+        self.self_obs_size, self.task_obs_size = int(self_obs_size), int(task_obs_size)
+        self.obs_size = self.self_obs_size + self.task_obs_size
+        self.in_pitch = r32(self.obs_size)
+        self.actions_num = int(actions_num)
+        self.a_pitch = r4(self.actions_num)
+        si = params["space"]["continuous"].get("sigma_init", {"val": 0.0})
+        self.sigma = torch.full((self.actions_num,), float(si.get("val", 0.0)), dtype=torch.float32, device=self.device)
+        self.split_k = split_k
+        self._graphs = {}
+        self.book = ParamBook(self.device, split_k)
+        self.lins = self._build(1)["lins"]                      # registers every parameter in construction order
+        self.book.finalize()
+        self.reset_parameters()
+        self.training = True
+
+    def _new_graph(self, m, x=None):
+        """An MlpGraph for m rows whose buffer 'x' is ``x`` (m, in_pitch): the normalised observation buffer, or a fresh one."""
+        g = MlpGraph(self.book, m)
+        g.buffer("x", self.obs_size, tensor=x if x is not None else torch.zeros(m, self.in_pitch, device=self.device))
+        return g
+
+    def graph(self, m, x=None):
+        """Buffers + plans for a batch of m rows; ``x`` (m, in_pitch) is the normalised observation buffer."""
+        key = (m, x.data_ptr() if x is not None else 0)
+        out = self._graphs.get(key)
+        if out is None:
+            g = self._build(m, x=x)["graph"]
+            out = self._graphs[key] = {"g": g, "x": g.act_bufs["x"], **self._plans(g)}
+        return out
+
+    # ------------------------------------------------------------------ parameters (reference names)
+    def _names(self):
+        """reference key -> (book name, row slice or None)"""
+        return {n: (n, None) for n in self.book.params}
+
+    def state_dict(self, buf=None):
+        sd = {k: self.book.logical(n, buf, sl).clone() for k, (n, sl) in self._names().items()}
+        sd["a2c_network.sigma"] = self.sigma.clone()
+        return sd
+
+    def gradients(self):
+        sd = self.state_dict(self.book.grad)
+        del sd["a2c_network.sigma"]
+        return sd
+
+    def load_state_dict(self, sd, strict=True):
+        stacked = {}                                            # book name -> {first row: the reference's part}
+        for k, (n, sl) in self._names().items():
+            if k not in sd:
+                if strict:
+                    raise KeyError(k)
+            elif sl is None:
+                self.book.set(n, sd[k])
+            else:
+                stacked.setdefault(n, {})[sl.start] = sd[k].to(self.device, torch.float32)
+        for n, parts in stacked.items():
+            p = self.book.params[n]
+            is_bias = n.endswith(".bias")
+            full = torch.cat([parts[k].reshape(1, -1) if is_bias else parts[k].reshape(-1, p.cols) for k in sorted(parts)],
+                             dim=1 if is_bias else 0)
+            self.book.set(n, full)
+        if "a2c_network.sigma" in sd:
+            self.sigma.copy_(sd["a2c_network.sigma"].to(self.device, torch.float32))
+
+    def reset_parameters(self, generator=None):
+        for group in self.lins.values():
+            for lin in (group if isinstance(group, list) else [group]):
+                init_linear_(self.book, lin, generator)
+
+    def parameters_count(self):
+        return self.book.n_flat
+
+    def train(self, mode=True):
+        self.training = mode
+        return self
+
+    def eval(self):
+        return self.train(False)
+
+
+class GraphModel:
+    """Base of the model interface CommonAgent / AMPAgent drive over a GraphNetwork: workspace(m, train) / forward / eval_critic / backward
+    over one flat parameter buffer.  A subclass names its ``network`` class and writes the passes.  (No ``mixed_precision`` here: a model
+    that has the attribute says it builds the bf16 training passes, CommonAgent.__init__.)"""
+    network = None
+    supports_fused_sqnorm = True
+
+    def __init__(self, params, *, actions_num, self_obs_size, task_obs_size, task_obs_size_detail, device, split_k=8):
+        self.net = n = self.network(params, actions_num=actions_num, self_obs_size=self_obs_size, task_obs_size=task_obs_size,
+                                    task_obs_size_detail=task_obs_size_detail, device=device, split_k=split_k)
+        self.device, self.book = n.device, n.book
+        self.flat, self.grad, self.n_flat = n.book.flat, n.book.grad, n.book.n_flat
+        self.sigma, self.a_pitch, self.in_pitch, self.actions_num = n.sigma, n.a_pitch, n.in_pitch, n.actions_num
+        self.training = True
+        self._ws = {}
+
+    # ---- nn.Module-like surface
+    def parameters_count(self):
+        return self.n_flat
+
+    def train(self, mode=True):
+        self.training = mode
+        return self
+
+    def eval(self):
+        return self.train(False)
+
+    def is_rnn(self):
+        return False
+
+    def state_dict(self):
+        return self.net.state_dict()
+
+    def load_state_dict(self, sd, strict=True):
+        self.net.load_state_dict(sd, strict)
+
+    # ---- workspaces
+    def workspace(self, m, train):
+        ws = self._ws.get(m)
+        if ws is None:
+            G = self.net.graph(m)
+            g = G["g"]
+            ws = self._ws[m] = {"G": G, "g": g, "x": G["x"], "val": g.act_bufs["value"][:, :1], "dval": g.grad("value")[:, :1]}
+            self._fill_workspace(ws, m)
+        return ws
+
+    def _fill_workspace(self, ws, m):
+        """The entries beyond G / g / x / val / dval.  Default: mu and its gradient are the graph's 'mu' buffer."""
+        g, A = ws["g"], self.actions_num
+        ws["mu"], ws["dmu"] = g.act_bufs["mu"][:, :A], g.grad("mu")[:, :A]
+
+    # ---- the end of a backward pass
+    def _untouched(self, ws, tags):
+        """Flat parameter ranges of the sub-networks whose tag is not in ``tags`` (the ones this pass did not visit)."""
+        key = ("untouched",) + tuple(tags)
+        if key not in ws:
+            ws[key] = ws["g"].untouched_ranges(set(tags))
+        return ws[key]
+
+    def _reduce(self, grad_scale, untouched, sq_partials=None, sync=None):
+        """grad = grad_scale * (sum of the slabs), zeros over the ``untouched`` ranges.  ``sq_partials``: the norm clip's per-block sums of
+        squares are left there, by the reduce launch itself when it can (one region launch, no ``sync``), by their own launch otherwise.
+        ``sync(grad)``: the data-parallel all-reduce, which has to come between the two."""
+        fused = self.book.reduce_grads(grad_scale, untouched=untouched, sq_partials=None if sync is not None else sq_partials)
+        if sync is not None:
+            sync(self.book.grad)
+        if sq_partials is not None and not fused:
+            K.sqnorm_partial(self.book.grad, self.book.n_flat, sq_partials)
+        return self.book.grad

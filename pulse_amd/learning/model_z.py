@@ -11,53 +11,21 @@ import torch
 
 from .. import kernels as K
 
+from .graph import GraphModel
 from .network_z import AMPZNetwork
 
 
-class AMPZModel:
-    def __init__(self, params, *, actions_num, self_obs_size, task_obs_size, task_obs_size_detail, device, split_k=8, generator=None):
-        self.net = AMPZNetwork(params, actions_num=actions_num, self_obs_size=self_obs_size, task_obs_size=task_obs_size,
-                               task_obs_size_detail=task_obs_size_detail, device=device, split_k=split_k)
-        n = self.net
-        self.device = n.device
-        self.book = n.book
-        self.flat, self.grad, self.n_flat = n.book.flat, n.book.grad, n.book.n_flat
-        self.sigma, self.a_pitch, self.in_pitch, self.actions_num = n.sigma, n.a_pitch, n.in_pitch, n.actions_num
-        self.embedding_size = n.embedding_size
+class AMPZModel(GraphModel):
+    network = AMPZNetwork
+
+    def __init__(self, params, *, generator=None, **kw):
+        super().__init__(params, **kw)
+        self.embedding_size = self.net.embedding_size
         self.generator = generator
-        self.training = True
-        self._ws = {}
 
-    # ---- nn.Module-like surface
-    def parameters_count(self):
-        return self.n_flat
-
-    def train(self, mode=True):
-        self.training = mode
-        return self
-
-    def eval(self):
-        return self.train(False)
-
-    def is_rnn(self):
-        return False
-
-    def state_dict(self):
-        return self.net.state_dict()
-
-    def load_state_dict(self, sd, strict=True):
-        self.net.load_state_dict(sd, strict)
-
-    # ---- workspaces
-    def workspace(self, m, train):
-        ws = self._ws.get(m)
-        if ws is None:
-            G = self.net.graph(m)
-            g, A = G["g"], self.actions_num
-            ws = {"G": G, "g": g, "x": G["x"], "mu": g.act_bufs["mu"][:, :A], "val": g.act_bufs["value"][:, :1],
-                  "dmu": g.grad("mu")[:, :A], "dval": g.grad("value")[:, :1], "z_noise": None}
-            self._ws[m] = ws
-        return ws
+    def _fill_workspace(self, ws, m):
+        super()._fill_workspace(ws, m)
+        ws["z_noise"] = None                                        # (a test's injected re-parameterisation noise, _embed)
 
     def _embed(self, ws):
         """form_embedding (amp_network_z_builder.py:79-121) on the encoder heads in one launch: clamp, re-parameterise, and place z and the
@@ -119,20 +87,9 @@ class AMPZModel:
     def backward_prior(self, ws):
         ws["G"]["bwd_prior"].run()                                  # d loss / d prior heads was written by backward_actor(kin=...)
 
-    supports_fused_sqnorm = True
-
     def backward(self, ws, m, grad_scale=1.0, sq_partials=None, on_bucket=None):
         """PPO backward: actor (through the VAE) + critic; weight gradients of untouched sub-nets (the prior: kin pass only) are zero.
         ``sq_partials``: the gradient reduce also leaves the norm clip's per-block sums of squares there; returns True when it did."""
         self.backward_actor(ws)
         ws["G"]["bwd_critic"].run()
-        done = self.book.reduce_grads(grad_scale, untouched=self._untouched(ws, ("dec", "enc", "critic", "critic_z")), sq_partials=sq_partials)
-        if sq_partials is not None and not done:                # (the uniform reduce: more regions than one launch takes)
-            K.sqnorm_partial(self.book.grad, self.book.n_flat, sq_partials)
-        return self.book.grad
-
-    def _untouched(self, ws, tags):
-        key = ("untouched",) + tuple(tags)
-        if key not in ws:
-            ws[key] = ws["g"].untouched_ranges(set(tags))
-        return ws[key]
+        return self._reduce(grad_scale, self._untouched(ws, ("dec", "enc", "critic", "critic_z")), sq_partials)

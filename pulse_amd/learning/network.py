@@ -28,6 +28,7 @@ import torch
 
 from .. import kernels as K
 from .._lib import ACT_RELU, ACT_SILU, EPI_RELU_GRAD, EPI_SILU_GRAD, GEMM_OUT_CONTIG
+from .graph import r4, r32
 
 
 # PULSE_RELU_BITMASK=0: the bf16-storage path's relu-grad launches re-read the bf16 activations instead of the forward's sign bytes (A/B switch; same bits)
@@ -39,14 +40,6 @@ RELU_BITMASK = os.environ.get("PULSE_RELU_BITMASK", "1") != "0"
 # there too: stress tests).
 RELU_BITMASK_F32 = os.environ.get("PULSE_RELU_BITMASK_F32", "1") in ("1", "2")
 RELU_BITMASK_F32_FORCE = os.environ.get("PULSE_RELU_BITMASK_F32", "0") == "2"      # (stress tests: also beside a concurrent chain)
-
-
-def _r4(x):
-    return (x + 3) // 4 * 4
-
-
-def _r32(x):
-    return (x + 31) // 32 * 32
 
 
 class A2CNetwork:
@@ -62,7 +55,7 @@ class A2CNetwork:
         self.actions_num = int(actions_num)
         self.value_size = 1
         self.in_dim = int(input_shape[0] if isinstance(input_shape, (tuple, list)) else input_shape)
-        self.in_pitch = _r32(self.in_dim)
+        self.in_pitch = r32(self.in_dim)
         self.units = [int(u) for u in self.units]
         if any(u % 4 for u in self.units) or not self.units:
             raise NotImplementedError("MLP unit sizes must be non-empty multiples of 4")
@@ -70,7 +63,7 @@ class A2CNetwork:
         if self.act not in (ACT_RELU, ACT_SILU):
             raise NotImplementedError(f"activation {self.activation!r} (relu / silu supported)")
         self.split_k = int(split_k)
-        self.a_pitch = _r4(self.actions_num)
+        self.a_pitch = r4(self.actions_num)
         self._build_layout()
         self.flat = torch.zeros(self.n_flat, dtype=torch.float32, device=self.device)
         self.grad = torch.zeros(self.n_flat, dtype=torch.float32, device=self.device)
@@ -128,11 +121,11 @@ class A2CNetwork:
         #   block 0 = mu.weight (A rows), block 1 row 0 = value.weight, rows 1.. stay zero (zero gradient, Adam keeps 0)
         self.head_rows = self.actions_num
         self.wh_off = off; off += 2 * self.head_rows * u[-1]
-        off = _r4(off)
+        off = r4(off)
         self.bh_off = off; off += 2 * self.a_pitch
         self.wmu_off, self.wv_off = self.wh_off, self.wh_off + self.head_rows * u[-1]
         self.bmu_off, self.bv_off = self.bh_off, self.bh_off + self.a_pitch
-        self.n_flat = _r4(off)
+        self.n_flat = r4(off)
 
     def _w_view(self, buf, l, net):
         u, k = self.units[l], self.in_w[l]
@@ -255,7 +248,7 @@ class A2CNetwork:
                 # fp32-storage bf16 kernel -- there every operand is rounded to bf16 on its way into LDS and every output leaves
                 # bf16-representable -- at half the operand traffic, which is what bounded that kernel.
                 i16 = lambda r, c: torch.zeros(r, c, dtype=torch.int16, device=dev)
-                hp = _r32(self.head_rows)
+                hp = r32(self.head_rows)
                 ws["x16"] = i16(m, self.in_pitch)
                 ws["h16"] = [i16(m, 2 * uu) for uu in u]
                 ws["dz16"] = [i16(m, 2 * uu) for uu in u]

@@ -23,8 +23,7 @@ import torch
 from .. import kernels as K
 from .._lib import ACT_RELU, ACT_SILU, ACT_SILU_D
 from . import graph as G_
-from .graph import Linear, MlpGraph, ParamBook, init_linear_, r4
-from .network_z import _Replay
+from .graph import GraphModel, GraphNetwork, Linear
 
 
 def mcp_parameter_layout(units, num_prim, obs_size):
@@ -44,9 +43,8 @@ def mcp_parameter_layout(units, num_prim, obs_size):
     return out
 
 
-class AMPMCPNetwork:
+class AMPMCPNetwork(GraphNetwork):
     def __init__(self, params, *, actions_num, self_obs_size, task_obs_size, task_obs_size_detail, device="cuda:0", split_k=8):
-        self.device = torch.device(device)
         d = dict(task_obs_size_detail or {})
         self.num_prim = int(d.get("num_prim", 4))                                     # :39
         if not 1 <= self.num_prim <= 32:
@@ -54,41 +52,19 @@ class AMPMCPNetwork:
         if int(actions_num) != self.num_prim:
             raise ValueError(f"amp_mcp: the env's action is the {actions_num}-wide weight vector but task_obs_size_detail['num_prim'] = {self.num_prim} "
                              "(mu = the composer's output, amp_network_mcp_builder.py:81)")
-        if not params.get("separate", False):
-            raise NotImplementedError("separate: True required")
-        space = params["space"]["continuous"]
-        if not space.get("fixed_sigma", True):
+        if not params["space"]["continuous"].get("fixed_sigma", True):
             raise NotImplementedError("amp_mcp with fixed_sigma: False (sigma(a_out), amp_network_mcp_builder.py:85; no shipped config)")
         self.has_softmax = bool(params.get("has_softmax", True))                      # :33
         # params["ending_act"]: read by nothing in the reference (the trailing activation is unconditional) -- ignored
-        self.self_obs_size, self.task_obs_size = int(self_obs_size), int(task_obs_size)
-        self.obs_size = self.self_obs_size + self.task_obs_size
-        self.in_pitch = (self.obs_size + 31) // 32 * 32
-        self.actions_num = self.num_prim
-        self.a_pitch = r4(self.actions_num)
         self.units = [int(u) for u in params["mlp"]["units"]]
         if params["mlp"]["activation"] not in ("relu", "silu"):
             raise NotImplementedError(f"amp_mcp activation {params['mlp']['activation']!r}: relu / silu are built")
         self.act = K.ACTIVATIONS[params["mlp"]["activation"]]
-        si = space.get("sigma_init", {"val": 0.0})
-        self.sigma = torch.full((self.actions_num,), float(si.get("val", 0.0)), dtype=torch.float32, device=self.device)
-        self.split_k = split_k
-        self._graphs = {}
-        self.book = None
-        g = self._build(1)
-        self.book.finalize()
-        self.lins = g["lins"]
-        self.reset_parameters()
-        self.training = True
+        super().__init__(params, actions_num=actions_num, self_obs_size=self_obs_size, task_obs_size=task_obs_size, device=device, split_k=split_k)
 
     def _build(self, m, x=None):
-        first = self.book is None
-        if first:
-            self.book = ParamBook(self.device, self.split_k)
-        book = self.book if first else _Replay(self.book)
         U, P = self.units, self.num_prim
-        g = MlpGraph(book, m)
-        g.buffer("x", self.obs_size, tensor=x if x is not None else torch.zeros(m, self.in_pitch, device=self.device))
+        g, book = self._new_graph(m, x), self.book
         lins = {}
         # AMPBuilder.Network order: actor_mlp, critic_mlp, value, mu (network_builder.py:245-261), then the composer (amp_network_mcp_builder.py:41-51).
         # actor_mlp and mu are parameters only: eval_actor (:64-86) never calls them, so they get no activation buffers and no launches
@@ -97,26 +73,20 @@ class AMPMCPNetwork:
             lins["actor_mlp"].append(Linear(book, f"a2c_network.actor_mlp.{2 * i}", k, u, self.act))
             k = u
         names_c = [f"c{i + 1}" for i in range(len(U))]
-        lins["critic_mlp"] = g.mlp(book, "a2c_network.critic_mlp", "x", self.obs_size, U, self.act, names_c, tag="critic")
+        lins["critic_mlp"] = g.mlp("a2c_network.critic_mlp", "x", self.obs_size, U, self.act, names_c, tag="critic")
         g.buffer("value", 1)
         lins["value"] = g.linear(Linear(book, "a2c_network.value", U[-1], 1), names_c[-1], "value", grad_ranges=[(0, U[-1], self.act, names_c[-1], 0)], tag="critic")
         lins["mu"] = Linear(book, "a2c_network.mu", U[-1], P)
         # composer = Sequential(Linear, act, ..., Linear(units[-1], num_prim), act): the last layer is activated like the others
         names_p = [f"p{i + 1}" for i in range(len(U))] + ["h"]
-        lins["composer"] = g.mlp(book, "a2c_network.composer", "x", self.obs_size, U + [P], self.act, names_p, tag="composer")
+        lins["composer"] = g.mlp("a2c_network.composer", "x", self.obs_size, U + [P], self.act, names_p, tag="composer")
         if self.has_softmax:
             g.buffer("mu", P)
         return {"graph": g, "lins": lins}
 
-    def graph(self, m, x=None):
-        key = (m, x.data_ptr() if x is not None else 0)
-        if key in self._graphs:
-            return self._graphs[key]
-        g = self._build(m, x=x)["graph"]
-        out = {"g": g, "x": g.act_bufs["x"], "fwd_actor": g.forward_plan({"composer"}), "fwd_critic": g.forward_plan({"critic"}),
-               "bwd_actor": g.backward_plan({"composer"}), "bwd_critic": g.backward_plan({"critic"})}
-        self._graphs[key] = out
-        return out
+    def _plans(self, g):
+        return {"fwd_actor": g.forward_plan({"composer"}), "fwd_critic": g.forward_plan({"critic"}),
+                "bwd_actor": g.backward_plan({"composer"}), "bwd_critic": g.backward_plan({"critic"})}
 
     def unused_ranges(self):
         """Flat ranges of actor_mlp / mu: no pass writes their gradient slabs, the gradient reduce writes zeros there."""
@@ -130,89 +100,17 @@ class AMPMCPNetwork:
                     spans.append((lo, hi))
         return spans
 
-    # ------------------------------------------------------------------ parameters (reference names)
-    def state_dict(self, buf=None):
-        sd = {}
-        for p in self.book.params.values():
-            v = self.book.get(p.name, buf)
-            sd[p.name] = (v.reshape(-1) if p.name.endswith(".bias") else v).clone()
-        sd["a2c_network.sigma"] = self.sigma.clone()
-        return sd
 
-    def gradients(self):
-        sd = self.state_dict(self.book.grad)
-        sd.pop("a2c_network.sigma")
-        return sd
-
-    def load_state_dict(self, sd, strict=True):
-        for p in self.book.params.values():
-            if p.name not in sd:
-                if strict:
-                    raise KeyError(p.name)
-                continue
-            self.book.set(p.name, sd[p.name].to(self.device, torch.float32))
-        if "a2c_network.sigma" in sd:
-            self.sigma.copy_(sd["a2c_network.sigma"].to(self.device, torch.float32))
-
-    def reset_parameters(self, generator=None):
-        for group in self.lins.values():
-            for lin in (group if isinstance(group, list) else [group]):
-                init_linear_(self.book, lin, generator)
-
-    def parameters_count(self):
-        return self.book.n_flat
-
-    def train(self, mode=True):
-        self.training = mode
-        return self
-
-    def eval(self):
-        return self.train(False)
-
-
-class AMPMCPModel:
+class AMPMCPModel(GraphModel):
     """The model interface CommonAgent / AMPAgent drive (workspace / forward / eval_critic / backward over one flat buffer)."""
+    network = AMPMCPNetwork
 
-    def __init__(self, params, *, actions_num, self_obs_size, task_obs_size, task_obs_size_detail, device, split_k=8):
-        self.net = AMPMCPNetwork(params, actions_num=actions_num, self_obs_size=self_obs_size, task_obs_size=task_obs_size,
-                                 task_obs_size_detail=task_obs_size_detail, device=device, split_k=split_k)
-        n = self.net
-        self.device, self.book = n.device, n.book
-        self.flat, self.grad, self.n_flat = n.book.flat, n.book.grad, n.book.n_flat
-        self.sigma, self.a_pitch, self.in_pitch, self.actions_num = n.sigma, n.a_pitch, n.in_pitch, n.actions_num
-        self.training = True
-        self._ws = {}
-
-    def parameters_count(self):
-        return self.n_flat
-
-    def train(self, mode=True):
-        self.training = mode
-        return self
-
-    def eval(self):
-        return self.train(False)
-
-    def is_rnn(self):
-        return False
-
-    def state_dict(self):
-        return self.net.state_dict()
-
-    def load_state_dict(self, sd, strict=True):
-        self.net.load_state_dict(sd, strict)
-
-    def workspace(self, m, train):
-        ws = self._ws.get(m)
-        if ws is None:
-            G = self.net.graph(m)
-            g, P = G["g"], self.actions_num
-            # without the softmax mu IS the composer's activated output (:81)
-            mu = g.act_bufs["mu" if self.net.has_softmax else "h"]
-            ws = {"G": G, "g": g, "x": G["x"], "mu": mu[:, :P], "val": g.act_bufs["value"][:, :1],
-                  "dmu": torch.zeros(m, self.a_pitch, device=self.device)[:, :P], "dval": g.grad("value")[:, :1]}
-            self._ws[m] = ws
-        return ws
+    def _fill_workspace(self, ws, m):
+        g, P = ws["g"], self.actions_num
+        # without the softmax mu IS the composer's activated output (:81)
+        ws["mu"] = g.act_bufs["mu" if self.net.has_softmax else "h"][:, :P]
+        ws["dmu"] = torch.zeros(m, self.a_pitch, device=self.device)[:, :P]
+        ws["unused"] = self.net.unused_ranges()
 
     def forward_actor(self, ws, m):
         ws["G"]["fwd_actor"].run()
@@ -226,8 +124,6 @@ class AMPMCPModel:
 
     def eval_critic(self, ws, m):
         ws["G"]["fwd_critic"].run()
-
-    supports_fused_sqnorm = True
 
     def backward(self, ws, m, grad_scale=1.0, sq_partials=None, on_bucket=None):
         """d loss / d (mu, value) are in ws['dmu'] / ws['dval'].  The composer's tail (softmax, last activation) is one launch that leaves
@@ -243,8 +139,4 @@ class AMPMCPModel:
                             aux=aux, activation=act)
         ws["G"]["bwd_actor"].run()
         ws["G"]["bwd_critic"].run()
-        if "untouched" not in ws:
-            ws["untouched"] = net.unused_ranges()
-        if not self.book.reduce_grads(grad_scale, untouched=ws["untouched"], sq_partials=sq_partials) and sq_partials is not None:
-            K.sqnorm_partial(self.book.grad, self.book.n_flat, sq_partials)
-        return self.book.grad
+        return self._reduce(grad_scale, ws["unused"], sq_partials)

@@ -78,7 +78,7 @@ class PnnTeacher:
             for k in range(num_prim):
                 sizes = _layer_sizes(pm, f"a2c_network.pnn.actors.{k}")
                 units = [s[0] for s in sizes[:-1]]
-                self._lins += g.mlp(self.book, f"a2c_network.pnn.actors.{k}", "x", self.in_dim, units, act, [f"p{k}h{i}" for i in range(len(units))],
+                self._lins += g.mlp(f"a2c_network.pnn.actors.{k}", "x", self.in_dim, units, act, [f"p{k}h{i}" for i in range(len(units))],
                                     final_linear=sizes[-1][0], final_dst="acts", final_dst_col=k * self.a_pitch)
         self._clins = []
         if cm is not None:
@@ -86,7 +86,7 @@ class PnnTeacher:
             cunits = [s[0] for s in csizes]
             if cunits[-1] != num_prim:
                 raise ValueError(f"composer emits {cunits[-1]} weights for {num_prim} primitives")
-            self._clins = g.mlp(self.book, "a2c_network.composer", "x", self.in_dim, cunits, act, [f"ch{i}" for i in range(len(cunits) - 1)] + ["w"])
+            self._clins = g.mlp("a2c_network.composer", "x", self.in_dim, cunits, act, [f"ch{i}" for i in range(len(cunits) - 1)] + ["w"])
         self.book.finalize(trainable=False)
         for lin in self._lins:
             self.book.set(lin.w.name, pm[lin.w.name])
