@@ -294,7 +294,7 @@ def terrain_functions():
     """HumanoidTraj / HumanoidPedestrianTerrain (README: the terrain-traversal PULSE command): the TorchScript functions
     compute_location_observations (with the upright flag), compute_location_reward(_fuzzy), quat_apply_yaw and the terrain variant of
     compute_humanoid_reset (humanoid_pedestrian_terrain.py:1476-1646), HumanoidTraj's compute_humanoid_reset (humanoid_traj.py:256-300),
-    the METHODS get_heights / get_center_heights (:690-772), _fetch_traj_samples (humanoid_traj.py:196-211) and Terrain.world_points_to_map /
+    the METHODS get_heights / get_center_heights (:690-772), _compute_task_obs (:385-439), _fetch_traj_samples (humanoid_traj.py:196-211) and Terrain.world_points_to_map /
     sample_height_points (:1191-1270), plus the TrajGenerator class (phc/utils/traj_generator.py; its ``np.int`` needs numpy < 1.24, so
     the name is supplied)."""
     if "terrain" in _cache:
@@ -316,7 +316,7 @@ def terrain_functions():
         exec(compile(text, f"<reference:humanoid_pedestrian_terrain.py:{name}>", "exec"), ns)
         out["terrain_" + name if name == "compute_humanoid_reset" else name] = ns[name]
     ns["remove_base_rot"] = env_functions()["remove_base_rot"]
-    for cls, names in (("HumanoidPedestrianTerrain", ["get_heights", "get_center_heights"]), ("Terrain", ["world_points_to_map", "sample_height_points"])):
+    for cls, names in (("HumanoidPedestrianTerrain", ["get_heights", "get_center_heights", "_compute_task_obs"]), ("Terrain", ["world_points_to_map", "sample_height_points"])):
         for name, text in _extract(tf, names, methods_of=cls).items():
             exec(compile(text, f"<reference:{cls}.{name}>", "exec"), ns)
             out[f"{cls}.{name}"] = ns[name]

@@ -140,7 +140,7 @@ def strike_reset(reset_buf, progress_buf, contact_buf, contact_body_ids, rigid_b
 #   traj_location_observations   compute_location_observations      humanoid_pedestrian_terrain.py:1587-1616
 #   location_reward(_fuzzy)      compute_location_reward(_fuzzy)    :1619-1646
 #   terrain_reset / traj_reset   compute_humanoid_reset             :1476-1531 / humanoid_traj.py:256-300
-#   sample_heights               Terrain.world_points_to_map + sample_height_points (no groups)   :1191-1270
+#   world_points_to_cells / sample_heights   Terrain.world_points_to_map / + sample_height_points (no groups)   :1191-1270
 #   terrain_heights / terrain_center_heights   get_heights / get_center_heights   :690-772
 #   terrain_task_obs             _compute_task_obs          :384-440
 # ---------------------------------------------------------------------------------------------------------------------
@@ -268,11 +268,17 @@ def quat_apply(a, b):
 def sample_heights(heightsamples, points, horizontal_scale, vertical_scale):
     """Terrain.world_points_to_map + sample_height_points without groups: integer cell (truncation), clip, min of the cell and its
     diagonal neighbour, scaled.  heightsamples: (rows, cols) int16; points (B, P, 3)."""
+    px, py = world_points_to_cells(heightsamples, points, horizontal_scale)
+    h = torch.min(heightsamples[px, py], heightsamples[px + 1, py + 1])
+    return (h * vertical_scale).view(points.shape[0], -1)
+
+
+def world_points_to_cells(heightsamples, points, horizontal_scale):
+    """Terrain.world_points_to_map (:1191-1197): truncation towards zero, then the clip to [0, size - 2] in x and y; flat (B * P,) each."""
     p = (points / horizontal_scale).long()
     px = torch.clip(p[:, :, 0].reshape(-1), 0, heightsamples.shape[0] - 2)
     py = torch.clip(p[:, :, 1].reshape(-1), 0, heightsamples.shape[1] - 2)
-    h = torch.min(heightsamples[px, py], heightsamples[px + 1, py + 1])
-    return (h * vertical_scale).view(points.shape[0], -1)
+    return px, py
 
 
 def terrain_sample_points(sensor_states, height_points, upright=True):

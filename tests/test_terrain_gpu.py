@@ -20,22 +20,28 @@ def g(k, dev):
     return torch.from_numpy(Z[k]).to(dev)
 
 
-def explain_height_differences(got, want, rb, upright, tol=1e-5, hs=None, hp=None, cp=None):
+def explain_height_differences(got, want, rb, upright, tol=1e-5, hs=None, hp=None, cp=None, sensor_body=None, use_center_height=True,
+                               horizontal_scale=0.1, vertical_scale=0.005, height_meas_scale=5.0):
     """The height-map gather is index work: a device sample may only differ from the reference's where the sample's world point sits on a
     cell EDGE (the device's sinf / cosf / atan2f of the heading differ from the CPU libm by an ulp, so the rotated point moves by a few
     ulps and truncation picks the neighbouring cell).  For every differing sample this proves exactly that: (a) the point's cell
     coordinate is within 8 ulps of an integer in x or y, and (b) the device's value is the reference formula evaluated with the cell index
-    shifted by one across that edge.  Returns the number of such samples; raises on any difference it cannot explain."""
+    shifted by one across that edge.  Returns the number of such samples; raises on any difference it cannot explain.
+    ``sensor_body`` (default: the head), the map ``hs``, the grids ``hp`` / ``cp``, the scales and ``use_center_height`` (False: heights are
+    taken relative to the root's z) are those of the launch under test."""
     pad3 = lambda t: torch.cat([t, torch.zeros(t.shape[0], 1)], 1) if t.shape[1] == 2 else t
     hs = torch.from_numpy(Z["heightsamples"]) if hs is None else hs
     hp = pad3(torch.from_numpy(Z["height_points"]) if hp is None else hp)
     cp = pad3(torch.from_numpy(Z["center_points"]) if cp is None else cp)
     rbc = rb.cpu()
-    head = syn.SMPL_BODY_NAMES.index("Head")
-    sensor, root = rbc[:, head, 0:7], rbc[:, 0]
-    pts = TO.terrain_sample_points(sensor, hp, upright)                      # (n, 1024, 3) fp32, the reference's arithmetic
-    u = pts[..., :2] / 0.1                                                   # cell coordinates as the reference forms them
-    center = TO.terrain_center_heights(hs, root, cp, 0.1, 0.005, upright).mean(dim=-1, keepdim=True)
+    sensor_body = syn.SMPL_BODY_NAMES.index("Head") if sensor_body is None else sensor_body
+    sensor, root = rbc[:, sensor_body, 0:7], rbc[:, 0]
+    pts = TO.terrain_sample_points(sensor, hp, upright)                      # (n, points, 3) fp32, the reference's arithmetic
+    u = pts[..., :2] / horizontal_scale                                      # cell coordinates as the reference forms them
+    if use_center_height:
+        center = TO.terrain_center_heights(hs, root, cp, horizontal_scale, vertical_scale, upright).mean(dim=-1, keepdim=True)
+    else:
+        center = root[:, 2:3]                                                # _compute_task_obs :427: the root's own height
     bad = ((got.cpu() - want.cpu()).abs() > tol).nonzero()
     explained = 0
     for e, k in bad.tolist():
@@ -48,8 +54,8 @@ def explain_height_differences(got, want, rb, upright, tol=1e-5, hs=None, hp=Non
             for dy in ((-1, 0, 1) if near[1] else (0,)):
                 px = min(max(ix + dx, 0), hs.shape[0] - 2)
                 py = min(max(iy + dy, 0), hs.shape[1] - 2)
-                h = min(int(hs[px, py]), int(hs[px + 1, py + 1])) * 0.005
-                cands.append(float(np.clip(np.float32(center[e, 0].item()) - np.float32(h), -3, 3) * 5.0))
+                h = min(int(hs[px, py]), int(hs[px + 1, py + 1])) * vertical_scale
+                cands.append(float(np.clip(np.float32(center[e, 0].item()) - np.float32(h), -3, 3) * height_meas_scale))
         assert min(abs(got[e, k].item() - c) for c in cands) <= 2e-5, f"env {e} sample {k}: {got[e, k].item()} matches no neighbouring cell {cands}"
         explained += 1
     return explained
