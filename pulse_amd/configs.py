@@ -64,6 +64,14 @@ NETWORK_MCP = {           # phc/data/cfg/learning/im_mcp.yaml:11-45 (network: am
     "disc": {"units": [1024, 512], "activation": "relu", "initializer": {"name": "default"}},
 }
 
+NETWORK_PNN = {           # phc/data/cfg/learning/im_pnn.yaml:11-43 (network: amp_pnn)
+    "name": "amp_pnn", "separate": True, "discrete": False,
+    "space": {"continuous": {"mu_activation": "None", "sigma_activation": "None", "mu_init": {"name": "default"},
+                             "sigma_init": {"name": "const_initializer", "val": -2.9}, "fixed_sigma": True, "learn_sigma": False}},
+    "mlp": {"units": [1024, 512], "activation": "relu", "d2rl": False, "initializer": {"name": "default"}},
+    "disc": {"units": [1024, 512], "activation": "relu", "initializer": {"name": "default"}},
+}
+
 # phc/data/cfg/env/phc_kp_mcp_iccv.yaml:23-80 (task HumanoidImMCPGetup): the switches this package reads; ``models`` is the synthetic PNN
 # checkpoint make_env builds (the shipped file names output/phc_kp_pnn_iccv/Humanoid.pth)
 ENV_MCP = {"fut_tracks": False, "obs_v": 7, "has_pnn": True, "fitting": True, "num_prim": 4, "training_prim": 2, "actors_to_load": 4,
@@ -112,6 +120,21 @@ CONFIGS = {
     "mcp": {"num_envs": 1536, "horizon_length": 32, "minibatch_size": 16384, "network": "amp_mcp", "env": "mcp", "agent": "amp"},
     "mcp_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_mcp", "env": "mcp", "agent": "amp",
                   "units": [256, 128]},
+    # PHC's first stage (learning=im_pnn, env=phc_kp_pnn_iccv): column training_prim of num_prim progressive columns trains, the AMP
+    # discriminator beside it.  ``pnn`` is cfg5's shape, env, discriminator and mixed_precision with the amp_pnn network: the same launches
+    "pnn": {"num_envs": 8192, "horizon_length": 32, "minibatch_size": 16384, "units": [1024, 512], "network": "amp_pnn", "env": "amp", "agent": "amp",
+            "extra": {"enable_disc": True, "mixed_precision": True},
+            "env_overrides": {"num_prim": 4, "training_prim": 0, "actors_to_load": 0, "has_lateral": False}},
+    "pnn_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "units": [512, 512], "network": "amp_pnn", "env": "amp", "agent": "amp",
+                  "extra": {"enable_disc": True, "amp_minibatch_size": 64, "amp_obs_demo_buffer_size": 4096, "amp_replay_buffer_size": 4096,
+                            "amp_batch_size": 128},
+                  "env_overrides": {"num_prim": 4, "training_prim": 0, "actors_to_load": 0, "has_lateral": False}},
+    # a later column with lateral links into it (graph path, fp32): the concatenated second layer reads 3 x 36 = 108 columns
+    "pnn_lateral_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "units": [36, 32], "network": "amp_pnn", "env": "amp",
+                          "agent": "amp",
+                          "extra": {"enable_disc": True, "amp_minibatch_size": 64, "amp_obs_demo_buffer_size": 4096, "amp_replay_buffer_size": 4096,
+                                    "amp_batch_size": 128},
+                          "env_overrides": {"num_prim": 3, "training_prim": 2, "actors_to_load": 2, "has_lateral": True}},
     # small shapes of the same graphs for tests
     "cfg3_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_z", "env": "vae", "agent": "amp",
                    "extra": {"use_seq_rl": True}},
@@ -138,6 +161,10 @@ def agent_config(name, **overrides):
         net = copy.deepcopy(NETWORK_MCP)
         if "units" in c:
             net["mlp"]["units"] = list(c["units"])
+    elif c.get("network") == "amp_pnn":
+        net = copy.deepcopy(NETWORK_PNN)
+        if "units" in c:
+            net["mlp"]["units"] = list(c["units"])
     elif c.get("network") == "amp_z_reader":
         net = copy.deepcopy(NETWORK_Z_READER)
         if "units" in c:
@@ -150,6 +177,7 @@ def agent_config(name, **overrides):
     cfg.update(c.get("extra", {}))
     cfg.update(overrides)
     cfg["_env_kind"], cfg["_agent_kind"], cfg["_humanoid"] = c.get("env", "im"), c.get("agent", "common"), c.get("humanoid", "smpl")
+    cfg["_env_overrides"] = dict(c.get("env_overrides", {}))          # cfg["env"] keys the config itself sets (amp_pnn reads its four switches there)
     return cfg, c["num_envs"]
 
 
@@ -248,7 +276,7 @@ def make_agent(name="cfg2", device="cuda:0", seed=1234, rank=0, rollout=None, re
     if num_envs_override is not None:
         num_envs = int(num_envs_override)
     vec_env, rollout = make_env(num_envs, cfg["horizon_length"], device, seed=seed, rank=rank, rollout=rollout, env_kind=cfg["_env_kind"],
-                                reference=reference, env_overrides=env_overrides, humanoid=humanoid if humanoid is not None else cfg["_humanoid"])
+                                reference=reference, env_overrides=dict(cfg["_env_overrides"], **(env_overrides or {})) or None, humanoid=humanoid if humanoid is not None else cfg["_humanoid"])
     cfg.update({"vec_env": vec_env, "device": device, "seed": seed})
     cls = AMPAgent if cfg["_agent_kind"] == "amp" else CommonAgent
     return cls("pulse_amd", cfg), rollout

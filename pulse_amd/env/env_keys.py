@@ -58,7 +58,8 @@ _LOAD = ("consumed where the reference opens its motion file and builds the libr
          "over a built MotionLib -- MotionLib.from_motion_data takes the loaded data dict and min_length as arguments")
 _VIEW = "viewer / debug drawing (out of scope)"
 _DEAD = "the reference stores it in an attribute that nothing on the training path reads"
-_TEACH = "steers which PNN column trains / loads (amp_network_pnn_builder.py): PNN training is not built, the primitives come frozen from a checkpoint"
+_TEACH = ("steers which PNN column trains / loads (amp_network_pnn_builder.py:36-38): read by the amp_pnn network (learning/network_pnn.py) from "
+          "cfg['env'], not by the env")
 
 INERT = {
     "task": "selects the task class (utils/parse_task.py:57-70): the caller instantiates the class",

@@ -375,6 +375,11 @@ class AMPAgent(CommonAgent):
         else:
             model = {k: v for k, v in model.items() if "._disc_" not in k}
         super().set_full_state_weights(dict(weights, model=model))
+        if self.enable_disc and self._optimizer_restarted:
+            # amp_pnn on its next primitive: the one Adam step counter both flat buffers share restarts, so the discriminator's moments (whose
+            # bias correction it drives) restart with it; its weights and normaliser are kept
+            self.disc_exp_avg.zero_()
+            self.disc_exp_avg_sq.zero_()
         if self.save_kin_info and "kin_optimizer" in weights and "exp_avg" in weights["kin_optimizer"]:
             self.kin_exp_avg.copy_(weights["kin_optimizer"]["exp_avg"])
             self.kin_exp_avg_sq.copy_(weights["kin_optimizer"]["exp_avg_sq"])

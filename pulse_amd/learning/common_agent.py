@@ -203,6 +203,13 @@ class CommonAgent:
             return {"amp_z": AMPZModel, "amp_sept": AMPSeptModel, "amp_mcp": AMPMCPModel}[name](
                 params, actions_num=net_config["actions_num"], self_obs_size=task.get_self_obs_size(), task_obs_size=task.get_task_obs_size(),
                 task_obs_size_detail=task.get_task_obs_size_detail(), device=self.ppo_device, split_k=int(self.config.get("split_k", 8)), **extra)
+        if name == "amp_pnn":
+            # AMPPNNBuilder.Network (amp_network_pnn_builder.py:25-89): num_prim progressive columns, column training_prim trains.  The four
+            # switches come from cfg["env"] with the reference's defaults (humanoid_im.py:503-506); without laterals the model IS the actor /
+            # critic pair on A2CNetwork's launch plans (network_pnn.py)
+            from .network_pnn import build_pnn_model
+            return build_pnn_model(params, task=self.vec_env.env.task, actions_num=net_config["actions_num"], input_shape=net_config["input_shape"],
+                                   device=self.ppo_device, split_k=int(self.config.get("split_k", 8)), mixed_precision=self.mixed_precision)
         if name == "amp_z_reader":
             # AMPZReaderBuilder.Network (amp_network_z_reader_builder.py:21-57) IS AMPBuilder.Network -- the plain actor / critic MLP
             # whose 32-d "action" is the latent a frozen PULSE decoder turns into joint targets inside env.step -- unless
@@ -799,6 +806,8 @@ class CommonAgent:
     def get_full_state_weights(self):
         state = {"model": self.model.state_dict(), "epoch": self.epoch_num, "frame": self.frame,
                  "optimizer": {"exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(), "step": self.optimizer_step}}
+        if hasattr(self.model, "training_prim"):                       # amp_pnn: which column the flat buffer's actor slots (and the moments) belong to
+            state["training_prim"] = int(self.model.training_prim)
         if self.normalize_input:
             state["running_mean_std"] = self.running_mean_std.state_dict()
         if self.normalize_value:
@@ -809,7 +818,16 @@ class CommonAgent:
         self.model.load_state_dict(weights["model"])
         self.epoch_num = weights.get("epoch", 0)
         self.frame = weights.get("frame", 0)
-        if "optimizer" in weights and "exp_avg" in weights["optimizer"]:
+        tp = getattr(self.model, "training_prim", None)
+        self._optimizer_restarted = tp is not None and int(weights.get("training_prim", tp)) != int(tp)
+        if self._optimizer_restarted:
+            # amp_pnn moving on to the next primitive: the model (every column) is taken, but the flat buffer now holds another column, so the
+            # stored moments describe other parameters -- the policy optimiser starts over (the reference's torch Adam would
+            # keep the critic's moments)
+            self.exp_avg.zero_()
+            self.exp_avg_sq.zero_()
+            self.optimizer_step = 0
+        elif "optimizer" in weights and "exp_avg" in weights["optimizer"]:
             self.exp_avg.copy_(weights["optimizer"]["exp_avg"])
             self.exp_avg_sq.copy_(weights["optimizer"]["exp_avg_sq"])
             self.optimizer_step = int(weights["optimizer"]["step"])
