@@ -28,12 +28,8 @@ import math
 
 import torch
 
-from .. import _lib
 from .._lib import MotionStateArgs
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+from .._marshal import Filler, launch, mask_u8
 
 
 def _round4(n):
@@ -406,39 +402,19 @@ class MotionLib:
               reset=None, fields=None):
         """One launch.  Times either given (``motion_times``) or built in-kernel from the episode clock
         ((progress + step_shift) * dt + start_times + start_offsets).  ``out``: dict of preallocated outputs to reuse."""
-        lib = _lib.load()
         dev = self._device
-        ids = motion_ids
-        if ids.dtype != torch.int64 or not ids.is_cuda:
-            raise TypeError("motion_ids: int64 device tensor expected")
-        ids = ids.contiguous()
-        ne = ids.numel()                                   # per-env arrays
+        P = Filler(not_gpu=TypeError)                      # (this method answers a tensor of the wrong kind, device or dtype with TypeError)
+        f32 = torch.float32
+        ne = motion_ids.numel()                            # per-env arrays
         n = ne if motion_times is not None else ne * int(time_steps)
         j, nd = self.num_bodies, self.num_dof
-        keep = [ids]
-
-        def f32(t, name, shape):
-            if t is None:
-                return None
-            if t.dtype != torch.float32 or not t.is_cuda:
-                raise TypeError(f"{name}: float32 device tensor expected")
-            t = t.contiguous()
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
-            keep.append(t)
-            return t
-
         a = MotionStateArgs()
         self.fill_tables(a.tab)
-        a.n, a.motion_ids = n, ids.data_ptr()
+        a.n, a.motion_ids = n, P(motion_ids, "motion_ids", torch.int64)
         if reset is not None:
             # reset mode (include/pulse_hip.h 2b): masked envs get a new start time and their reference state in one launch
-            m = reset["mask"]
-            m = (m.view(torch.uint8) if m.dtype == torch.bool else m).contiguous()
-            keep.append(m)
-            a.reset_mask, a.step_shift, a.dt = m.data_ptr(), int(step_shift), float(dt)
-            ph = f32(reset.get("phase"), "reset.phase", (ne,))
-            a.reset_phase = ph.data_ptr() if ph is not None else None
+            a.reset_mask, a.step_shift, a.dt = P(mask_u8(reset["mask"]), "reset.mask", torch.uint8), int(step_shift), float(dt)
+            a.reset_phase = P(reset.get("phase"), "reset.phase", f32, (ne,))
             a.reset_time_interval = int(bool(reset.get("time_interval", False)))
             for field, key, dt_ in (("reset_start_times", "start_times", torch.float32), ("reset_progress", "progress", torch.int64),
                                     ("reset_clear0", "clear0", torch.int64), ("reset_clear1", "clear1", torch.int64),
@@ -449,22 +425,16 @@ class MotionLib:
                     if t_.dtype != dt_ or not t_.is_contiguous() or t_.numel() != (3 * ne if key == "zero_global_offset" else ne):
                         raise TypeError(f"reset.{key}: contiguous {dt_} tensor of {ne} elements expected")
                     setattr(a, field, t_.data_ptr())
-            so = f32(start_offsets, "start_offsets", (ne,))
-            a.start_offsets = so.data_ptr() if so is not None else None
+            a.start_offsets = P(start_offsets, "start_offsets", f32, (ne,))
         elif motion_times is not None:
-            a.motion_times = f32(motion_times, "motion_times", (n,)).data_ptr()
+            a.motion_times = P(motion_times, "motion_times", f32, (n,))
         else:
-            if progress is None or progress.dtype != torch.int64:
+            if progress is None:
                 raise TypeError("query needs motion_times or an int64 progress tensor")
-            progress = progress.contiguous()
-            keep.append(progress)
-            a.progress, a.step_shift, a.dt = progress.data_ptr(), int(step_shift), float(dt)
+            a.progress, a.step_shift, a.dt = P(progress, "progress", torch.int64), int(step_shift), float(dt)
             a.time_steps, a.traj_dt = int(time_steps), float(traj_dt)
-            st, so = f32(start_times, "start_times", (ne,)), f32(start_offsets, "start_offsets", (ne,))
-            a.start_times = st.data_ptr() if st is not None else None
-            a.start_offsets = so.data_ptr() if so is not None else None
-        off = f32(offset, "offset", (ne, 3))
-        a.offset = off.data_ptr() if off is not None else None
+            a.start_times, a.start_offsets = P(start_times, "start_times", f32, (ne,)), P(start_offsets, "start_offsets", f32, (ne,))
+        a.offset = P(offset, "offset", f32, (ne, 3))
         res = {} if out is None else out
         e = lambda key, *shape, dtype=torch.float32: res[key] if key in res else res.setdefault(key, torch.empty(*shape, dtype=dtype, device=dev))
         if root_only:
@@ -484,7 +454,7 @@ class MotionLib:
         if with_frames:
             a.frame_idx0, a.frame_idx1 = e("frame_idx0", n, dtype=torch.int64).data_ptr(), e("frame_idx1", n, dtype=torch.int64).data_ptr()
             a.blend = e("blend", n).data_ptr()
-        _lib.check(lib.pulse_motion_state(ctypes.byref(a), _stream()), "pulse_motion_state")
+        launch("pulse_motion_state", ctypes.byref(a))
         return res
 
     def get_motion_state(self, motion_ids, motion_times, offset=None, out=None):

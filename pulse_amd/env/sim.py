@@ -9,10 +9,14 @@ that "physics" overwrites every step, dof force / velocity tensors, a PD-target 
 ``RecordedMotion`` plays the role of ``MotionLibBase.get_motion_state``
 (phc/utils/motion_lib_base.py:434-517) for the two evaluations per step (time t and t+1).
 """
+import ctypes
+
 import torch
 
 from .. import kernels as K
 from .. import synthetic as syn
+from .._lib import PdSimArgs
+from .._marshal import Filler, launch, ptr
 
 
 class RecordedRollout:
@@ -228,21 +232,17 @@ class PdSim(KinematicSim):
         self._reset_mask = torch.zeros(num_envs, dtype=torch.uint8, device=device)
 
     def simulate_and_refresh(self):
-        from .. import _lib
         self.frame = (self.frame + 1) % self.bank_frames
         t, c = self._target, syn.PD_SIM
-        a = _lib.PdSimArgs()
+        a, P = PdSimArgs(), Filler()
         a.num_envs, a.num_bodies = self.num_envs, self.skeleton["num_bodies"]
-        a.target_rb, a.target_dof_pos, a.target_dof_vel = t["rb_records"].data_ptr(), t["dof_pos"].data_ptr(), t["dof_vel"].data_ptr()
-        act = self.pd_targets.contiguous()
-        a.action, a.noise_acc = act.data_ptr(), self.bank["acc"][self.frame].data_ptr()
-        a.sag, a.lever_dir = self._sag.data_ptr(), self._lever_dir.data_ptr()
+        a.target_rb, a.target_dof_pos, a.target_dof_vel = ptr(t["rb_records"]), ptr(t["dof_pos"]), ptr(t["dof_vel"])
+        a.action, a.noise_acc = P(self.pd_targets, "pd_targets"), ptr(self.bank["acc"][self.frame])
+        a.sag, a.lever_dir = ptr(self._sag), ptr(self._lever_dir)
         a.kp, a.kd, a.dt, a.action_scale, a.lever, a.substeps = c["kp"], c["kd"], self.dt, c["action_scale"], c["lever"], c["substeps"]
-        a.err, a.err_vel = self.err.data_ptr(), self.err_vel.data_ptr()
-        a.rb, a.dof_pos, a.dof_vel, a.dof_force = (self.rigid_body_state.data_ptr(), self.dof_pos.data_ptr(), self.dof_vel.data_ptr(),
-                                                   self.dof_force.data_ptr())
-        import ctypes
-        _lib.check(_lib.load().pulse_pd_sim_step(ctypes.byref(a), torch.cuda.current_stream().cuda_stream), "pulse_pd_sim_step")
+        a.err, a.err_vel = ptr(self.err), ptr(self.err_vel)
+        a.rb, a.dof_pos, a.dof_vel, a.dof_force = ptr(self.rigid_body_state), ptr(self.dof_pos), ptr(self.dof_vel), ptr(self.dof_force)
+        launch("pulse_pd_sim_step", ctypes.byref(a))
 
     def on_reset(self, mask):
         """Reference-state init of the masked envs (HumanoidIm.reset_masked wrote their state): the error states restart at zero."""

@@ -3,33 +3,22 @@
 Same rules as ``ops.py``: GPU tensors only, enqueue on torch's current stream, no fallback.
 """
 import ctypes
+import functools
 import os
 
 import torch
 
 from . import _lib
 from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, EPI_BIAS_ACT, GEMM_RED_CONTIG, GemmDesc, PpoLossArgs
-from .ops import _dev, _ptr, _stream
+from ._marshal import b16 as _b16, entry as _entry, launch as _launch, ptr, rows2d, stream as _stream
 
 ACTIVATIONS = {"None": ACT_NONE, "none": ACT_NONE, None: ACT_NONE, "relu": ACT_RELU, "silu": ACT_SILU}
 
-
-def _p(t):
-    return t.data_ptr() if t is not None else None
-
-
-def _chk(t, name, dtype=torch.float32, contiguous=True):
-    """Raw-pointer arguments: wrong dtype / device / layout would be silently re-interpreted by the kernel (e.g. uint8 dones read as
-    int64), so they are rejected here.  None passes through (optional arguments)."""
-    if t is None:
-        return None
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise TypeError(f"{name}: expected a CUDA tensor, got {type(t).__name__} on {getattr(t, 'device', None)}")
-    if t.dtype != dtype and not (dtype == torch.uint8 and t.dtype == torch.bool):
-        raise TypeError(f"{name}: expected dtype {dtype}, got {t.dtype}")
-    if contiguous and t.numel() > 0 and t.stride(-1) != 1:
-        raise ValueError(f"{name}: innermost stride must be 1, got strides {tuple(t.stride())}")
-    return t.data_ptr()
+# pointer of an optional tensor; given a name, the tensor is validated first (unit inner stride unless unit_stride=False).  In this module a
+# tensor that is not on the GPU is a TypeError.
+_p = functools.partial(ptr, unit_stride=True, not_gpu=TypeError)
+_rows = functools.partial(rows2d, not_gpu=TypeError)
+_I16, _I64, _F64 = torch.int16, torch.int64, torch.float64
 
 
 class GemmProfiler:
@@ -82,24 +71,19 @@ def make_gemm_desc(A, B, C, *, M, N, K, lda, ldb, ldc, a_layout=GEMM_RED_CONTIG,
     ``relu_mask``: int32 tensor (alloc_relu_mask) -- a relu forward records the sign bits there, a relu-grad launch with aux=None reads them
     (pulse_hip.h: pulse_gemm_desc.relu_mask); ld_mask / stride_mask / mask_off in 32-bit words."""
     d = GemmDesc()
-    d.A = A.data_ptr() + 4 * a_off
-    d.B = B.data_ptr() + 4 * b_off
-    d.C = C.data_ptr() + 4 * c_off
-    d.C2 = (C2.data_ptr() + 4 * c2_off) if C2 is not None else None
-    d.bias = (bias.data_ptr() + 4 * bias_off) if bias is not None else None
-    d.aux = (aux.data_ptr() + 4 * aux_off) if aux is not None else None
+    d.A, d.B, d.C = _p(A, off=a_off), _p(B, off=b_off), _p(C, off=c_off)
+    d.C2, d.bias, d.aux = _p(C2, off=c2_off), _p(bias, off=bias_off), _p(aux, off=aux_off)
     d.M, d.N, d.K = M, N, K
     d.lda, d.ldb, d.ldc, d.ldc2, d.ldaux = lda, ldb, ldc, ldc2, ldaux
     d.a_layout, d.b_layout, d.batch = a_layout, b_layout, batch
     d.stride_a, d.stride_b, d.stride_c, d.stride_c2 = stride_a, stride_b, stride_c, stride_c2
     d.stride_bias, d.stride_aux = stride_bias, stride_aux
     d.split_k, d.split_stride, d.activation, d.epilogue = split_k, split_stride, activation, epilogue
-    d.rowsum = (rowsum.data_ptr() + 4 * rowsum_off) if rowsum is not None else None
-    d.stride_rowsum = stride_rowsum
+    d.rowsum, d.stride_rowsum = _p(rowsum, off=rowsum_off), stride_rowsum
     if relu_mask is not None:
         if relu_mask.dtype != torch.int32:
             raise TypeError("relu_mask must be an int32 tensor (alloc_relu_mask)")
-        d.relu_mask, d.ld_mask, d.stride_mask = relu_mask.data_ptr() + 4 * mask_off, int(ld_mask), int(stride_mask)
+        d.relu_mask, d.ld_mask, d.stride_mask = _p(relu_mask, None, torch.int32, mask_off), int(ld_mask), int(stride_mask)
     # bf16 MFMA with fp32 storage (bf16 autocast over fp32 master weights); split-K slabs are partial sums and stay unrounded
     x3 = (not compute_bf16) and (f32_mode or F32_MODE) == "x3"
     d.compute_type = _lib.GEMM_COMPUTE_BF16 if compute_bf16 else (_lib.GEMM_COMPUTE_F32X3 if x3 else _lib.GEMM_COMPUTE_F32)
@@ -183,19 +167,25 @@ def dw_split_b16(M, N, batch, max_split):
     return dw_split(tm * ((N + 127) // 128) * batch, max_split, fill=256)
 
 
+def _launch_desc(name, d, flops, tag, stream, retag=None):
+    """One GEMM launch of entry ``name``; with the profiler on, bracketed by an event pair and recorded under ``tag`` (``retag(tag)``, asked
+    after the launch, when the entry can say more about what served it)."""
+    if not PROFILER.enabled:
+        return _launch(name, ctypes.byref(d), st=stream)
+    ev0, ev1 = PROFILER._event(), PROFILER._event()
+    ev0.record()
+    _launch(name, ctypes.byref(d), st=stream)
+    ev1.record()
+    PROFILER.records.append((ev0, ev1, flops, retag(tag) if retag else tag))
+
+
+def _x3w_tag(tag):
+    """An x3 launch served by the 256 x 256 tile (gemm_x3w_kernel) gets its own line in the bench's roofline."""
+    return "x3w_" + tag[3:] if tag.startswith("x3_") and _entry("pulse_gemm_last_tile")() == 256 else tag
+
+
 def launch_gemm(d, flops=0.0, tag="fwd", stream=None):
-    lib = _lib.load()
-    st = _stream() if stream is None else stream
-    if PROFILER.enabled:
-        ev0, ev1 = PROFILER._event(), PROFILER._event()
-        ev0.record()
-        _lib.check(lib.pulse_gemm_f32(ctypes.byref(d), st), "pulse_gemm_f32")
-        ev1.record()
-        if tag.startswith("x3_") and lib.pulse_gemm_last_tile() == 256:
-            tag = "x3w_" + tag[3:]            # served by the 256 x 256 tile (gemm_x3w_kernel): its own line in the bench's roofline
-        PROFILER.records.append((ev0, ev1, flops, tag))
-        return
-    _lib.check(lib.pulse_gemm_f32(ctypes.byref(d), st), "pulse_gemm_f32")
+    _launch_desc("pulse_gemm_f32", d, flops, tag, stream, _x3w_tag)
 
 
 def gemm(A, B, C, **kw):
@@ -208,34 +198,36 @@ class Plan:
     """A pre-built launch sequence: GEMM descriptors and bound C-ABI calls are created once per
     workspace, so replaying a forward / backward pass costs one ctypes call per kernel."""
 
+    # op kinds: ops holds (kind, descriptor, flops, tag) for the two GEMM kinds and (kind, bound entry, arguments, entry name) for the others
+    GEMM, CALL, GEMM_X3P, PARTIAL_REDUCE = 0, 1, 2, 3
+
     def __init__(self, bf16=False):
         self.ops = []
         self.split = 0
         self.bf16 = bool(bf16)          # every GEMM of this plan runs on the bf16 MFMA (mixed_precision training passes)
+        self.partial_reduces = []       # (dst_off, count, rows, src) of every call_partial_reduce
 
     def gemm(self, A, B, C, **kw):
         kw.setdefault("compute_bf16", self.bf16)
-        self.ops.append((0,) + make_gemm_desc(A, B, C, **kw))
+        self.ops.append((Plan.GEMM,) + make_gemm_desc(A, B, C, **kw))
 
     def call(self, name, *args):
-        self.ops.append((1, getattr(_lib.load(), name), args, name))
+        self.ops.append((Plan.CALL, _entry(name), args, name))     # (the tuple keeps ctypes arrays among the arguments alive)
 
     def call_partial_reduce(self, src, rows, count, slabs, dst_off):
         """Ordered sum of ``rows`` partial rows of ``src`` (row stride src.stride(0), ``count`` floats each) into slab 0 of ``slabs`` at element
         ``dst_off`` (pulse_reduce_slabs).  Registered separately: run(skip_partial_reduces=True) leaves these launches out when the caller's
         ReduceGrads reads the partials itself (``partial_reduces`` lists what it has to read)."""
-        self.ops.append((3, _lib.load().pulse_reduce_slabs, (src.data_ptr(), int(rows), int(src.stride(0)), int(count), slabs.data_ptr() + 4 * int(dst_off), 1.0),
-                         "pulse_reduce_slabs"))
-        if not hasattr(self, "partial_reduces"):
-            self.partial_reduces = []
+        name = "pulse_reduce_slabs"
+        self.ops.append((Plan.PARTIAL_REDUCE, _entry(name), (src.data_ptr(), int(rows), int(src.stride(0)), int(count), _p(slabs, off=int(dst_off)), 1.0), name))
         self.partial_reduces.append((int(dst_off), int(count), int(rows), src))
 
     def gemm_x3p(self, A, B, **kw):
-        self.ops.append((2,) + make_gemm_x3p_desc(A, B, **kw))
+        self.ops.append((Plan.GEMM_X3P,) + make_gemm_x3p_desc(A, B, **kw))
 
     def gemm_b16(self, A, B, **kw):
         """bf16-storage GEMM (pulse_gemm_x3p, planes = 1): A / B / Cp / aux are int16 (bf16 bit pattern) tensors."""
-        self.ops.append((2,) + make_gemm_x3p_desc(A, B, planes=1, **kw))
+        self.gemm_x3p(A, B, planes=1, **kw)
 
     def refresh_b16(self, flat, flat16, count):
         """flat16[i] = bf16(flat[i]) for the whole flat parameter buffer: the bf16 weight image the plan's GEMMs read is rebuilt inside the
@@ -255,34 +247,24 @@ class Plan:
             raise ValueError("weights_b16: at most four transposes per launch")
         arr = (_lib.B16Transpose * max(1, len(transposes)))()
         for d, kw in zip(arr, transposes):
-            if kw["out"].dtype != torch.int16:
-                raise TypeError("weights_b16: transposed images must be int16")
-            d.in_, d.ld_in, d.rows, d.cols = kw["x"].data_ptr() + 4 * kw.get("x_off", 0), kw["ld_in"], kw["rows"], kw["cols"]
-            d.out, d.ld_out = kw["out"].data_ptr() + 2 * kw.get("out_off", 0), kw["ld_out"]
+            d.in_, d.ld_in, d.rows, d.cols = _p(kw["x"], off=kw.get("x_off", 0)), kw["ld_in"], kw["rows"], kw["cols"]
+            d.out, d.ld_out = _b16(kw["out"], "weights_b16: a transposed image", kw.get("out_off", 0)), kw["ld_out"]
             d.batch, d.stride_in, d.stride_out = kw.get("batch", 1), kw.get("stride_in", 0), kw.get("stride_out", 0)
-        self._keep = getattr(self, "_keep", []) + [arr]
         self.call("pulse_weights_to_b16", flat.data_ptr(), count, flat16.data_ptr(), len(transposes), arr)
 
     def transpose_b16(self, x, out, **kw):
-        x_off, out_off = kw.pop("x_off", 0), kw.pop("out_off", 0)
-        if out.dtype != torch.int16:
-            raise TypeError("transpose_b16: out must be int16")
-        self.call("pulse_transpose_to_b16", x.data_ptr() + 4 * x_off, kw["ld_in"], kw["rows"], kw["cols"], out.data_ptr() + 2 * out_off, kw["ld_out"],
-                  kw.get("batch", 1), kw.get("stride_in", 0), kw.get("stride_out", 0))
+        self.call("pulse_transpose_to_b16", _p(x, off=kw.pop("x_off", 0)), kw["ld_in"], kw["rows"], kw["cols"],
+                  _b16(out, "transpose_b16: out", kw.pop("out_off", 0)), kw["ld_out"], kw.get("batch", 1), kw.get("stride_in", 0), kw.get("stride_out", 0))
 
     def colsum_b16(self, x, m, n, ld, slabs, num_slabs, slab_stride, out_off, x_off=0):
         """Bias gradient of a bf16 gradient matrix (m, n): slab s of ``slabs`` receives, at [out_off, out_off + n), the column sums over the
         s-th of ``num_slabs`` row ranges -- summed with the weight gradients by the one slab reduce, like the fp32 kernels' ``rowsum``."""
-        if x.dtype != torch.int16:
-            raise TypeError("colsum_b16: x must be an int16 (bf16 bit pattern) tensor")
-        self.call("pulse_colsum_partial_b16", x.data_ptr() + 2 * x_off, m, n, ld, num_slabs, slabs.data_ptr() + 4 * out_off, slab_stride)
+        self.call("pulse_colsum_partial_b16", _b16(x, "colsum_b16: x", x_off), m, n, ld, num_slabs, _p(slabs, off=out_off), slab_stride)
 
     def colsum_weighted_b16(self, x, w16, w_stride, m, n, ld, slabs, num_slabs, slab_stride, out_off, w_off=0):
         """slab s [out_off, out_off + n) = sum over the s-th row range of w16[m * w_stride] * x[m][:]: the weight gradient of a one-output Linear."""
-        if x.dtype != torch.int16 or w16.dtype != torch.int16:
-            raise TypeError("colsum_weighted_b16: x / w16 must be int16 (bf16 bit pattern) tensors")
-        self.call("pulse_colsum_weighted_b16", x.data_ptr(), m, n, ld, w16.data_ptr() + 2 * w_off, w_stride, num_slabs, slabs.data_ptr() + 4 * out_off,
-                  slab_stride)
+        self.call("pulse_colsum_weighted_b16", _b16(x, "colsum_weighted_b16: x"), m, n, ld, _b16(w16, "colsum_weighted_b16: w16", w_off), w_stride,
+                  num_slabs, _p(slabs, off=out_off), slab_stride)
 
     def run(self, start=0, stop=None, skip_partial_reduces=False):
         """``skip_partial_reduces``: leave out the small ordered reduces registered with call_partial_reduce -- the caller's fused gradient reduce
@@ -290,16 +272,14 @@ class Plan:
         (Round 5 measured replaying plan segments as captured HIP graphs: flat inside the epoch -- cfg2 68.0 / 68.6 ms eager vs 68.4 / 69.2,
         profiles/r05_ab_runs.txt; the update is one dependent chain the host enqueues far ahead of the device.  The path was removed in round 6.)"""
         st = _stream()
-        for op in self.ops[start:stop]:
-            if op[0] == 0:
-                launch_gemm(op[1], op[2], op[3], st)
-            elif op[0] == 2:
-                launch_gemm_x3p(op[1], op[2], op[3], st)
-            elif op[0] == 3:
-                if not skip_partial_reduces:
-                    _lib.check(op[1](*op[2], st), op[3])
-            else:
-                _lib.check(op[1](*op[2], st), op[3])
+        GEMM, GEMM_X3P, CALL, check = self.GEMM, self.GEMM_X3P, self.CALL, _lib.check
+        for kind, what, args, tag in self.ops[start:stop]:
+            if kind == GEMM:
+                launch_gemm(what, args, tag, st)
+            elif kind == GEMM_X3P:
+                launch_gemm_x3p(what, args, tag, st)
+            elif kind == CALL or not skip_partial_reduces:
+                check(what(*args, st), tag)
 
 
 # --------------------------------------------------------------------------- #
@@ -307,62 +287,53 @@ class Plan:
 # --------------------------------------------------------------------------- #
 def vae_embed(heads, x, ain, *, rows, embedding_size, self_obs_size, z_col, eps=None, cin=None, clamp=True, clamp_max=2.0):
     a = _lib.VaeEmbedArgs()
-    a.heads, a.heads_stride = _chk(heads, "heads"), heads.stride(0)
-    a.eps, a.eps_stride = _chk(eps, "eps"), (eps.stride(0) if eps is not None else 0)
-    a.x, a.x_stride = _chk(x, "x"), x.stride(0)
-    a.ain, a.ain_stride = _chk(ain, "ain"), ain.stride(0)
-    a.cin, a.cin_stride = _chk(cin, "cin"), (cin.stride(0) if cin is not None else 0)
+    a.heads, a.heads_stride = _p(heads, "heads"), heads.stride(0)
+    a.eps, a.eps_stride = _p(eps, "eps"), (eps.stride(0) if eps is not None else 0)
+    a.x, a.x_stride = _p(x, "x"), x.stride(0)
+    a.ain, a.ain_stride = _p(ain, "ain"), ain.stride(0)
+    a.cin, a.cin_stride = _p(cin, "cin"), (cin.stride(0) if cin is not None else 0)
     a.rows, a.embedding_size, a.self_obs_size, a.z_col = rows, embedding_size, self_obs_size, z_col
     a.clamp_logvar, a.clamp_max = int(bool(clamp)), float(clamp_max)
-    _lib.check(_lib.load().pulse_vae_embed(ctypes.byref(a), _stream()), "pulse_vae_embed")
+    _launch("pulse_vae_embed", ctypes.byref(a))
 
 
 def vae_kin_loss(pred, gt, zheads, pheads, progress, dmu, partials, *, rows, num_actions, embedding_size, horizon, clamp=True, clamp_max=2.0,
                  use_ar1=True, use_regu=False):
     a = _lib.VaeKinArgs()
-    a.pred, a.pred_stride, a.gt, a.gt_stride = _chk(pred, "pred"), pred.stride(0), _chk(gt, "gt"), gt.stride(0)
-    a.zheads, a.zheads_stride, a.pheads, a.pheads_stride = _chk(zheads, "zheads"), zheads.stride(0), _chk(pheads, "pheads"), pheads.stride(0)
-    a.progress = _chk(progress, "progress", torch.int64)
+    a.pred, a.pred_stride, a.gt, a.gt_stride = _p(pred, "pred"), pred.stride(0), _p(gt, "gt"), gt.stride(0)
+    a.zheads, a.zheads_stride, a.pheads, a.pheads_stride = _p(zheads, "zheads"), zheads.stride(0), _p(pheads, "pheads"), pheads.stride(0)
+    a.progress = _p(progress, "progress", torch.int64)
     a.rows, a.num_actions, a.embedding_size, a.horizon = rows, num_actions, embedding_size, horizon
     a.clamp_logvar, a.clamp_max, a.use_ar1, a.use_regu = int(bool(clamp)), float(clamp_max), int(bool(use_ar1)), int(bool(use_regu))
-    a.dmu, a.dmu_stride = _chk(dmu, "dmu"), dmu.stride(0)
-    a.partials, a.num_blocks = _chk(partials, "partials"), partials.shape[0]
-    _lib.check(_lib.load().pulse_vae_kin_loss(ctypes.byref(a), _stream()), "pulse_vae_kin_loss")
+    a.dmu, a.dmu_stride = _p(dmu, "dmu"), dmu.stride(0)
+    a.partials, a.num_blocks = _p(partials, "partials"), partials.shape[0]
+    _launch("pulse_vae_kin_loss", ctypes.byref(a))
 
 
 def vae_head_backward(zheads, dzheads, *, rows, embedding_size, horizon=1, pheads=None, dpheads=None, eps=None, dz=None, progress=None, clamp=True,
                       clamp_max=2.0, c_kl=0.0, c_ar1=0.0, c_regu=0.0):
     a = _lib.VaeHeadBwdArgs()
-    a.zheads, a.zheads_stride = _chk(zheads, "zheads"), zheads.stride(0)
-    a.pheads, a.pheads_stride = _chk(pheads, "pheads"), (pheads.stride(0) if pheads is not None else 0)
-    a.eps, a.eps_stride = _chk(eps, "eps"), (eps.stride(0) if eps is not None else 0)
-    a.dz, a.dz_stride = _chk(dz, "dz"), (dz.stride(0) if dz is not None else 0)
-    a.progress = _chk(progress, "progress", torch.int64)
+    a.zheads, a.zheads_stride = _p(zheads, "zheads"), zheads.stride(0)
+    a.pheads, a.pheads_stride = _p(pheads, "pheads"), (pheads.stride(0) if pheads is not None else 0)
+    a.eps, a.eps_stride = _p(eps, "eps"), (eps.stride(0) if eps is not None else 0)
+    a.dz, a.dz_stride = _p(dz, "dz"), (dz.stride(0) if dz is not None else 0)
+    a.progress = _p(progress, "progress", torch.int64)
     a.rows, a.embedding_size, a.horizon = rows, embedding_size, horizon
     a.clamp_logvar, a.clamp_max = int(bool(clamp)), float(clamp_max)
     a.c_kl, a.c_ar1, a.c_regu = float(c_kl), float(c_ar1), float(c_regu)
-    a.dzheads, a.dzheads_stride = _chk(dzheads, "dzheads"), dzheads.stride(0)
-    a.dpheads, a.dpheads_stride = _chk(dpheads, "dpheads"), (dpheads.stride(0) if dpheads is not None else 0)
-    _lib.check(_lib.load().pulse_vae_head_backward(ctypes.byref(a), _stream()), "pulse_vae_head_backward")
+    a.dzheads, a.dzheads_stride = _p(dzheads, "dzheads"), dzheads.stride(0)
+    a.dpheads, a.dpheads_stride = _p(dpheads, "dpheads"), (dpheads.stride(0) if dpheads is not None else 0)
+    _launch("pulse_vae_head_backward", ctypes.byref(a))
 
 
 # --------------------------------------------------------------------------- #
 # MCP composer head (include/pulse_hip.h section 4e)
 # --------------------------------------------------------------------------- #
-def _mcp_rows(t, name, rows, cols):
-    _chk(t, name)
-    if t.dim() != 2 or t.shape[0] != rows or t.shape[1] < cols:
-        raise ValueError(f"{name}: expected a ({rows}, >= {cols}) tensor, got {tuple(t.shape)}")
-    if rows > 1 and t.stride(0) < cols:
-        raise ValueError(f"{name}: row stride {t.stride(0)} does not cover {cols} columns")
-    return t.data_ptr(), (t.stride(0) if rows > 1 else max(cols, t.shape[1]))
-
-
 def mcp_head_forward(h, mu, *, rows, num_prim):
     """mu[:, :num_prim] = softmax(h[:, :num_prim], dim=1): the nn.Softmax AMPMCPBuilder appends to the composer (amp_network_mcp_builder.py:53-55)."""
-    hp, hs = _mcp_rows(h, "h", rows, num_prim)
-    mp, ms = _mcp_rows(mu, "mu", rows, num_prim)
-    _lib.check(_lib.load().pulse_mcp_head_forward(hp, hs, rows, num_prim, mp, ms, _stream()), "pulse_mcp_head_forward")
+    hp, hs = _rows(h, "h", rows, num_prim)
+    mp, ms = _rows(mu, "mu", rows, num_prim)
+    _launch("pulse_mcp_head_forward", hp, hs, rows, num_prim, mp, ms)
     return mu
 
 
@@ -371,11 +342,11 @@ def mcp_head_backward(dmu, dz, *, rows, num_prim, mu=None, aux=None, activation=
     output; ACT_SILU: the pre-activation; ACT_SILU_D: the stored derivative): the composer's tail down to its last Linear's output."""
     if activation != ACT_NONE and aux is None:
         raise ValueError("mcp_head_backward: the activation's derivative needs aux")
-    dp, ds = _mcp_rows(dmu, "dmu", rows, num_prim)
-    zp, zs = _mcp_rows(dz, "dz", rows, num_prim)
-    mp, ms = _mcp_rows(mu, "mu", rows, num_prim) if mu is not None else (None, 0)
-    ap, as_ = _mcp_rows(aux, "aux", rows, num_prim) if aux is not None else (None, 0)
-    _lib.check(_lib.load().pulse_mcp_head_backward(dp, ds, mp, ms, ap, as_, int(activation), rows, num_prim, zp, zs, _stream()), "pulse_mcp_head_backward")
+    dp, ds = _rows(dmu, "dmu", rows, num_prim)
+    zp, zs = _rows(dz, "dz", rows, num_prim)
+    mp, ms = _rows(mu, "mu", rows, num_prim) if mu is not None else (None, 0)
+    ap, as_ = _rows(aux, "aux", rows, num_prim) if aux is not None else (None, 0)
+    _launch("pulse_mcp_head_backward", dp, ds, mp, ms, ap, as_, int(activation), rows, num_prim, zp, zs)
     return dz
 
 
@@ -401,7 +372,7 @@ def motion_build(frames, offsets, *, src_rot, src_trans, clip_src_start, clip_ou
     for name, t, dt in (("src_rot", src_rot, torch.float32), ("src_trans", src_trans, torch.float32), ("clip_src_start", clip_src_start, torch.int64),
                         ("clip_crop_start", clip_crop_start, torch.int64), ("clip_out_start", clip_out_start, torch.int64), ("clip_dt", clip_dt, torch.float32),
                         ("clip_heading", clip_heading, torch.float32), ("local_translation", local_translation, torch.float32), ("frames", frames, torch.float32)):
-        ptr = _chk(t, name, dt)
+        ptr = _p(t, name, dt)
         if t is not None and not t.is_contiguous():
             raise ValueError(f"{name}: contiguous tensor expected, got strides {tuple(t.stride())}")
         setattr(a, name, ptr)
@@ -423,7 +394,7 @@ def motion_build(frames, offsets, *, src_rot, src_trans, clip_src_start, clip_ou
     a.off_gts, a.off_grs, a.off_lrs = offsets["gts"], offsets["grs"], offsets["lrs"]
     a.off_gvs, a.off_gavs, a.off_dvs = offsets["gvs"], offsets["gavs"], offsets["dvs"]
     a.filter_w[:] = gaussian_weights()
-    _lib.check(_lib.load().pulse_motion_build(ctypes.byref(a), _stream()), "pulse_motion_build")
+    _launch("pulse_motion_build", ctypes.byref(a))
     return frames
 
 
@@ -443,24 +414,26 @@ def alloc_planes(rows, cols, device):
 def split_planes(x, out=None, *, rows=None, cols=None, transpose=False, row_idx=None, x_off=0, ld_in=None, out_off=0):
     """fp32 matrix -> its three bf16 planes (x == p0 + p1 + p2 exactly).  ``x`` is a 2-D tensor (or a base tensor with x_off / ld_in /
     rows / cols given explicitly); transpose=True writes the planes of x.T."""
-    _chk(x, "x")
+    return _to_planes("split_planes", 3, x, out, rows, cols, transpose, row_idx, x_off, ld_in, out_off)
+
+
+def _to_planes(fn, planes, x, out, rows, cols, transpose, row_idx, x_off, ld_in, out_off):
+    """split_planes (``planes`` 3: out (3, rows, pitch)) and to_b16 (``planes`` 1: out (rows, pitch), plane stride 0) on pulse_split_planes."""
+    xp = _p(x, "x", off=x_off)
     if ld_in is None:
         if x.dim() != 2 or x.stride(1) != 1:
-            raise ValueError("split_planes: 2-D tensor with contiguous rows expected (or explicit geometry)")
+            raise ValueError(f"{fn}: 2-D tensor with contiguous rows expected (or explicit geometry)")
         ld_in = x.stride(0)
-        r_in, c_in = x.shape
-        rows_out, cols_out = (c_in, r_in) if transpose else (r_in, c_in)
+        rows, cols = (x.shape[1], x.shape[0]) if transpose else x.shape
         if row_idx is not None:
-            rows_out = row_idx.numel()
-    else:
-        rows_out, cols_out = rows, cols
+            rows = row_idx.numel()
     if out is None:
-        out = alloc_planes(rows_out, cols_out, x.device)
-    if out.dtype != torch.int16 or out.dim() != 3 or out.shape[0] != 3 or out.stride(2) != 1 or not out.is_cuda:
-        raise TypeError("split_planes: out must be a (3, rows, pitch) int16 CUDA tensor")
-    _chk(row_idx, "row_idx", torch.int64)
-    _lib.check(_lib.load().pulse_split_planes(x.data_ptr() + 4 * x_off, ld_in, rows_out, cols_out, out.data_ptr() + 2 * out_off, out.stride(0),
-                                              out.stride(1), 1 if transpose else 0, _p(row_idx), _stream()), "pulse_split_planes")
+        out = alloc_planes(rows, cols, x.device) if planes == 3 else alloc_b16(rows, cols, x.device)
+    op = _b16(out, f"{fn}: out", out_off)
+    if out.dim() != (3 if planes == 3 else 2) or (planes == 3 and out.shape[0] != 3) or out.stride(-1) != 1:
+        raise TypeError(f"{fn}: out must be a {'(3, rows, pitch)' if planes == 3 else '(rows, pitch)'} int16 CUDA tensor")
+    _launch("pulse_split_planes", xp, ld_in, rows, cols, op, out.stride(0) if planes == 3 else 0, out.stride(-2), 1 if transpose else 0,
+            _p(row_idx, "row_idx", _I64))
     return out
 
 
@@ -477,25 +450,7 @@ def alloc_b16(rows, cols, device):
 
 def to_b16(x, out=None, *, rows=None, cols=None, transpose=False, row_idx=None, x_off=0, ld_in=None, out_off=0):
     """fp32 matrix -> the same matrix rounded to bf16 (round to nearest even), pad columns zero-filled.  Geometry arguments as split_planes."""
-    _chk(x, "x")
-    if ld_in is None:
-        if x.dim() != 2 or x.stride(1) != 1:
-            raise ValueError("to_b16: 2-D tensor with contiguous rows expected (or explicit geometry)")
-        ld_in = x.stride(0)
-        r_in, c_in = x.shape
-        rows_out, cols_out = (c_in, r_in) if transpose else (r_in, c_in)
-        if row_idx is not None:
-            rows_out = row_idx.numel()
-    else:
-        rows_out, cols_out = rows, cols
-    if out is None:
-        out = alloc_b16(rows_out, cols_out, x.device)
-    if out.dtype != torch.int16 or out.dim() != 2 or out.stride(1) != 1 or not out.is_cuda:
-        raise TypeError("to_b16: out must be a (rows, pitch) int16 CUDA tensor")
-    _chk(row_idx, "row_idx", torch.int64)
-    _lib.check(_lib.load().pulse_split_planes(x.data_ptr() + 4 * x_off, ld_in, rows_out, cols_out, out.data_ptr() + 2 * out_off, 0,
-                                              out.stride(0), 1 if transpose else 0, _p(row_idx), _stream()), "pulse_split_planes")
-    return out
+    return _to_planes("to_b16", 1, x, out, rows, cols, transpose, row_idx, x_off, ld_in, out_off)
 
 
 def from_b16(p):
@@ -521,37 +476,30 @@ def make_gemm_x3p_desc(A, B, *, M, N, K, C=None, Cp=None, bias=None, activation=
             raise TypeError(f"gemm_x3p: {nm} must be a {'(3, rows, pitch)' if planes == 3 else '(rows, pitch)'} int16 CUDA tensor")
     d = _lib.GemmX3pDesc()
     d.planes = planes
-    d.A, d.a_plane_stride, d.lda = A.data_ptr() + 2 * a_off, (A.stride(0) if planes == 3 else 0), (lda if lda is not None else A.stride(nd - 2))
-    d.B, d.b_plane_stride, d.ldb = B.data_ptr() + 2 * b_off, (B.stride(0) if planes == 3 else 0), (ldb if ldb is not None else B.stride(nd - 2))
+    d.A, d.a_plane_stride, d.lda = _p(A, None, _I16, a_off), (A.stride(0) if planes == 3 else 0), (lda if lda is not None else A.stride(nd - 2))
+    d.B, d.b_plane_stride, d.ldb = _p(B, None, _I16, b_off), (B.stride(0) if planes == 3 else 0), (ldb if ldb is not None else B.stride(nd - 2))
     d.a_layout, d.b_layout = a_layout, b_layout
     if C is not None:
-        _chk(C, "C")
-        d.C, d.ldc = C.data_ptr() + 4 * c_off, ldc
+        d.C, d.ldc = _p(C, "C", off=c_off), ldc
     if Cp is not None:
-        d.Cp, d.c_plane_stride, d.ldcp = Cp.data_ptr() + 2 * cp_off, (Cp.stride(0) if planes == 3 else 0), (ldcp if ldcp is not None else Cp.stride(nd - 2))
-    d.C2 = (C2.data_ptr() + 4 * c2_off) if C2 is not None else None
-    d.ldc2 = ldc2
-    d.bias = (bias.data_ptr() + 4 * bias_off) if bias is not None else None
-    if aux is not None and aux.dtype == torch.int16:
-        d.aux, d.aux_is_bf16 = aux.data_ptr() + 2 * aux_off, 1
-    else:
-        d.aux = (aux.data_ptr() + 4 * aux_off) if aux is not None else None
-    d.ldaux = ldaux
+        d.Cp, d.c_plane_stride, d.ldcp = _p(Cp, None, _I16, cp_off), (Cp.stride(0) if planes == 3 else 0), (ldcp if ldcp is not None else Cp.stride(nd - 2))
+    d.C2, d.ldc2, d.bias = _p(C2, off=c2_off), ldc2, _p(bias, off=bias_off)
+    d.aux_is_bf16 = int(aux is not None and aux.dtype == torch.int16)
+    d.aux, d.ldaux = _p(aux, None, _I16 if d.aux_is_bf16 else torch.float32, aux_off), ldaux
     d.M, d.N, d.K, d.batch = M, N, K, batch
     d.stride_a, d.stride_b, d.stride_c, d.stride_cp, d.stride_c2 = stride_a, stride_b, stride_c, stride_cp, stride_c2
     d.stride_bias, d.stride_aux = stride_bias, stride_aux
     d.split_k, d.split_stride, d.activation, d.epilogue = split_k, split_stride, activation, epilogue
     if out_colsum is not None:             # (row_tiles(M, N, batch), >= covering columns) fp32: per-row-tile column sums of the stored output
-        _chk(out_colsum, "out_colsum")
-        ld = out_colsum.stride(0) if ld_out_colsum is None else ld_out_colsum
+        d.out_colsum, d.stride_out_colsum = _p(out_colsum, "out_colsum", off=out_colsum_off), stride_out_colsum
+        d.ld_out_colsum = out_colsum.stride(0) if ld_out_colsum is None else ld_out_colsum
         need = gemm_x3p_row_tiles(M, N, batch)
         if out_colsum.dim() != 2 or out_colsum.shape[0] < need:
             raise ValueError(f"gemm_x3p: out_colsum needs {need} rows (one per row tile)")
-        d.out_colsum, d.stride_out_colsum, d.ld_out_colsum = out_colsum.data_ptr() + 4 * out_colsum_off, stride_out_colsum, ld
     if relu_mask8 is not None:             # uint8 (rows, roundup8(cols) / 8): alloc_relu_mask8; offsets / strides in bytes
         if relu_mask8.dtype != torch.uint8:
             raise TypeError("relu_mask8 must be a uint8 tensor (alloc_relu_mask8)")
-        d.relu_mask8 = relu_mask8.data_ptr() + int(mask8_off)
+        d.relu_mask8 = _p(relu_mask8, None, torch.uint8, int(mask8_off))
         d.ld_mask8, d.stride_mask8 = int(relu_mask8.stride(0) if ld_mask8 is None else ld_mask8), int(stride_mask8)
     flops = 2.0 * M * (algo_n if algo_n else N) * (algo_k if algo_k else K) * batch
     kc_a, kc_b = a_layout == GEMM_RED_CONTIG, b_layout == GEMM_RED_CONTIG
@@ -570,16 +518,7 @@ def gemm_set_option(key, value):
 
 
 def launch_gemm_x3p(d, flops=0.0, tag="x3p_fwd", stream=None):
-    lib = _lib.load()
-    st = _stream() if stream is None else stream
-    if PROFILER.enabled:
-        ev0, ev1 = PROFILER._event(), PROFILER._event()
-        ev0.record()
-        _lib.check(lib.pulse_gemm_x3p(ctypes.byref(d), st), "pulse_gemm_x3p")
-        ev1.record()
-        PROFILER.records.append((ev0, ev1, flops, tag))
-        return
-    _lib.check(lib.pulse_gemm_x3p(ctypes.byref(d), st), "pulse_gemm_x3p")
+    _launch_desc("pulse_gemm_x3p", d, flops, tag, stream)
 
 
 def gemm_x3p(A, B, **kw):
@@ -588,7 +527,7 @@ def gemm_x3p(A, B, **kw):
 
 def linear_forward(x, w, bias=None, activation=ACT_NONE, out=None):
     """Convenience: y = act(x @ w.T + bias) for 2-D row-major tensors with 16-byte aligned rows."""
-    x, w = _dev(x, "x"), _dev(w, "w")
+    _p(x, "x", unit_stride=False), _p(w, "w", unit_stride=False)
     m, k = x.shape
     n = w.shape[0]
     if out is None:
@@ -598,13 +537,11 @@ def linear_forward(x, w, bias=None, activation=ACT_NONE, out=None):
 
 
 def reduce_slabs(slabs, num_slabs, slab_stride, count, out, scale=1.0, slabs_off=0, out_off=0):
-    _lib.check(_lib.load().pulse_reduce_slabs(slabs.data_ptr() + 4 * slabs_off, num_slabs, slab_stride, count,
-                                              out.data_ptr() + 4 * out_off, float(scale), _stream()), "pulse_reduce_slabs")
+    _launch("pulse_reduce_slabs", _p(slabs, off=slabs_off), num_slabs, slab_stride, count, _p(out, off=out_off), float(scale))
 
 
 def colsum_partial(x, m, n, ld, num_chunks, partial, ld_partial, x_off=0, partial_off=0):
-    _lib.check(_lib.load().pulse_colsum_partial(x.data_ptr() + 4 * x_off, m, n, ld, num_chunks,
-                                                partial.data_ptr() + 4 * partial_off, ld_partial, _stream()), "pulse_colsum_partial")
+    _launch("pulse_colsum_partial", _p(x, off=x_off), m, n, ld, num_chunks, _p(partial, off=partial_off), ld_partial)
 
 
 def rms_copy_supported(x, cols, y, y_cols, raw_out):
@@ -623,55 +560,43 @@ def rms_normalize(x, mean, var, *, rows, cols, x_stride, y, y_stride, y_cols=Non
     record of the observation, see rms_copy_supported); normalising direction, fp32 output, no planes."""
     if num_blocks is None:
         num_blocks = max(1, min(512, rows // 16)) if moment_partials is None else moment_partials.shape[0]
+    # the four entries share their leading arguments (the plain one takes the direction before y) and their tail up to num_blocks
+    head = (_p(x), x_stride, _p(row_idx), rows, cols, _p(mean), _p(var), eps, clip)
+    tail = (_p(y), y_stride, cols if y_cols is None else y_cols, _p(moment_partials), num_blocks)
     if raw_out is not None:
         if unnorm or planes is not None or y.dtype != torch.float32:
             raise ValueError("rms_normalize: raw_out goes with the plain normalising direction only")
         if not raw_out.is_cuda or raw_out.dtype != torch.float32 or raw_out.dim() != 2 or raw_out.stride(1) != 1 or raw_out.shape[0] < rows:
             raise TypeError("rms_normalize: raw_out must be a (>= rows, cols) float32 CUDA view with unit inner stride")
-        _lib.check(_lib.load().pulse_rms_normalize_copy(_p(x), x_stride, _p(row_idx), rows, cols, _p(mean), _p(var), eps, clip, _p(y), y_stride,
-                                                        cols if y_cols is None else y_cols, _p(moment_partials), num_blocks, raw_out.data_ptr(),
-                                                        raw_out.stride(0), _stream()), "pulse_rms_normalize_copy")
-        return
-    if y.dtype == torch.int16:
+        _launch("pulse_rms_normalize_copy", *head, *tail, raw_out.data_ptr(), raw_out.stride(0))
+    elif y.dtype == torch.int16:
         if unnorm or planes is not None or not y.is_cuda or y.stride(-1) != 1:
             raise ValueError("rms_normalize: a bf16 output goes with the normalising direction, without planes")
-        _lib.check(_lib.load().pulse_rms_normalize_b16(_p(x), x_stride, _p(row_idx), rows, cols, _p(mean), _p(var), eps, clip, y.data_ptr(), y_stride,
-                                                       cols if y_cols is None else y_cols, _p(moment_partials), num_blocks, _stream()), "pulse_rms_normalize_b16")
-        return
-    if planes is not None:
+        _launch("pulse_rms_normalize_b16", *head, *tail)
+    elif planes is not None:
         if unnorm:
             raise ValueError("rms_normalize: planes go with the normalising direction only")
         if planes.dtype != torch.int16 or planes.dim() != 3 or planes.shape[0] != 3 or planes.stride(2) != 1 or planes.shape[1] < rows or not planes.is_cuda:
             raise TypeError("rms_normalize: planes must be a (3, >= rows, pitch) int16 CUDA tensor")
-        _lib.check(_lib.load().pulse_rms_normalize_planes(_p(x), x_stride, _p(row_idx), rows, cols, _p(mean), _p(var), eps, clip, _p(y), y_stride,
-                                                          cols if y_cols is None else y_cols, _p(moment_partials), num_blocks, planes.data_ptr(),
-                                                          planes.stride(0), planes.stride(1), _stream()), "pulse_rms_normalize_planes")
-        return
-    _lib.check(_lib.load().pulse_rms_normalize(_p(x), x_stride, _p(row_idx), rows, cols, _p(mean), _p(var), eps, clip,
-                                               1 if unnorm else 0, _p(y), y_stride, cols if y_cols is None else y_cols,
-                                               _p(moment_partials), num_blocks, _stream()), "pulse_rms_normalize")
+        _launch("pulse_rms_normalize_planes", *head, *tail, planes.data_ptr(), planes.stride(0), planes.stride(1))
+    else:
+        _launch("pulse_rms_normalize", *head, 1 if unnorm else 0, *tail)
 
 
 def rms_update(mean, var, count, moment_partials, cols, count_old, batch_count):
-    _lib.check(_lib.load().pulse_rms_update(_p(mean), _p(var), _p(count), _p(moment_partials), moment_partials.shape[0], cols,
-                                            float(count_old), float(batch_count), _stream()), "pulse_rms_update")
+    _launch("pulse_rms_update", _p(mean), _p(var), _p(count), _p(moment_partials), moment_partials.shape[0], cols, float(count_old), float(batch_count))
 
 
 def policy_sample(mu, mu_stride, logstd, noise, noise_stride, rows, num_actions, actions, actions_stride, neglogp,
                   neglogp_stride=1, sigmas=None, sigmas_stride=0, value_raw=None, value_stride=0, value_mean=None,
                   value_var=None, values=None, values_stride=0, mu_off=0, actions_off=0, sigmas_off=0, neglogp_off=0,
                   values_off=0, mus_out=None, mus_out_stride=0, mus_out_off=0):
-    def po(t, off):
-        return (t.data_ptr() + 4 * off) if t is not None else None
-    for t, nm in ((mu, "mu"), (logstd, "logstd"), (noise, "noise"), (value_raw, "value_raw"), (actions, "actions"), (sigmas, "sigmas"),
-                  (neglogp, "neglogp"), (values, "values"), (mus_out, "mus_out")):
-        _chk(t, nm)
-    _chk(value_mean, "value_mean", torch.float64), _chk(value_var, "value_var", torch.float64)
-    _lib.check(_lib.load().pulse_policy_sample(po(mu, mu_off), mu_stride, _p(logstd), _p(noise), noise_stride, _p(value_raw),
-                                               value_stride, _p(value_mean), _p(value_var), rows, num_actions,
-                                               po(actions, actions_off), actions_stride, po(sigmas, sigmas_off), sigmas_stride,
-                                               po(neglogp, neglogp_off), neglogp_stride, po(values, values_off), values_stride,
-                                               po(mus_out, mus_out_off), mus_out_stride, _stream()), "pulse_policy_sample")
+    f32 = torch.float32
+    _launch("pulse_policy_sample", _p(mu, "mu", f32, mu_off), mu_stride, _p(logstd, "logstd"), _p(noise, "noise"), noise_stride,
+            _p(value_raw, "value_raw"), value_stride, _p(value_mean, "value_mean", _F64), _p(value_var, "value_var", _F64), rows, num_actions,
+            _p(actions, "actions", f32, actions_off), actions_stride, _p(sigmas, "sigmas", f32, sigmas_off), sigmas_stride,
+            _p(neglogp, "neglogp", f32, neglogp_off), neglogp_stride, _p(values, "values", f32, values_off), values_stride,
+            _p(mus_out, "mus_out", f32, mus_out_off), mus_out_stride)
 
 
 def ppo_loss(*, mu, mu_stride, value, value_stride, logstd, old_logstd, idx, actions, actions_stride, old_mu, old_mu_stride,
@@ -690,88 +615,73 @@ def ppo_loss(*, mu, mu_stride, value, value_stride, logstd, old_logstd, idx, act
     a.dmu, a.dmu_stride, a.dvalue, a.dvalue_stride = _p(dmu), dmu_stride, _p(dvalue), dvalue_stride
     a.partials, a.num_blocks = _p(partials), partials.shape[0]
     if dmu16 is not None:                  # bf16 copies of the head gradients (int16 bit patterns; *_off in bf16 elements)
-        if dmu16.dtype != torch.int16 or dvalue16 is None or dvalue16.dtype != torch.int16:
-            raise TypeError("ppo_loss: dmu16 / dvalue16 must be int16 (bf16 bit pattern) CUDA tensors")
-        a.dmu16, a.dmu16_stride = dmu16.data_ptr() + 2 * dmu16_off, dmu16_stride
-        a.dvalue16, a.dvalue16_stride = dvalue16.data_ptr() + 2 * dvalue16_off, dvalue16_stride
-    _lib.check(_lib.load().pulse_ppo_loss(ctypes.byref(a), _stream()), "pulse_ppo_loss")
+        if dvalue16 is None:
+            raise TypeError("ppo_loss: dmu16 goes with dvalue16")
+        a.dmu16, a.dmu16_stride = _b16(dmu16, "ppo_loss: dmu16", dmu16_off), dmu16_stride
+        a.dvalue16, a.dvalue16_stride = _b16(dvalue16, "ppo_loss: dvalue16", dvalue16_off), dvalue16_stride
+    _launch("pulse_ppo_loss", ctypes.byref(a))
 
 
 def advantage_normalize(returns, values, adv_out, partials):
     """adv = (returns - values - mean) / (std + 1e-8) over flat tensors (common_agent.py:589-599)."""
     n = returns.numel()
-    lib = _lib.load()
-    _lib.check(lib.pulse_advantage_moments(_p(returns), _p(values), n, _p(adv_out), _p(partials), partials.shape[0], _stream()),
-               "pulse_advantage_moments")
-    _lib.check(lib.pulse_advantage_normalize(_p(adv_out), n, _p(partials), partials.shape[0], _stream()), "pulse_advantage_normalize")
+    _launch("pulse_advantage_moments", _p(returns), _p(values), n, _p(adv_out), _p(partials), partials.shape[0])
+    _launch("pulse_advantage_normalize", _p(adv_out), n, _p(partials), partials.shape[0])
     return adv_out
 
 
 def sqnorm_partial(x, count, partials):
-    _chk(x, "x"), _chk(partials, "partials")
+    xp, pp = _p(x, "x"), _p(partials, "partials")
     if x.numel() < count or not x.is_contiguous():
         raise ValueError(f"sqnorm_partial: x must be a contiguous buffer of at least {count} floats")
-    _lib.check(_lib.load().pulse_sqnorm_partial(_p(x), count, _p(partials), partials.numel(), _stream()), "pulse_sqnorm_partial")
+    _launch("pulse_sqnorm_partial", xp, count, pp, partials.numel())
 
 
 def disc_head(logits, b, scale, dlogits, stats):
     """AMPAgent._disc_loss head on the (3b, 1) logit column (any row stride): fills ``dlogits`` (same shape) and ``stats`` (8 floats:
     pred loss, agent BCE, demo BCE, agent acc, demo acc, agent logit mean, demo logit mean, 0)."""
-    _chk(logits, "logits"), _chk(dlogits, "dlogits"), _chk(stats, "stats")
+    lp, dp, sp = _p(logits, "logits"), _p(dlogits, "dlogits"), _p(stats, "stats")
     if logits.shape[0] != 3 * b or dlogits.shape[0] != 3 * b or stats.numel() < 8 or not stats.is_contiguous():
         raise ValueError("disc_head: logits / dlogits must have 3b rows and stats 8 contiguous floats")
-    _lib.check(_lib.load().pulse_disc_head(_p(logits), logits.stride(0), b, float(scale), _p(dlogits), dlogits.stride(0), _p(stats), _stream()),
-               "pulse_disc_head")
+    _launch("pulse_disc_head", lp, logits.stride(0), b, float(scale), dp, dlogits.stride(0), sp)
 
 
 def disc_head_b16(logits, b, scale, dlogits16, stats, dlogits=None, bias_grad=None):
     """disc_head writing the logit gradients as bf16 (dlogits16: int16 (>= 3b, pitch) tensor, column 0) and optionally as fp32 too;
     ``bias_grad`` (a float32 view, element 0): receives their sum = the logit bias' gradient."""
-    _chk(logits, "logits"), _chk(stats, "stats"), _chk(dlogits, "dlogits"), _chk(bias_grad, "bias_grad", contiguous=False)
+    lp, sp, dp, bp = _p(logits, "logits"), _p(stats, "stats"), _p(dlogits, "dlogits"), _p(bias_grad, "bias_grad", unit_stride=False)
     if dlogits16.dtype != torch.int16 or not dlogits16.is_cuda or dlogits16.shape[0] < 3 * b or logits.shape[0] != 3 * b or stats.numel() < 8:
         raise ValueError("disc_head_b16: logits must have 3b rows, dlogits16 be an int16 CUDA tensor of >= 3b rows, stats 8 floats")
-    _lib.check(_lib.load().pulse_disc_head_b16(_p(logits), logits.stride(0), b, float(scale), _p(dlogits), dlogits.stride(0) if dlogits is not None else 0,
-                                               dlogits16.data_ptr(), dlogits16.stride(0), _p(stats), _p(bias_grad), _stream()), "pulse_disc_head_b16")
+    _launch("pulse_disc_head_b16", lp, logits.stride(0), b, float(scale), dp, dlogits.stride(0) if dlogits is not None else 0, dlogits16.data_ptr(),
+            dlogits16.stride(0), sp, bp)
 
 
 def transpose_to_b16(x, out, *, rows, cols, ld_in, ld_out, batch=1, stride_in=0, stride_out=0, x_off=0, out_off=0):
     """out[z][c][r] = bf16(x[z][r][c]); x fp32 base tensor (+ x_off floats), out int16 base tensor (+ out_off elements)."""
-    _chk(x, "x")
-    if out.dtype != torch.int16 or not out.is_cuda:
-        raise TypeError("transpose_to_b16: out must be an int16 CUDA tensor")
-    _lib.check(_lib.load().pulse_transpose_to_b16(x.data_ptr() + 4 * x_off, ld_in, rows, cols, out.data_ptr() + 2 * out_off, ld_out, batch, stride_in,
-                                                  stride_out, _stream()), "pulse_transpose_to_b16")
+    _launch("pulse_transpose_to_b16", _p(x, "x", off=x_off), ld_in, rows, cols, _b16(out, "transpose_to_b16: out", out_off), ld_out, batch, stride_in,
+            stride_out)
 
 
 def colsum_partial_b16(x, m, n, ld, num_chunks, partial, ld_partial, x_off=0, partial_off=0):
-    if x.dtype != torch.int16 or not x.is_cuda:
-        raise TypeError("colsum_partial_b16: x must be an int16 (bf16 bit pattern) CUDA tensor")
-    _chk(partial, "partial")
-    _lib.check(_lib.load().pulse_colsum_partial_b16(x.data_ptr() + 2 * x_off, m, n, ld, num_chunks, partial.data_ptr() + 4 * partial_off, ld_partial,
-                                                    _stream()), "pulse_colsum_partial_b16")
+    _launch("pulse_colsum_partial_b16", _b16(x, "colsum_partial_b16: x", x_off), m, n, ld, num_chunks, _p(partial, "partial", off=partial_off), ld_partial)
 
 
 def disc_penalty(G, rows, cols, scale, partials, out32=None, out16=None, out32_off=0, out16_off=0, ld32=0, ld16=0):
     """partials[block] = sum G^2; out32 / out16 (+ element offsets) = scale * G as fp32 / bf16."""
-    _chk(G, "G"), _chk(partials, "partials"), _chk(out32, "out32")
-    if out16 is not None and (out16.dtype != torch.int16 or not out16.is_cuda):
-        raise TypeError("disc_penalty: out16 must be an int16 CUDA tensor")
-    _lib.check(_lib.load().pulse_disc_penalty(G.data_ptr(), G.stride(0), rows, cols, float(scale),
-                                              (out32.data_ptr() + 4 * out32_off) if out32 is not None else None, ld32,
-                                              (out16.data_ptr() + 2 * out16_off) if out16 is not None else None, ld16,
-                                              partials.data_ptr(), partials.numel(), _stream()), "pulse_disc_penalty")
+    _launch("pulse_disc_penalty", _p(G, "G"), G.stride(0), rows, cols, float(scale), _p(out32, "out32", off=out32_off), ld32,
+            _b16(out16, "disc_penalty: out16", out16_off) if out16 is not None else None, ld16, _p(partials, "partials"), partials.numel())
 
 
 def disc_reg(flat, grad, ranges, partials):
     """ranges: [(offset, length, alpha)] (<= 4).  grad[off + i] += alpha * flat[off + i]; partials (blocks, 4) = per-block sums of flat[range]^2."""
-    _chk(flat, "flat"), _chk(grad, "grad"), _chk(partials, "partials")
+    fp, gp, pp = _p(flat, "flat"), _p(grad, "grad"), _p(partials, "partials")
     n = len(ranges)
     if not 1 <= n <= 4 or partials.dim() != 2 or partials.shape[1] != 4 or not partials.is_contiguous():
         raise ValueError("disc_reg: 1..4 ranges, partials (blocks, 4) contiguous")
     offs = (ctypes.c_int64 * n)(*[int(r[0]) for r in ranges])
     lens = (ctypes.c_int64 * n)(*[int(r[1]) for r in ranges])
     als = (ctypes.c_float * n)(*[float(r[2]) for r in ranges])
-    _lib.check(_lib.load().pulse_disc_reg(flat.data_ptr(), _p(grad), n, offs, lens, als, partials.data_ptr(), partials.shape[0], _stream()), "pulse_disc_reg")
+    _launch("pulse_disc_reg", fp, gp, n, offs, lens, als, pp, partials.shape[0])
 
 
 def carve_reduce_regions(base, parts, max_regions=8):
@@ -813,7 +723,7 @@ class ReduceGrads:
         n = len(regions)
         if not 1 <= n <= 32:
             raise ValueError("ReduceGrads: 1..32 regions")
-        _chk(slabs, "slabs"), _chk(out, "out"), _chk(flat, "flat")
+        _p(slabs, "slabs"), _p(out, "out"), _p(flat, "flat")
         self.n = n
         self.offs = (ctypes.c_int64 * n)(*[int(r[0]) for r in regions])
         self.cnts = (ctypes.c_int64 * n)(*[int(r[1]) for r in regions])
@@ -821,14 +731,14 @@ class ReduceGrads:
         self.als = (ctypes.c_float * n)(*[float(r[3]) for r in regions])
         self._src_keep = [r[4] if len(r) > 4 else None for r in regions]          # (the tensors stay alive with the launch)
         for t in self._src_keep:
-            _chk(t, "region src", contiguous=False)
+            _p(t, "region src", unit_stride=False)
         self.srcs = (ctypes.c_void_p * n)(*[(t.data_ptr() if t is not None else None) for t in self._src_keep])
         self.sstr = (ctypes.c_int64 * n)(*[(int(r[5]) if len(r) > 5 and r[4] is not None else 0) for r in regions])
         self.slabs, self.stride, self.out, self.flat = slabs, int(slab_stride), out, flat
         self.has_alpha = any(float(r[3]) != 0.0 for r in regions)
 
     def run(self, scale=1.0, sq_partials=None, w2_partials=None, num_blocks=1024, alphas=None):
-        _chk(sq_partials, "sq_partials"), _chk(w2_partials, "w2_partials")
+        sq, w2 = _p(sq_partials, "sq_partials"), _p(w2_partials, "w2_partials")
         if alphas is not None:                       # per-call regulariser coefficients (one per region)
             if len(alphas) != self.n:
                 raise ValueError("ReduceGrads: one alpha per region")
@@ -840,27 +750,23 @@ class ReduceGrads:
             raise ValueError("ReduceGrads: w2_partials must be (num_blocks, 8) contiguous, num_blocks = sq_partials.numel() (default 1024)")
         if (w2_partials is not None or self.has_alpha) and self.flat is None:
             raise ValueError("ReduceGrads: regulariser terms need the flat parameter buffer")
-        _lib.check(_lib.load().pulse_reduce_grads(self.slabs.data_ptr(), self.stride, self.n, self.offs, self.cnts, self.nsl, self.als, self.srcs, self.sstr,
-                                                  self.out.data_ptr(), float(scale), _p(self.flat), _p(sq_partials), _p(w2_partials), num_blocks, _stream()),
-                   "pulse_reduce_grads")
+        _launch("pulse_reduce_grads", self.slabs.data_ptr(), self.stride, self.n, self.offs, self.cnts, self.nsl, self.als, self.srcs, self.sstr,
+                self.out.data_ptr(), float(scale), _p(self.flat), sq, w2, num_blocks)
 
 
 def disc_reward(logits, n, scale, out):
-    _chk(logits, "logits", contiguous=False), _chk(out, "out", contiguous=False)
-    _lib.check(_lib.load().pulse_disc_reward(logits.data_ptr(), logits.stride(0), n, float(scale), out.data_ptr(), out.stride(0), _stream()), "pulse_disc_reward")
+    _launch("pulse_disc_reward", _p(logits, "logits", unit_stride=False), logits.stride(0), n, float(scale), _p(out, "out", unit_stride=False), out.stride(0))
 
 
 def adam_step(params, grads, exp_avg, exp_avg_sq, count, *, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
               max_norm=0.0, sqnorm_partials=None, grad_norm_out=None):
     for t, nm in ((params, "params"), (grads, "grads"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"), (sqnorm_partials, "sqnorm_partials"),
                   (grad_norm_out, "grad_norm_out")):
-        _chk(t, nm)
+        _p(t, nm)
         if t is not None and nm in ("params", "grads", "exp_avg", "exp_avg_sq") and (t.numel() < count or not t.is_contiguous()):
             raise ValueError(f"adam_step: {nm} must be a contiguous buffer of at least {count} floats")
-    _lib.check(_lib.load().pulse_adam_step(_p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), count, float(lr), beta1, beta2,
-                                           eps, weight_decay, int(step), float(max_norm), _p(sqnorm_partials),
-                                           sqnorm_partials.numel() if sqnorm_partials is not None else 0, _p(grad_norm_out),
-                                           _stream()), "pulse_adam_step")
+    _launch("pulse_adam_step", _p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), count, float(lr), beta1, beta2, eps, weight_decay, int(step),
+            float(max_norm), _p(sqnorm_partials), sqnorm_partials.numel() if sqnorm_partials is not None else 0, _p(grad_norm_out))
 
 
 def adam_step_multi(groups, *, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, max_norm=0.0, sqnorm_partials=None, grad_norm_out=None):
@@ -868,19 +774,17 @@ def adam_step_multi(groups, *, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, weigh
     n = len(groups)
     if not 1 <= n <= 4:
         raise ValueError("adam_step_multi: 1..4 groups")
-    _chk(sqnorm_partials, "sqnorm_partials"), _chk(grad_norm_out, "grad_norm_out")
+    sq, gn = _p(sqnorm_partials, "sqnorm_partials"), _p(grad_norm_out, "grad_norm_out")
     cols = [[], [], [], []]
     for g in groups:
         for k, nm in enumerate(("params", "grads", "exp_avg", "exp_avg_sq")):
-            _chk(g[k], nm)
+            cols[k].append(_p(g[k], nm))
             if g[k].numel() < g[4] or not g[k].is_contiguous():
                 raise ValueError(f"adam_step_multi: {nm} must be a contiguous buffer of at least {g[4]} floats")
-            cols[k].append(g[k].data_ptr())
     arrs = [(ctypes.c_void_p * n)(*c) for c in cols]
     counts = (ctypes.c_int64 * n)(*[int(g[4]) for g in groups])
-    _lib.check(_lib.load().pulse_adam_step_multi(n, arrs[0], arrs[1], arrs[2], arrs[3], counts, float(lr), beta1, beta2, eps, weight_decay, int(step),
-                                                 float(max_norm), _p(sqnorm_partials), sqnorm_partials.numel() if sqnorm_partials is not None else 0,
-                                                 _p(grad_norm_out), _stream()), "pulse_adam_step_multi")
+    _launch("pulse_adam_step_multi", n, *arrs, counts, float(lr), beta1, beta2, eps, weight_decay, int(step), float(max_norm), sq,
+            sqnorm_partials.numel() if sqnorm_partials is not None else 0, gn)
 
 
 def rollout_record(*, rewards, dones, terminate, value_raw, value_stride, value_mean, value_var, value_eps, buf_rewards, buf_next_values,
@@ -889,38 +793,32 @@ def rollout_record(*, rewards, dones, terminate, value_raw, value_stride, value_
     """play_steps bookkeeping of one rollout step in one launch (include/pulse_hip.h section 2c)."""
     a = _lib.RolloutRecordArgs()
     a.num_envs = rewards.numel()
-    a.rewards, a.reward_scale, a.reward_shift = _chk(rewards, "rewards"), float(reward_scale), float(reward_shift)
-    a.dones, a.terminate = _chk(dones, "dones", torch.int64), _chk(terminate, "terminate", torch.int64)
-    _chk(done_mask, "done_mask", torch.uint8), _chk(current_rewards, "current_rewards"), _chk(current_lengths, "current_lengths")
-    _chk(meter_rewards, "meter_rewards"), _chk(meter_lengths, "meter_lengths"), _chk(value_mean, "value_mean", torch.float64)
-    _chk(value_var, "value_var", torch.float64)
+    a.rewards, a.reward_scale, a.reward_shift = _p(rewards, "rewards"), float(reward_scale), float(reward_shift)
+    a.dones, a.terminate = _p(dones, "dones", _I64), _p(terminate, "terminate", _I64)
     a.value_raw, a.value_stride = _p(value_raw), int(value_stride)
-    a.value_mean, a.value_var, a.value_eps = _p(value_mean), _p(value_var), float(value_eps)
+    a.value_mean, a.value_var, a.value_eps = _p(value_mean, "value_mean", _F64), _p(value_var, "value_var", _F64), float(value_eps)
     a.buf_rewards, a.buf_next_values, a.buf_dones, a.env_stride = _p(buf_rewards), _p(buf_next_values), _p(buf_dones), int(env_stride)
-    a.current_rewards, a.current_lengths = _p(current_rewards), _p(current_lengths)
-    a.meter_rewards, a.meter_lengths, a.meter_max_size = _p(meter_rewards), _p(meter_lengths), float(meter_max_size)
-    a.done_mask, a.buf_terminate = _p(done_mask), _p(buf_terminate)
+    a.current_rewards, a.current_lengths = _p(current_rewards, "current_rewards"), _p(current_lengths, "current_lengths")
+    a.meter_rewards, a.meter_lengths, a.meter_max_size = _p(meter_rewards, "meter_rewards"), _p(meter_lengths, "meter_lengths"), float(meter_max_size)
+    a.done_mask, a.buf_terminate = _p(done_mask, "done_mask", torch.uint8), _p(buf_terminate)
     if meter_partials is not None:          # (blocks, 4) row of this step: the meter updates are applied later by rollout_meters
-        _chk(meter_partials, "meter_partials")
+        a.meter_partials, a.meter_blocks = _p(meter_partials, "meter_partials"), meter_partials.shape[0]
         if meter_partials.dim() != 2 or meter_partials.shape[1] != 4 or not meter_partials.is_contiguous():
             raise ValueError("rollout_record: meter_partials must be a contiguous (blocks, 4) tensor")
-        a.meter_partials, a.meter_blocks = meter_partials.data_ptr(), meter_partials.shape[0]
-    _lib.check(_lib.load().pulse_rollout_record(ctypes.byref(a), _stream()), "pulse_rollout_record")
+    _launch("pulse_rollout_record", ctypes.byref(a))
 
 
 def rollout_meters(partials, meter_rewards, meter_lengths, meter_max_size):
     """The deferred AverageMeter updates of a rollout: partials (steps, blocks, 4) from rollout_record(meter_partials=partials[step])."""
-    _chk(partials, "partials"), _chk(meter_rewards, "meter_rewards"), _chk(meter_lengths, "meter_lengths")
+    pp, rp, lp = _p(partials, "partials"), _p(meter_rewards, "meter_rewards"), _p(meter_lengths, "meter_lengths")
     if partials.dim() != 3 or partials.shape[2] != 4 or not partials.is_contiguous():
         raise ValueError("rollout_meters: partials must be a contiguous (steps, blocks, 4) tensor")
-    _lib.check(_lib.load().pulse_rollout_meters(partials.data_ptr(), partials.shape[0], partials.shape[1], meter_rewards.data_ptr(), meter_lengths.data_ptr(),
-                                               float(meter_max_size), _stream()), "pulse_rollout_meters")
+    _launch("pulse_rollout_meters", pp, partials.shape[0], partials.shape[1], rp, lp, float(meter_max_size))
 
 
 def kinematic_sim_step(target_rb, noise_rb, rb, target_dof_pos, noise_dof_pos, dof_pos, target_dof_vel, noise_dof_vel, dof_vel, force_src,
                        dof_force):
     n, j = rb.shape[0], rb.shape[1]
-    _lib.check(_lib.load().pulse_kinematic_sim_step(_p(target_rb), _p(noise_rb), _p(rb), n, j, _p(target_dof_pos), _p(noise_dof_pos),
-                                                    _p(dof_pos), _p(target_dof_vel), _p(noise_dof_vel), _p(dof_vel), _p(force_src),
-                                                    _p(dof_force), dof_pos.shape[1], _stream()), "pulse_kinematic_sim_step")
+    _launch("pulse_kinematic_sim_step", _p(target_rb), _p(noise_rb), _p(rb), n, j, _p(target_dof_pos), _p(noise_dof_pos), _p(dof_pos), _p(target_dof_vel),
+            _p(noise_dof_vel), _p(dof_vel), _p(force_src), _p(dof_force), dof_pos.shape[1])
 

@@ -300,7 +300,7 @@ class DiscNetwork:
                 plain.append((lin.w.off, lin.w.rows * lin.w.pitch, ns, 0.0))
                 plain.append((lin.b.off, lin.b.rows * lin.b.pitch, S, 0.0))
             assert plain[-1][0] + plain[-1][1] == self.n_flat and all(a[0] + a[1] == b[0] for a, b in zip(plain, plain[1:]))
-            parts = {r[0]: r for r in getattr(ws["wgrad"], "partial_reduces", [])}
+            parts = {r[0]: r for r in ws["wgrad"].partial_reduces}
             regions = []
             for off, cnt, nsl, al0 in plain:
                 pr = parts.pop(off, None)

@@ -392,6 +392,8 @@ class MlpGraph:
 
 
 def _concat_plans(a, b):
+    # only the launches are joined: ``partial_reduces`` stays empty (an MlpGraph's plans register none -- their gradient reduce is not fused)
+    # and ``bf16`` is spent once a plan's descriptors are built
     p = K.Plan()
     p.ops = a.ops + b.ops
     return p

@@ -512,7 +512,7 @@ class A2CNetwork:
         """Regions of the whole-gradient reduce: every layer's range with the slabs its launch wrote, and -- carved out of those -- every range
         whose partials the plan registered (Plan.call_partial_reduce), summed from their own buffers.  More than 8 regions (deep MLPs): the
         plan keeps its small reduces and the ranges are reduced one by one."""
-        regions, fused = K.carve_reduce_regions(self._slab_regions(ws), getattr(plan, "partial_reduces", []))
+        regions, fused = K.carve_reduce_regions(self._slab_regions(ws), plan.partial_reduces)
         ws["reduce_all_fused"] = fused
         return K.ReduceGrads(self._slabs, self.n_flat, regions, self.grad) if len(regions) <= 8 else None
 

@@ -21,39 +21,15 @@ import torch
 
 from . import _lib
 from ._lib import PULSE_IM_RESET, PULSE_IM_REWARD, PULSE_IM_SELF_OBS, PULSE_IM_TASK_OBS, AmpObsArgs, ImStepArgs, RewardSpecs
+from ._marshal import Filler, check as _dev, launch as _launch, mask_u8, ptr as _ptr, rows2d, select_envs, step_outputs
 
 DEFAULT_REWARD_SPECS = {"k_pos": 100.0, "k_rot": 10.0, "k_vel": 0.1, "k_ang_vel": 0.1,
                         "w_pos": 0.5, "w_rot": 0.3, "w_vel": 0.1, "w_ang_vel": 0.1}
 
 
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream():
-    """The current torch stream of the current device as a hipStream_t.  Called once per kernel launch: the raw accessor is ~20x cheaper than
-    building a torch.cuda.Stream object (8 us under a profiler, a tenth of the rollout's host time)."""
-    if _raw_stream is not None:
-        return ctypes.c_void_p(_raw_stream(torch.cuda.current_device()))
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _dev(t, name, dtype=torch.float32):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name}: expected a torch.Tensor, got {type(t)}")
-    if not t.is_cuda:
-        raise ValueError(f"{name}: tensor must live on the GPU (pulse_amd has no CPU path)")
-    if t.dtype != dtype:
-        raise TypeError(f"{name}: expected dtype {dtype}, got {t.dtype}")
-    return t
-
-
 def _c(t, name, dtype=torch.float32):
-    t = _dev(t, name, dtype)
+    t = _dev(t, name, dtype)             # (a tensor that is not on the GPU is a ValueError in this module)
     return t if t.is_contiguous() else t.contiguous()
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 # --------------------------------------------------------------------------- #
@@ -70,14 +46,14 @@ def quat_mul(a, b):
     if a.shape != b.shape:
         raise AssertionError("quat_mul: shape mismatch")  # the reference asserts equal shapes
     out = torch.empty_like(a)
-    _lib.check(_lib.load().pulse_quat_mul(_ptr(a), _ptr(b), _ptr(out), _rows(a, 4, "a"), _stream()), "pulse_quat_mul")
+    _launch("pulse_quat_mul", _ptr(a), _ptr(b), _ptr(out), _rows(a, 4, "a"))
     return out
 
 
 def quat_conjugate(a):
     a = _c(a, "a")
     out = torch.empty_like(a)
-    _lib.check(_lib.load().pulse_quat_conjugate(_ptr(a), _ptr(out), _rows(a, 4, "a"), _stream()), "pulse_quat_conjugate")
+    _launch("pulse_quat_conjugate", _ptr(a), _ptr(out), _rows(a, 4, "a"))
     return out
 
 
@@ -87,7 +63,7 @@ def my_quat_rotate(q, v):
     if _rows(v, 3, "v") != m:
         raise ValueError("my_quat_rotate: q and v row counts differ")
     out = torch.empty_like(v)
-    _lib.check(_lib.load().pulse_quat_rotate(_ptr(q), _ptr(v), _ptr(out), m, _stream()), "pulse_quat_rotate")
+    _launch("pulse_quat_rotate", _ptr(q), _ptr(v), _ptr(out), m)
     return out
 
 
@@ -96,28 +72,28 @@ def quat_to_angle_axis(q):
     m = _rows(q, 4, "q")
     angle = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
     axis = torch.empty(q.shape[:-1] + (3,), dtype=torch.float32, device=q.device)
-    _lib.check(_lib.load().pulse_quat_to_angle_axis(_ptr(q), _ptr(angle), _ptr(axis), m, _stream()), "pulse_quat_to_angle_axis")
+    _launch("pulse_quat_to_angle_axis", _ptr(q), _ptr(angle), _ptr(axis), m)
     return angle, axis
 
 
 def quat_to_exp_map(q):
     q = _c(q, "q")
     out = torch.empty(q.shape[:-1] + (3,), dtype=torch.float32, device=q.device)
-    _lib.check(_lib.load().pulse_quat_to_exp_map(_ptr(q), _ptr(out), _rows(q, 4, "q"), _stream()), "pulse_quat_to_exp_map")
+    _launch("pulse_quat_to_exp_map", _ptr(q), _ptr(out), _rows(q, 4, "q"))
     return out
 
 
 def quat_to_tan_norm(q):
     q = _c(q, "q")
     out = torch.empty(q.shape[:-1] + (6,), dtype=torch.float32, device=q.device)
-    _lib.check(_lib.load().pulse_quat_to_tan_norm(_ptr(q), _ptr(out), _rows(q, 4, "q"), _stream()), "pulse_quat_to_tan_norm")
+    _launch("pulse_quat_to_tan_norm", _ptr(q), _ptr(out), _rows(q, 4, "q"))
     return out
 
 
 def exp_map_to_quat(e):
     e = _c(e, "exp_map")
     out = torch.empty(e.shape[:-1] + (4,), dtype=torch.float32, device=e.device)
-    _lib.check(_lib.load().pulse_exp_map_to_quat(_ptr(e), _ptr(out), _rows(e, 3, "exp_map"), _stream()), "pulse_exp_map_to_quat")
+    _launch("pulse_exp_map_to_quat", _ptr(e), _ptr(out), _rows(e, 3, "exp_map"))
     return out
 
 
@@ -128,28 +104,28 @@ def slerp(q0, q1, t):
     if q1.shape != q0.shape or t.numel() != m:
         raise ValueError("slerp: shape mismatch")
     out = torch.empty_like(q0)
-    _lib.check(_lib.load().pulse_slerp(_ptr(q0), _ptr(q1), _ptr(t), _ptr(out), m, _stream()), "pulse_slerp")
+    _launch("pulse_slerp", _ptr(q0), _ptr(q1), _ptr(t), _ptr(out), m)
     return out
 
 
 def calc_heading(q):
     q = _c(q, "q")
     out = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
-    _lib.check(_lib.load().pulse_calc_heading(_ptr(q), _ptr(out), _rows(q, 4, "q"), _stream()), "pulse_calc_heading")
+    _launch("pulse_calc_heading", _ptr(q), _ptr(out), _rows(q, 4, "q"))
     return out
 
 
 def calc_heading_quat(q):
     q = _c(q, "q")
     out = torch.empty_like(q)
-    _lib.check(_lib.load().pulse_calc_heading_quat(_ptr(q), _ptr(out), _rows(q, 4, "q"), 0, _stream()), "pulse_calc_heading_quat")
+    _launch("pulse_calc_heading_quat", _ptr(q), _ptr(out), _rows(q, 4, "q"), 0)
     return out
 
 
 def calc_heading_quat_inv(q):
     q = _c(q, "q")
     out = torch.empty_like(q)
-    _lib.check(_lib.load().pulse_calc_heading_quat(_ptr(q), _ptr(out), _rows(q, 4, "q"), 1, _stream()), "pulse_calc_heading_quat")
+    _launch("pulse_calc_heading_quat", _ptr(q), _ptr(out), _rows(q, 4, "q"), 1)
     return out
 
 
@@ -162,12 +138,6 @@ def _specs_struct(specs=None, power_coef=0.0005, power_reward=True):
         s.update(specs)
     return RewardSpecs(s["k_pos"], s["k_rot"], s["k_vel"], s["k_ang_vel"], s["w_pos"], s["w_rot"], s["w_vel"],
                        s["w_ang_vel"], float(power_coef), 1 if power_reward else 0)
-
-
-def _ids32(ids, device):
-    if isinstance(ids, torch.Tensor):
-        return ids.to(device=device, dtype=torch.int32).contiguous()
-    return torch.tensor(list(ids), dtype=torch.int32, device=device)
 
 
 def pack_rb(body_pos, body_rot, body_vel, body_ang_vel):
@@ -245,21 +215,41 @@ def im_step(rb, *, what, ref_now=None, ref_next=None, time_steps=1, dof_force=No
     Low-level entry: one launch of pulse_im_step.  ``rb`` is (N, J, 13) with unit inner strides
     (the env stride may be larger).  ref_* are dicts with keys pos/rot/vel/ang.  Outputs that are
     not supplied are allocated.  Returns dict(obs, rew, rew_raw, reset, terminate)."""
+    kw = {k: v for k, v in locals().items() if k not in ("rb", "cache", "obs_copy")}       # first statement: exactly the other parameters
+    sig = _im_step_signature(rb, **kw) if cache is not None else None
+    if cache is not None and cache.get("sig") == sig:
+        a, out, fill = cache["args"], cache["out"], None
+    else:
+        a, out, fill, owned = _im_step_fill(rb, **kw)
+    if "obs" in out:
+        a.obs_copy, a.obs_copy_stride = _obs_copy_fields(obs_copy, a.num_envs, a.obs_cols, rb.device)
+    elif obs_copy is not None:
+        raise ValueError("obs_copy without an observation stage")
+    _launch("pulse_im_step", ctypes.byref(a))
+    if cache is not None and fill is not None:
+        cache.clear()
+        if owned and not fill.copied:
+            cache.update(sig=sig, args=a, keep=fill.keep, out=out)
+    return out
+
+
+def _im_step_signature(rb, **kw):
+    """The identity of an im_step launch for its cache: everything the struct-filling body receives -- a keyword added to im_step is part
+    of it without being listed anywhere -- and the module's debug bits as they are now."""
+    return _launch_sig((rb, kw, _IM_DEBUG_BITS))
+
+
+def _im_step_fill(rb, *, what, ref_now, ref_next, time_steps, dof_force, dof_vel, progress, pass_time, cycle_counter, track_ids, reset_ids, term_dist,
+                  reset_use_mean, full_body_reward, obs_version, local_root_obs, root_height_obs, specs, power_coef, power_reward, env_ids, env_mask,
+                  obs, obs_cols, rew, rew_raw, reset, terminate, clock, motion, upright, enable_early_termination, self_obs_version, force_sensor,
+                  dof_pos, ref_next_dof_pos, smpl_params, limb_weights, recovery_counter, zero_out_far, occl_bits, occl_reset):
+    """im_step's struct-filling body -> (pulse_im_step_args without its obs_copy fields, the outputs dict, the Filler that keeps the
+    struct's tensors alive, whether every output is the caller's).  Only a launch whose outputs are all caller-owned may be replayed: an
+    output this wrapper allocates would be a new buffer on every call."""
     lib = _lib.load()
-    if cache is not None:
-        sig = _launch_sig((rb, what, ref_now, ref_next, time_steps, dof_force, dof_vel, progress, pass_time, cycle_counter, track_ids, reset_ids, term_dist,
-                           reset_use_mean, full_body_reward, obs_version, local_root_obs, root_height_obs, specs, power_coef, power_reward, env_ids, env_mask,
-                           obs, obs_cols, rew, rew_raw, reset, terminate, clock, motion, upright, enable_early_termination, self_obs_version, force_sensor,
-                           dof_pos, ref_next_dof_pos, smpl_params, limb_weights, recovery_counter, zero_out_far, occl_bits, occl_reset, _IM_DEBUG_BITS))
-        if cache.get("sig") == sig:
-            ca = cache["args"]
-            ca.obs_copy, ca.obs_copy_stride = _obs_copy_fields(obs_copy, ca.num_envs, ca.obs_cols, rb.device)
-            _lib.check(lib.pulse_im_step(ctypes.byref(ca), _stream()), "pulse_im_step")
-            return cache["out"]
-        # only launches whose outputs are all caller-owned are replayed (an output this wrapper allocates would be a new buffer every call)
-        owned = ((obs is not None or not what & (PULSE_IM_SELF_OBS | PULSE_IM_TASK_OBS)) and
-                 ((rew is not None and rew_raw is not None) or not what & PULSE_IM_REWARD) and
-                 ((reset is not None and terminate is not None) or not what & PULSE_IM_RESET))
+    owned = ((obs is not None or not what & (PULSE_IM_SELF_OBS | PULSE_IM_TASK_OBS)) and
+             ((rew is not None and rew_raw is not None) or not what & PULSE_IM_REWARD) and
+             ((reset is not None and terminate is not None) or not what & PULSE_IM_RESET))
     rb = _dev(rb, "rb")
     hist = 1
     if self_obs_version == 2:                      # (N, H, J, 13) history, oldest first (compute_humanoid_observations_smpl_max_v2)
@@ -277,19 +267,8 @@ def im_step(rb, *, what, ref_now=None, ref_next=None, time_steps=1, dof_force=No
         rb_stride = rb.stride()[0]
     dev = rb.device
     a = ImStepArgs()
-    keep = []  # keep temporaries alive until the call returns
-
-    copied = []                                    # arguments that had to be converted into a temporary: such a launch is never replayed from the cache
-
-    def P(t, name, dtype=torch.float32):
-        if t is None:
-            return None
-        t2 = _c(t, name, dtype)
-        if t2.data_ptr() != t.data_ptr():
-            copied.append(name)
-        keep.append(t2)
-        return t2.data_ptr()
-
+    P = Filler()
+    P.keep.append(rb)
     a.rb, a.rb_env_stride, a.num_envs, a.num_bodies = rb.data_ptr(), rb_stride, n, j
     a.upright_start, a.enable_early_termination = int(bool(upright)), int(bool(enable_early_termination))
     a.self_obs_version, a.hist_steps = int(self_obs_version), hist
@@ -302,7 +281,7 @@ def im_step(rb, *, what, ref_now=None, ref_next=None, time_steps=1, dof_force=No
             _dev(t, name)
             if t.dim() != 2 or t.shape[0] != n or t.stride(1) != 1:
                 raise ValueError(f"{name}: (num_envs, width) with contiguous rows expected")
-            keep.append(t)
+            P.keep.append(t)
             setattr(a, name, t.data_ptr()); setattr(a, name + "_width", t.shape[1]); setattr(a, name + "_stride", t.stride(0))
             fsw += t.shape[1]
     if recovery_counter is not None:
@@ -320,18 +299,7 @@ def im_step(rb, *, what, ref_now=None, ref_next=None, time_steps=1, dof_force=No
     a.dof_pos, a.ref_next_dof_pos = P(dof_pos, "dof_pos"), P(ref_next_dof_pos, "ref_next_dof_pos")
     if dof_pos is not None and dof_force is None:
         a.num_dof = dof_pos.shape[-1]
-    if env_ids is not None:
-        ids_in = env_ids
-        env_ids = _c(env_ids, "env_ids", torch.int64)
-        if env_ids.data_ptr() != ids_in.data_ptr():
-            copied.append("env_ids")
-        keep.append(env_ids)
-        a.env_ids, a.num_ids = env_ids.data_ptr(), env_ids.numel()
-    if env_mask is not None:
-        m = env_mask
-        if m.dtype == torch.bool:
-            m = m.view(torch.uint8)                 # (a view: same memory, in-place edits stay visible to a replayed launch)
-        a.env_mask = P(m, "env_mask", torch.uint8)
+    select_envs(a, P, env_ids, env_mask)
     if ref_now is not None:
         a.ref_now_pos, a.ref_now_rot = P(ref_now["pos"], "ref_now.pos"), P(ref_now["rot"], "ref_now.rot")
         a.ref_now_vel, a.ref_now_ang = P(ref_now["vel"], "ref_now.vel"), P(ref_now["ang"], "ref_now.ang")
@@ -344,24 +312,12 @@ def im_step(rb, *, what, ref_now=None, ref_next=None, time_steps=1, dof_force=No
         a.num_dof = dof_force.shape[-1]
     a.progress = P(progress, "progress", torch.int64)
     if pass_time is not None:
-        pt = pass_time.view(torch.uint8) if pass_time.dtype == torch.bool else pass_time
-        a.pass_time = P(pt, "pass_time", torch.uint8)
+        a.pass_time = P(mask_u8(pass_time), "pass_time", torch.uint8)
     a.cycle_counter = P(cycle_counter, "cycle_counter", torch.int64)
-    # id lists: a Python list is part of the launch signature (its VALUES are), but a tensor that had to be converted (int64 ids, another
-    # device) would leave the cached struct pointing at a private copy that later in-place edits of the caller's tensor never reach:
-    # such a launch is not replayed from the cache
     if track_ids is not None:
-        t = _ids32(track_ids, dev)
-        if isinstance(track_ids, torch.Tensor) and t.data_ptr() != track_ids.data_ptr():
-            copied.append("track_ids")
-        keep.append(t)
-        a.track_ids, a.num_track = t.data_ptr(), t.numel()
+        a.track_ids, a.num_track = P.ids32(track_ids, "track_ids", dev)
     if reset_ids is not None:
-        t = _ids32(reset_ids, dev)
-        if isinstance(reset_ids, torch.Tensor) and t.data_ptr() != reset_ids.data_ptr():
-            copied.append("reset_ids")
-        keep.append(t)
-        a.reset_ids, a.num_reset = t.data_ptr(), t.numel()
+        a.reset_ids, a.num_reset = P.ids32(reset_ids, "reset_ids", dev)
     a.term_dist = P(term_dist, "term_dist")
     a.reset_use_mean, a.full_body_reward = int(reset_use_mean), int(full_body_reward)
     a.what, a.obs_version = what | _IM_DEBUG_BITS, obs_version
@@ -381,22 +337,8 @@ def im_step(rb, *, what, ref_now=None, ref_next=None, time_steps=1, dof_force=No
         a.obs, a.obs_stride = obs.data_ptr(), obs.stride()[0]
         a.obs_cols = width if obs_cols is None else obs_cols
         out["obs"] = obs
-        a.obs_copy, a.obs_copy_stride = _obs_copy_fields(obs_copy, n, a.obs_cols, dev)
-    elif obs_copy is not None:
-        raise ValueError("obs_copy without an observation stage")
-    if what & PULSE_IM_REWARD:
-        rw = 5 if power_reward else 4
-        rew = torch.empty(n, dtype=torch.float32, device=dev) if rew is None else _dev(rew, "rew")
-        rew_raw = torch.empty(n, rw, dtype=torch.float32, device=dev) if rew_raw is None else _dev(rew_raw, "rew_raw")
-        if not (rew.is_contiguous() and rew_raw.is_contiguous() and rew_raw.shape[-1] == rw):
-            raise ValueError("rew / rew_raw must be contiguous, rew_raw (N, 4|5)")
-        a.rew, a.rew_raw = rew.data_ptr(), rew_raw.data_ptr()
-        out["rew"], out["rew_raw"] = rew, rew_raw
-    if what & PULSE_IM_RESET:
-        reset = torch.empty(n, dtype=torch.int64, device=dev) if reset is None else _dev(reset, "reset", torch.int64)
-        terminate = torch.empty(n, dtype=torch.int64, device=dev) if terminate is None else _dev(terminate, "terminate", torch.int64)
-        a.reset, a.terminate = reset.data_ptr(), terminate.data_ptr()
-        out["reset"], out["terminate"] = reset, terminate
+    step_outputs(a, P, out, n, dev, reward=what & PULSE_IM_REWARD, resets=what & PULSE_IM_RESET, raw_width=5 if power_reward else 4,
+                 rew=rew, rew_raw=rew_raw, reset=reset, terminate=terminate)
     if clock is not None:
         a.progress_rw, a.progress_inc = P(clock.get("progress_rw"), "clock.progress_rw", torch.int64), int(clock.get("inc", 0))
         a.clock_dt = float(clock.get("dt", 0.0))
@@ -405,7 +347,7 @@ def im_step(rb, *, what, ref_now=None, ref_next=None, time_steps=1, dof_force=No
         a.cycle_motion, a.max_episode_length = int(bool(clock.get("cycle_motion", False))), int(clock.get("max_episode_length", 0))
         pto = clock.get("pass_time_out")
         if pto is not None:
-            a.pass_time_out = P(pto.view(torch.uint8) if pto.dtype == torch.bool else pto, "clock.pass_time_out", torch.uint8)
+            a.pass_time_out = P(mask_u8(pto), "clock.pass_time_out", torch.uint8)
     if motion is not None:
         a.use_motion = 1
         motion["lib"].fill_tables(a.motion)
@@ -415,12 +357,7 @@ def im_step(rb, *, what, ref_now=None, ref_next=None, time_steps=1, dof_force=No
         if trb is not None:
             a.track_rb, a.track_rb_stride = P(trb, "motion.track_rb"), trb.stride(0)
         a.track_dof_pos, a.track_dof_vel = P(motion.get("track_dof_pos"), "motion.track_dof_pos"), P(motion.get("track_dof_vel"), "motion.track_dof_vel")
-    _lib.check(lib.pulse_im_step(ctypes.byref(a), _stream()), "pulse_im_step")
-    if cache is not None:
-        cache.clear()
-        if owned and not copied:
-            cache.update(sig=sig, args=a, keep=keep + [rb], out=out)
-    return out
+    return a, out, P, owned
 
 
 def compute_humanoid_observations_smpl_max(body_pos, body_rot, body_vel, body_ang_vel, smpl_params=None,
@@ -457,10 +394,6 @@ def remove_base_rot(quat):
     """phc/env/tasks/humanoid.py:1616-1620."""
     base = torch.tensor([[-0.5, -0.5, -0.5, 0.5]], dtype=torch.float32, device=quat.device).repeat(quat.shape[0], 1)
     return quat_mul(quat, base)
-
-
-def _split_task_only(full, self_w):
-    return full[:, self_w:]
 
 
 def compute_imitation_observations_v6(root_pos, root_rot, body_pos, body_rot, body_vel, body_ang_vel,
@@ -627,12 +560,12 @@ def im_eval_accum(rb, ref_pos, num_steps, step, ring, accum, *, env_mask=None):
     a.ref_pos, a.ref_env_stride = ref_pos.data_ptr(), ref_pos.stride(0) if n > 1 else 3 * j
     a.num_envs, a.num_bodies, a.num_steps, a.step = n, j, num_steps.data_ptr(), int(step)
     if env_mask is not None:
-        m = env_mask.view(torch.uint8) if env_mask.dtype == torch.bool else _dev(env_mask, "env_mask", torch.uint8)
-        if not m.is_cuda or tuple(m.shape) != (n,) or not m.is_contiguous():
+        m = _dev(env_mask, "env_mask", torch.uint8)
+        if tuple(m.shape) != (n,) or not m.is_contiguous():
             raise ValueError(f"env_mask: contiguous device {(n,)} bool / uint8 expected")
         a.env_mask = m.data_ptr()
     a.ring, a.accum, a.accum_stride = ring.data_ptr(), accum.data_ptr(), accum.stride(0) if n > 1 else 8
-    _lib.check(_lib.load().pulse_im_eval_accum(ctypes.byref(a), _stream()), "pulse_im_eval_accum")
+    _launch("pulse_im_eval_accum", ctypes.byref(a))
     return accum
 
 
@@ -650,35 +583,18 @@ def task_step(task, rb, *, what, prev_root_pos=None, dt=1.0 / 30.0, tar_speed=No
     n, j = rb.shape[0], rb.shape[1]
     dev = rb.device
     a = TaskStepArgs()
-    keep = []
-
-    def P(t, name, dtype=torch.float32):
-        if t is None:
-            return None
-        t = _c(t, name, dtype)
-        keep.append(t)
-        return t.data_ptr()
-
+    P = Filler()
     a.task = {"speed": TASK_SPEED, "reach": TASK_REACH, "strike": TASK_STRIKE}[task]
     a.what, a.num_envs = what, n
     a.rb, a.rb_env_stride, a.num_bodies = rb.data_ptr(), rb.stride()[0], j
-    if env_ids is not None:
-        env_ids = _c(env_ids, "env_ids", torch.int64)
-        keep.append(env_ids)
-        a.env_ids, a.num_ids = env_ids.data_ptr(), env_ids.numel()
-    if env_mask is not None:
-        a.env_mask = P(env_mask.view(torch.uint8) if env_mask.dtype == torch.bool else env_mask, "env_mask", torch.uint8)
+    select_envs(a, P, env_ids, env_mask)
     a.prev_root_pos, a.dt = P(prev_root_pos, "prev_root_pos"), float(dt)
     a.tar_speed, a.tar_pos, a.reach_body_id = P(tar_speed, "tar_speed"), P(tar_pos, "tar_pos"), int(reach_body_id)
     a.tar_states, a.tar_contact_forces = P(tar_states, "tar_states"), P(tar_contact_forces, "tar_contact_forces")
-    for name, ids in (("strike", strike_body_ids), ("contact", contact_body_ids)):
-        if ids is not None:
-            t = _ids32(ids, dev)
-            keep.append(t)
-            if name == "strike":
-                a.strike_body_ids, a.num_strike = t.data_ptr(), t.numel()
-            else:
-                a.contact_body_ids, a.num_contact_ids = t.data_ptr(), t.numel()
+    if strike_body_ids is not None:
+        a.strike_body_ids, a.num_strike = P.ids32(strike_body_ids, "strike_body_ids", dev)
+    if contact_body_ids is not None:
+        a.contact_body_ids, a.num_contact_ids = P.ids32(contact_body_ids, "contact_body_ids", dev)
     a.contact_forces, a.termination_heights = P(contact_forces, "contact_forces"), P(termination_heights, "termination_heights")
     a.progress, a.max_episode_length = P(progress, "progress", torch.int64), float(max_episode_length)
     a.enable_early_termination = int(bool(enable_early_termination))
@@ -693,18 +609,11 @@ def task_step(task, rb, *, what, prev_root_pos=None, dt=1.0 / 30.0, tar_speed=No
         _dev(obs, "obs")
         a.obs, a.obs_stride, a.obs_offset = obs.data_ptr(), obs.stride()[0], int(obs_offset)
         out["obs"] = obs
-    if what & TASK_REWARD:
-        rw = 2 if power_reward else 1
-        rew = torch.empty(n, dtype=torch.float32, device=dev) if rew is None else _dev(rew, "rew")
-        rew_raw = torch.empty(n, rw, dtype=torch.float32, device=dev) if rew_raw is None else _dev(rew_raw, "rew_raw")
-        a.rew, a.rew_raw, a.rew_raw_width = rew.data_ptr(), rew_raw.data_ptr(), rew_raw.shape[-1]
-        out["rew"], out["rew_raw"] = rew, rew_raw
-    if what & TASK_RESET:
-        reset = torch.empty(n, dtype=torch.int64, device=dev) if reset is None else _dev(reset, "reset", torch.int64)
-        terminate = torch.empty(n, dtype=torch.int64, device=dev) if terminate is None else _dev(terminate, "terminate", torch.int64)
-        a.reset, a.terminate = reset.data_ptr(), terminate.data_ptr()
-        out["reset"], out["terminate"] = reset, terminate
-    _lib.check(lib.pulse_task_step(ctypes.byref(a), _stream()), "pulse_task_step")
+    if what & TASK_REWARD:                     # (a caller's rew_raw sets the raw-reward width the kernel writes)
+        a.rew_raw_width = rew_raw.shape[-1] if rew_raw is not None else (2 if power_reward else 1)
+    step_outputs(a, P, out, n, dev, reward=what & TASK_REWARD, resets=what & TASK_RESET, raw_width=a.rew_raw_width,
+                 rew=rew, rew_raw=rew_raw, reset=reset, terminate=terminate)
+    _launch("pulse_task_step", ctypes.byref(a))
     return out
 
 
@@ -718,22 +627,29 @@ def amp_obs_width(num_joints, num_key_bodies, root_height_obs=True, *, version=1
     return _lib.load().pulse_amp_obs_width_v(num_joints, num_key_bodies, int(root_height_obs), int(version), int(num_shape), int(num_limb))
 
 
-def _amp_variant(a, fn, rows, upright, version, shape_params, limb_weights, dev, keep):
-    """The fields pulse_amp_obs_args and pulse_amp_hist_args share: upright_start, version, the optional shape / limb rows (``rows`` of them)."""
+def _amp_variant(a, P, fn, rows, dev, *, key_body_ids, joint_ids, all_joints, local_root_obs, root_height_obs, upright, version, shape_params,
+                 limb_weights):
+    """The fields pulse_amp_obs_args and pulse_amp_hist_args share: the key-body / joint selection (``all_joints`` without one), the root
+    options, upright_start, version, the optional shape / limb rows (``rows`` of them).  -> the frame width they give."""
     if version not in (1, 2):
         raise ValueError(f"{fn}: version must be 1 or 2, got {version!r}")
+    a.key_body_ids, a.num_key_bodies = P.ids32(key_body_ids, "key_body_ids", dev)
+    a.num_joints = all_joints
+    if joint_ids is not None:
+        a.joint_ids, a.num_joints = P.ids32(joint_ids, "joint_ids", dev)
+    a.local_root_obs, a.root_height_obs = int(local_root_obs), int(root_height_obs)
     a.upright_start, a.version = int(bool(upright)), int(version)
     for name, t in (("shape_params", shape_params), ("limb_weights", limb_weights)):
         if t is None:
             continue
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != rows:
             raise TypeError(f"{fn}: {name} must be a ({rows}, k) float32 tensor on {dev} with unit column stride")
-        keep.append(t)
+        P.keep.append(t)
         if name == "shape_params":
             a.shape_params, a.shape_stride, a.num_shape = t.data_ptr(), t.stride(0), t.shape[1]
         else:
             a.limb_weights, a.limb_stride, a.num_limb = t.data_ptr(), t.stride(0), t.shape[1]
-    return a.num_shape, a.num_limb
+    return _lib.load().pulse_amp_obs_width_v(a.num_joints, a.num_key_bodies, a.root_height_obs, a.version, a.num_shape, a.num_limb)
 
 
 def build_amp_observations_smpl(rb, dof_pos, dof_vel, key_body_ids, *, joint_ids=None, zero_joints=(), local_root_obs=True,
@@ -744,35 +660,20 @@ def build_amp_observations_smpl(rb, dof_pos, dof_vel, key_body_ids, *, joint_ids
     read as zero (:636-639); ``upright`` False: remove_base_rot first (:929-930); ``shape_params`` (N, k) / ``limb_weights`` (N, k) rows are
     appended (has_shape_obs_disc / has_limb_weight_obs, :963-966; pass the truncated view ``humanoid_shapes[:, :-6]``).
     Writes the first W columns of ``out`` rows (any row pitch) and returns ``out``."""
-    lib = _lib.load()
     rb = _dev(rb, "rb")
     n = rb.shape[0]
     dev = rb.device
-    dof_pos, dof_vel = _c(dof_pos, "dof_pos"), _c(dof_vel, "dof_vel")
-    kb = _ids32(key_body_ids, dev)
-    ji = _ids32(joint_ids, dev) if joint_ids is not None else None
-    nj = ji.numel() if ji is not None else dof_pos.shape[-1] // 3
     a = AmpObsArgs()
-    keep = [kb, ji, dof_pos, dof_vel]
-    ns, nl = _amp_variant(a, "build_amp_observations_smpl", n, upright, version, shape_params, limb_weights, dev, keep)
-    w = lib.pulse_amp_obs_width_v(nj, kb.numel(), int(root_height_obs), int(version), ns, nl)
+    P = Filler()
+    a.dof_pos, a.dof_vel, a.num_dof, a.num_envs = P(dof_pos, "dof_pos"), P(dof_vel, "dof_vel"), dof_pos.shape[-1], n
+    w = _amp_variant(a, P, "build_amp_observations_smpl", n, dev, key_body_ids=key_body_ids, joint_ids=joint_ids, all_joints=dof_pos.shape[-1] // 3,
+                     local_root_obs=local_root_obs, root_height_obs=root_height_obs, upright=upright, version=version, shape_params=shape_params,
+                     limb_weights=limb_weights)
     if out is None:
         out = torch.empty(n, w, dtype=torch.float32, device=dev)
     a.rb, a.rb_env_stride = rb.data_ptr(), rb.stride()[0]
-    a.dof_pos, a.dof_vel, a.num_dof, a.num_envs = dof_pos.data_ptr(), dof_vel.data_ptr(), dof_pos.shape[-1], n
-    if env_ids is not None:
-        env_ids = _c(env_ids, "env_ids", torch.int64)
-        keep.append(env_ids)
-        a.env_ids, a.num_ids = env_ids.data_ptr(), env_ids.numel()
-    if env_mask is not None:
-        m = env_mask.view(torch.uint8) if env_mask.dtype == torch.bool else env_mask
-        m = _c(m, "env_mask", torch.uint8)
-        keep.append(m)
-        a.env_mask = m.data_ptr()
-    a.joint_ids, a.num_joints = (ji.data_ptr() if ji is not None else None), nj
+    select_envs(a, P, env_ids, env_mask)
     a.zero_joint_mask = sum(1 << int(j) for j in zero_joints)
-    a.key_body_ids, a.num_key_bodies = kb.data_ptr(), kb.numel()
-    a.local_root_obs, a.root_height_obs = int(local_root_obs), int(root_height_obs)
     a.out, a.out_stride = out.data_ptr(), out.stride()[0]
     if hist_steps and hist_steps > 1:
         # ``out`` is slot 0 of the (N, hist_steps, W) history: shift + current frame (+ copy of the finished window) in this launch
@@ -783,7 +684,7 @@ def build_amp_observations_smpl(rb, dof_pos, dof_vel, key_body_ids, *, joint_ids
             a.window_out, a.window_stride = window_out.data_ptr(), window_out.stride(0)
     elif window_out is not None:
         raise ValueError("build_amp_observations_smpl: window_out goes with hist_steps > 1")
-    _lib.check(lib.pulse_amp_obs(ctypes.byref(a), _stream()), "pulse_amp_obs")
+    _launch("pulse_amp_obs", ctypes.byref(a))
     return out
 
 
@@ -792,33 +693,23 @@ def amp_hist_init(motion_lib, motion_ids, start_times, dt, env_mask, hist, key_b
     """_init_amp_obs_ref (humanoid_amp.py:531-563) for the masked envs: slots 1 .. S-1 of ``hist`` (N, S, W) := the AMP frames of each env's
     motion at start_times - dt * (k + 1), in one launch (pulse_amp_hist_init).  ``shape_params`` / ``limb_weights`` hold one row per MOTION
     (motion_bodies[:, :-6] / motion_limb_weights, :548-555); ``upright`` / ``version`` as build_amp_observations_smpl."""
-    lib = _lib.load()
     dev = hist.device
     if hist.dtype != torch.float32 or hist.dim() != 3 or hist.stride(2) != 1 or not hist.is_cuda:
         raise TypeError("amp_hist_init: hist must be a (N, S, W) float32 CUDA tensor")
     n, s_, w = hist.shape
-    ids = _c(motion_ids, "motion_ids", torch.int64)
-    st = _c(start_times, "start_times", torch.float32)
-    if ids.numel() != n or st.numel() != n:
+    if motion_ids.numel() != n or start_times.numel() != n:
         raise ValueError("amp_hist_init: one motion id / start time per env")
-    m = env_mask.view(torch.uint8) if env_mask.dtype == torch.bool else env_mask
-    m = _c(m, "env_mask", torch.uint8)
-    kb = _ids32(key_body_ids, dev)
-    ji = _ids32(joint_ids, dev) if joint_ids is not None else None
-    nj = ji.numel() if ji is not None else motion_lib.num_bodies - 1
     a = _lib.AmpHistArgs()
-    keep = []
-    ns, nl = _amp_variant(a, "amp_hist_init", motion_lib.num_motions(), upright, version, shape_params, limb_weights, dev, keep)
-    if lib.pulse_amp_obs_width_v(nj, kb.numel(), int(root_height_obs), int(version), ns, nl) != w:
+    P = Filler()
+    if _amp_variant(a, P, "amp_hist_init", motion_lib.num_motions(), dev, key_body_ids=key_body_ids, joint_ids=joint_ids,
+                    all_joints=motion_lib.num_bodies - 1, local_root_obs=local_root_obs, root_height_obs=root_height_obs, upright=upright,
+                    version=version, shape_params=shape_params, limb_weights=limb_weights) != w:
         raise ValueError("amp_hist_init: the history's frame width does not match the joint / key-body selection, version and rows")
     motion_lib.fill_tables(a.tab)
-    a.motion_ids, a.start_times, a.dt = ids.data_ptr(), st.data_ptr(), float(dt)
-    a.num_envs, a.env_mask, a.hist_steps = n, m.data_ptr(), s_
-    a.joint_ids, a.num_joints = (ji.data_ptr() if ji is not None else None), nj
-    a.key_body_ids, a.num_key_bodies = kb.data_ptr(), kb.numel()
-    a.local_root_obs, a.root_height_obs = int(local_root_obs), int(root_height_obs)
+    a.motion_ids, a.start_times, a.dt = P(motion_ids, "motion_ids", torch.int64), P(start_times, "start_times"), float(dt)
+    a.num_envs, a.env_mask, a.hist_steps = n, P(mask_u8(env_mask), "env_mask", torch.uint8), s_
     a.hist, a.env_stride, a.step_stride = hist.data_ptr(), hist.stride(0), hist.stride(1)
-    _lib.check(lib.pulse_amp_hist_init(ctypes.byref(a), _stream()), "pulse_amp_hist_init")
+    _launch("pulse_amp_hist_init", ctypes.byref(a))
     return hist
 
 
@@ -850,8 +741,7 @@ def discount_values(mb_fdones, mb_values, mb_rewards, mb_next_values, gamma, tau
     advs = torch.empty_strided(r.shape, r.stride(), dtype=torch.float32, device=r.device)
     rets = torch.empty_strided(r.shape, r.stride(), dtype=torch.float32, device=r.device) if return_returns else None
     gt = float(gamma) * float(tau)  # Python evaluates gamma * tau in double first
-    _lib.check(_lib.load().pulse_gae(_ptr(r), _ptr(v), _ptr(nv), _ptr(d), t, n, st, sn, float(gamma), gt,
-                                     _ptr(advs), _ptr(rets), _stream()), "pulse_gae")
+    _launch("pulse_gae", _ptr(r), _ptr(v), _ptr(nv), _ptr(d), t, n, st, sn, float(gamma), gt, _ptr(advs), _ptr(rets))
     return (advs, rets) if return_returns else advs
 
 
@@ -869,25 +759,21 @@ def traj_generate(rb, verts, u_dtheta, u_sharp, sharp_mask, u_heading, u_dspeed,
         raise ValueError("verts: contiguous (N, num_verts, 3) expected")
     seg_dt = episode_dur / (nv - 1)
     a = TrajGenArgs()
-    keep = []
-
-    def P(t, name, shape, dtype=torch.float32):
-        t = _c(t, name, dtype)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
-        keep.append(t)
-        return t.data_ptr()
+    P = Filler()
+    f32, u8, seg = torch.float32, torch.uint8, (n, nv - 1)
     a.num_envs, a.num_verts = n, nv
     if env_mask is not None:
-        a.env_mask = P(env_mask.view(torch.uint8) if env_mask.dtype == torch.bool else env_mask, "env_mask", (n,), torch.uint8)
+        a.env_mask = P(mask_u8(env_mask), "env_mask", u8, (n,))
     a.rb, a.rb_env_stride = rb.data_ptr(), rb.stride(0)
-    a.u_dtheta, a.u_sharp, a.u_dspeed = P(u_dtheta, "u_dtheta", (n, nv - 1)), P(u_sharp, "u_sharp", (n, nv - 1)), P(u_dspeed, "u_dspeed", (n, nv - 1))
-    a.sharp_mask = P(sharp_mask.view(torch.uint8) if sharp_mask.dtype == torch.bool else sharp_mask, "sharp_mask", (n, nv - 1), torch.uint8)
-    a.u_heading, a.u_speed0 = P(u_heading, "u_heading", (n,)), P(u_speed0, "u_speed0", (n,))
+    if any(t is None for t in (u_dtheta, u_sharp, sharp_mask, u_heading, u_dspeed, u_speed0)):
+        raise TypeError("traj_generate: every draw is required")
+    a.u_dtheta, a.u_sharp, a.u_dspeed = P(u_dtheta, "u_dtheta", f32, seg), P(u_sharp, "u_sharp", f32, seg), P(u_dspeed, "u_dspeed", f32, seg)
+    a.sharp_mask = P(mask_u8(sharp_mask), "sharp_mask", u8, seg)
+    a.u_heading, a.u_speed0 = P(u_heading, "u_heading", f32, (n,)), P(u_speed0, "u_speed0", f32, (n,))
     a.dtheta_scale, a.dspeed_scale, a.seg_dt = float(dtheta_max * seg_dt), float(accel_max * seg_dt), float(seg_dt)
     a.speed_min, a.speed_max = float(speed_min), float(speed_max)
     a.verts = verts.data_ptr()
-    _lib.check(_lib.load().pulse_traj_generate(ctypes.byref(a), _stream()), "pulse_traj_generate")
+    _launch("pulse_traj_generate", ctypes.byref(a))
     return verts
 
 
@@ -905,21 +791,9 @@ def traj_step(rb, verts, progress, *, what, dt, episode_dur, num_samples=10, sam
     n, j = rb.shape[0], rb.shape[1]
     dev = rb.device
     a = TrajStepArgs()
-    keep = []
-
-    def P(t, name, dtype=torch.float32):
-        if t is None:
-            return None
-        t = _c(t, name, dtype)
-        keep.append(t)
-        return t.data_ptr()
+    P = Filler()
     a.what, a.num_envs = what, n
-    if env_ids is not None:
-        env_ids = _c(env_ids, "env_ids", torch.int64)
-        keep.append(env_ids)
-        a.env_ids, a.num_ids = env_ids.data_ptr(), env_ids.numel()
-    if env_mask is not None:
-        a.env_mask = P(env_mask.view(torch.uint8) if env_mask.dtype == torch.bool else env_mask, "env_mask", torch.uint8)
+    select_envs(a, P, env_ids, env_mask)
     a.rb, a.rb_env_stride, a.num_bodies, a.upright_start = rb.data_ptr(), rb.stride(0), j, int(bool(upright))
     a.progress, a.dt = P(progress, "progress", torch.int64), float(dt)
     verts = _dev(verts, "verts")
@@ -935,7 +809,6 @@ def traj_step(rb, verts, progress, *, what, dt, episode_dur, num_samples=10, sam
         if heightsamples is not None:
             if heightsamples.dtype != torch.int16 or heightsamples.dim() != 2 or not heightsamples.is_contiguous() or not heightsamples.is_cuda:
                 raise TypeError("heightsamples: contiguous (rows, cols) int16 CUDA tensor expected")
-            keep.append(heightsamples)
             a.heightsamples, a.map_rows, a.map_cols = heightsamples.data_ptr(), heightsamples.shape[0], heightsamples.shape[1]
         a.horizontal_scale, a.vertical_scale = float(horizontal_scale), float(vertical_scale)
         if center_points is not None:
@@ -945,9 +818,7 @@ def traj_step(rb, verts, progress, *, what, dt, episode_dur, num_samples=10, sam
     a.num_dof = dof_force.shape[-1] if dof_force is not None else 0
     a.power_coef, a.power_reward, a.fuzzy_target = float(power_coef), int(bool(power_reward)), int(bool(fuzzy_target))
     if contact_body_ids is not None:
-        t = _ids32(contact_body_ids, dev)
-        keep.append(t)
-        a.contact_body_ids, a.num_contact_ids = t.data_ptr(), t.numel()
+        a.contact_body_ids, a.num_contact_ids = P.ids32(contact_body_ids, "contact_body_ids", dev)
     a.contact_forces, a.termination_heights = P(contact_forces, "contact_forces"), P(termination_heights, "termination_heights")
     a.max_episode_length, a.fail_dist = float(max_episode_length), float(fail_dist)
     a.enable_early_termination, a.terrain_reset, a.disable_collision = int(bool(enable_early_termination)), int(bool(terrain_reset)), int(bool(disable_collision))
@@ -959,33 +830,15 @@ def traj_step(rb, verts, progress, *, what, dt, episode_dur, num_samples=10, sam
         _dev(obs, "obs")
         a.obs, a.obs_stride, a.obs_offset = obs.data_ptr(), obs.stride(0), int(obs_offset)
         out["obs"] = obs
-    if what & TASK_REWARD:
-        rew = torch.empty(n, dtype=torch.float32, device=dev) if rew is None else _dev(rew, "rew")
-        rew_raw = torch.empty(n, 2, dtype=torch.float32, device=dev) if rew_raw is None else _dev(rew_raw, "rew_raw")
-        if not rew_raw.is_contiguous() or rew_raw.shape[-1] != 2:
-            raise ValueError("rew_raw: contiguous (N, 2) expected")
-        a.rew, a.rew_raw = rew.data_ptr(), rew_raw.data_ptr()
-        out["rew"], out["rew_raw"] = rew, rew_raw
-    if what & TASK_RESET:
-        reset = torch.empty(n, dtype=torch.int64, device=dev) if reset is None else _dev(reset, "reset", torch.int64)
-        terminate = torch.empty(n, dtype=torch.int64, device=dev) if terminate is None else _dev(terminate, "terminate", torch.int64)
-        a.reset, a.terminate = reset.data_ptr(), terminate.data_ptr()
-        out["reset"], out["terminate"] = reset, terminate
-    _lib.check(_lib.load().pulse_traj_step(ctypes.byref(a), _stream()), "pulse_traj_step")
+    step_outputs(a, P, out, n, dev, reward=what & TASK_REWARD, resets=what & TASK_RESET, raw_width=2, rew=rew, rew_raw=rew_raw, reset=reset,
+                 terminate=terminate)
+    _launch("pulse_traj_step", ctypes.byref(a))
     return out
 
 
 # --------------------------------------------------------------------------- #
 # MCP composer stage (include/pulse_hip.h section 4e)
 # --------------------------------------------------------------------------- #
-def _rows2d(t, name, rows, cols):
-    """A (rows, >= cols) float32 GPU view with unit column stride (the row stride is the pitch the kernel gets)."""
-    _dev(t, name)
-    if t.dim() != 2 or t.shape[0] != rows or t.shape[1] < cols or (t.numel() > 0 and (t.stride(1) != 1 or (rows > 1 and t.stride(0) < t.shape[1]))):
-        raise ValueError(f"{name}: expected a ({rows}, >= {cols}) view with unit column stride, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
-    return t
-
-
 def mcp_compose(weights, x, out=None, *, num_actions=None, discrete=False):
     """HumanoidImMCP.step's mixture (phc/env/tasks/humanoid_im_mcp.py:56-67): ``weights`` (N, P), ``x`` (N, P, a_pitch) -- the primitives'
     outputs side by side, rows may be pitched views -- -> actions (N, num_actions) = sum_k weights[:, k, None] * x[:, k, :num_actions].
@@ -994,7 +847,7 @@ def mcp_compose(weights, x, out=None, *, num_actions=None, discrete=False):
     if x.dim() != 3 or weights.dim() != 2 or x.shape[0] != weights.shape[0] or x.shape[1] != weights.shape[1]:
         raise ValueError(f"mcp_compose: weights (N, P) and x (N, P, a_pitch) expected, got {tuple(weights.shape)} and {tuple(x.shape)}")
     n, p = weights.shape
-    _rows2d(weights, "weights", n, p)
+    wp, ws = rows2d(weights, "weights", n, p)
     if x.numel() > 0 and (x.stride(2) != 1 or x.stride(1) < x.shape[2] or (n > 1 and x.stride(0) < p * x.stride(1))):
         raise ValueError(f"x: expected (N, P, a_pitch) rows with unit inner stride, got strides {tuple(x.stride())}")
     a = int(num_actions) if num_actions is not None else x.shape[2]
@@ -1002,7 +855,6 @@ def mcp_compose(weights, x, out=None, *, num_actions=None, discrete=False):
         raise ValueError(f"mcp_compose: num_actions = {a} outside 1 .. {x.shape[2]}")
     if out is None:
         out = torch.empty(n, a, dtype=torch.float32, device=x.device)
-    _rows2d(out, "out", n, a)
-    _lib.check(_lib.load().pulse_mcp_compose(_ptr(weights), weights.stride(0) if n else p, _ptr(x), x.stride(0) if n else p * x.stride(1), x.stride(1),
-                                             n, p, a, int(bool(discrete)), _ptr(out), out.stride(0) if n else a, _stream()), "pulse_mcp_compose")
+    op, os_ = rows2d(out, "out", n, a)
+    _launch("pulse_mcp_compose", wp, ws, _ptr(x), x.stride(0) if n else p * x.stride(1), x.stride(1), n, p, a, int(bool(discrete)), op, os_)
     return out[:, :a]
