@@ -36,7 +36,7 @@ extern "C" {
 #define PULSE_ERR_LAUNCH (-2)
 #define PULSE_ERR_UNSUPPORTED (-3)
 
-#define PULSE_ABI_VERSION 34
+#define PULSE_ABI_VERSION 35
 
 typedef void* pulse_stream_t; /* hipStream_t */
 
@@ -804,7 +804,17 @@ int pulse_disc_reward(const float* logits, int64_t logit_stride, int64_t n, floa
  * 4c. PULSE VAE head algebra (no autograd on the product path): form_embedding (amp_network_z_builder.py:79-121), the losses of
  *     AMPAgent._optimize_kin (amp_agent.py:771-849; kl_multi loss_functions.py:3-10) and their head-level gradients.
  *     Heads rows are [mu (E) | raw logvar (E)]; clamp_logvar applies clamp(logvar, -5, clamp_max) (use_vae_clamped_prior).
+ *     prior_mode (v35; amp_network_z_builder.py:226-241, 514-533; amp_agent.py:785-789):
+ *       LEARNED  prior heads [mu | raw logvar], clamped like the posterior's (use_vae_prior; wins when both switches are on)
+ *       FIXED    prior heads are the mean alone, E wide; log-variance = prior_fixed_logvar, NOT clamped (use_vae_fixed_prior);
+ *                sphere_prior: the mean goes through project_to_norm(., embedding_norm) first (acts in this mode only)
+ *       NONE     no prior heads; KL = -0.5 sum(1 + logvar - mu^2 - exp(logvar)) / rows; the regulariser is undefined
+ *     sphere_posterior (:118-119): z / (||z|| / embedding_norm + 1e-8) is what the decoder reads; the heads stay unprojected.
+ *     A zeroed new field is the behaviour of v34.
  * ------------------------------------------------------------------------- */
+#define PULSE_VAE_PRIOR_LEARNED 0
+#define PULSE_VAE_PRIOR_FIXED 1
+#define PULSE_VAE_PRIOR_NONE 2
 typedef struct pulse_vae_embed_args {
     const float* heads; int64_t heads_stride;   /* encoder heads (rows, >= 2E) */
     const float* eps; int64_t eps_stride;       /* re-parameterisation noise (rows, E) or NULL (z = mu, flags.test) */
@@ -813,20 +823,26 @@ typedef struct pulse_vae_embed_args {
     float* cin; int64_t cin_stride;             /* optional: critic input, self obs columns only */
     int32_t rows, embedding_size, self_obs_size, z_col;
     int32_t clamp_logvar; float clamp_max;
+    int32_t sphere_posterior; float embedding_norm;   /* needs embedding_size <= 32 */
 } pulse_vae_embed_args;
 int pulse_vae_embed(const pulse_vae_embed_args* args, pulse_stream_t s);
+/* HumanoidZ.compute_z_actions under the sphere posterior (humanoid_z.py:101-107): out = project_to_norm(a [+ b], norm); b may be NULL; cols <= 32 */
+int pulse_vae_project(const float* a, int64_t a_stride, const float* b, int64_t b_stride, float* out, int64_t out_stride, int32_t rows, int32_t cols,
+                      float norm, pulse_stream_t s);
 
 typedef struct pulse_vae_kin_args {
     const float* pred; int64_t pred_stride;     /* decoder output mu (rows, A) */
     const float* gt; int64_t gt_stride;         /* kin_dict['gt_action'] */
     const float* zheads; int64_t zheads_stride;
-    const float* pheads; int64_t pheads_stride; /* learned prior heads */
+    const float* pheads; int64_t pheads_stride; /* prior heads: (rows, 2E) LEARNED, (rows, E) FIXED, NULL allowed with NONE */
     const int64_t* progress;                    /* kin_dict['progress_buf'] (rows), env-major sequences of ``horizon`` steps */
     int32_t rows, num_actions, embedding_size, horizon;
     int32_t clamp_logvar; float clamp_max;
     int32_t use_ar1, use_regu;
     float* dmu; int64_t dmu_stride;             /* out: d mean||pred - gt|| / d pred */
     float* partials; int32_t num_blocks;        /* out: (num_blocks, 8) sums: action norm, KL, AR(1) norm, prior_mu^2, vae_mu^2, prior_lv^2, vae_lv^2, 0 */
+    int32_t prior_mode; float prior_fixed_logvar;
+    int32_t sphere_prior; float embedding_norm;
 } pulse_vae_kin_args;
 int pulse_vae_kin_loss(const pulse_vae_kin_args* args, pulse_stream_t s);
 
@@ -842,7 +858,10 @@ typedef struct pulse_vae_head_bwd_args {
     float c_ar1;   /* ar1_coefficient / (sequences * (horizon - 1)) or 0 */
     float c_regu;  /* 0.005 * 0.001 / (rows * E) or 0 */
     float* dzheads; int64_t dzheads_stride;     /* out (rows, 2E) */
-    float* dpheads; int64_t dpheads_stride;     /* out (rows, 2E), optional */
+    float* dpheads; int64_t dpheads_stride;     /* out (rows, 2E) LEARNED / (rows, E) FIXED, optional */
+    int32_t prior_mode; float prior_fixed_logvar;
+    int32_t sphere_prior, sphere_posterior;     /* sphere_posterior: dz is the gradient of the projected latent; z is recomputed from the heads and eps */
+    float embedding_norm;
 } pulse_vae_head_bwd_args;
 int pulse_vae_head_backward(const pulse_vae_head_bwd_args* args, pulse_stream_t s);
 int pulse_sizeof_vae_embed_args(void);

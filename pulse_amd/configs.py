@@ -41,6 +41,26 @@ ENV_IM_VAE = dict(ENV_IM, **{   # phc/data/cfg/env/env_im_vae.yaml:19-55 (PULSE 
     "use_vae_clamped_prior": True, "vae_var_clamp_max": 2, "kld_coefficient": 0.01, "kld_coefficient_min": 0.001, "kld_anneal": True,
     "ar1_coefficient": 0.005, "only_kin_loss": True, "distill": True, "save_kin_info": True, "cycle_motion": True})
 
+# Prior / posterior variants of the PULSE VAE (amp_network_z_builder.py:40-46, 118-119, 226-241, 514-533): env-dict overrides on top of
+# ENV_IM_VAE, e.g. make_agent("cfg3_small", env_overrides=vae_variant_env("fixed_sphere_post")).  No shipped config switches them on;
+# embedding_norm 2 and a non-zero fixed log-variance keep the variants apart from their defaults.
+VAE_VARIANTS = {
+    "learned": {},
+    "none": {"use_vae_prior": False},
+    "fixed": {"use_vae_prior": False, "use_vae_fixed_prior": True, "vae_prior_fixed_logvar": -0.5},
+    "fixed_sphere": {"use_vae_prior": False, "use_vae_fixed_prior": True, "vae_prior_fixed_logvar": -0.5, "use_vae_sphere_prior": True, "embedding_norm": 2},
+    "sphere_post": {"use_vae_sphere_posterior": True, "embedding_norm": 2},
+    "none_sphere_post": {"use_vae_prior": False, "use_vae_sphere_posterior": True, "embedding_norm": 2},
+    "fixed_sphere_post": {"use_vae_prior": False, "use_vae_fixed_prior": True, "vae_prior_fixed_logvar": -0.5, "use_vae_sphere_prior": True,
+                          "use_vae_sphere_posterior": True, "embedding_norm": 2},
+}
+
+
+def vae_variant_env(name, **extra):
+    """The env-dict overrides of a VAE_VARIANTS entry (a copy), for make_agent / make_env's ``env_overrides``."""
+    return dict(VAE_VARIANTS[name], **extra)
+
+
 NETWORK_Z_READER = {      # phc/data/cfg/learning/pulse_z_task.yaml:10-44 (network: amp_z_reader)
     "name": "amp_z_reader", "separate": True,
     "space": {"continuous": {"mu_activation": "None", "sigma_activation": "None", "mu_init": {"name": "default"},
@@ -205,8 +225,8 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
                "terrain_z": HT.HumanoidPedestrianTerrainZ}[env_kind]
         task = cls({"env": env_cfg} if humanoid == "smpl" else {"env": env_cfg, "robot": robot}, sim, device=device)
         znet = AMPZNetwork(NETWORK_Z, actions_num=69, self_obs_size=task.get_self_obs_size(), task_obs_size=576,
-                           task_obs_size_detail={"embedding_size": 32, "z_type": "vae", "use_vae_prior": True, "use_vae_clamped_prior": True,
-                                                 "vae_var_clamp_max": 2}, device=device)
+                           task_obs_size_detail=dict({"embedding_size": 32, "z_type": "vae", "use_vae_prior": True, "use_vae_clamped_prior": True,
+                                                      "vae_var_clamp_max": 2}, **task._z_detail), device=device)   # (the env dict's prior / posterior variant)
         rms = {"running_mean": torch.zeros(934, dtype=torch.float64), "running_var": torch.ones(934, dtype=torch.float64)}
         task.initialize_z_models({"model": znet.state_dict(), "running_mean_std": rms}, NETWORK_Z)
         return VecTaskPythonWrapper(task, rl_device=device), None

@@ -38,7 +38,13 @@ HONOURED = {
     # PULSE / distillation attributes the agent reads off the task (amp_agent.py:59-63, 773-832)
     "temp_running_mean", "kin_lr", "save_kin_info", "only_kin_loss", "distill", "z_type", "kld_coefficient", "kld_coefficient_min",
     "ar1_coefficient", "kld_anneal", "use_ar1_prior", "use_vae_prior", "use_vae_prior_regu", "embedding_size", "embedding_norm",
-    "use_vae_clamped_prior", "vae_var_clamp_max", "proj_norm", "auto_pmcp", "auto_pmcp_soft", "shape_resampling_interval", "fitting", "models",
+    "use_vae_clamped_prior", "vae_var_clamp_max", "proj_norm",
+    # prior / posterior variants of the PULSE VAE (amp_network_z_builder.py:40-46, 118-119, 226-241, 514-533; amp_agent.py:785-789;
+    # humanoid_z.py:44-48, 101-107).  use_vae_sphere_prior acts inside the fixed-prior branch only (:237-239): beside a learned prior, or
+    # with no prior at all, the reference ignores it and so does this package (accepted without effect).  When both use_vae_prior and
+    # use_vae_fixed_prior are on, the learned branch wins (if / elif in both places).
+    "use_vae_fixed_prior", "use_vae_sphere_prior", "use_vae_sphere_posterior", "vae_prior_fixed_logvar",
+    "auto_pmcp", "auto_pmcp_soft", "shape_resampling_interval", "fitting", "models",
     # MCP composer stage (humanoid_im_mcp.py:16-28): the action is a weight vector over num_prim frozen PNN primitives (env/humanoid_im_mcp.py)
     "num_prim", "discrete_moe", "has_pnn", "has_lateral", "z_activation",
     # get-up task (humanoid_im_getup.py:42-66)
@@ -76,7 +82,6 @@ INERT = {
     "hybridInitProb": "only read when stateInit is Hybrid (humanoid_amp.py:490-505), which raises here",
     "dict_size": "VQ dictionary size: only read for z_type vq_vae variants, which raise here",
     "embedding_partion": "VQ partition count: only read for z_type vq_vae variants, which raise here",
-    "vae_prior_fixed_logvar": "only read with use_vae_fixed_prior, which raises here",
     "num_env_group": "only read with divide_group, which raises here",
     "small_terrain": "debug switch of the terrain mesh creation (" + _SIM + ")",
 }
@@ -98,9 +103,6 @@ UNBUILT = {
     "z_readout": ((False,), "amp_network_z_builder.py:63, amp_network_z_reader_builder.py:36"),
     "z_all": ((False,), "amp_network_z_builder.py:37 (z fed to every decoder layer)"),
     "vae_prior_policy": ((False,), "amp_network_z_reader_builder.py:38-57"),
-    "use_vae_fixed_prior": ((False,), "amp_network_z_builder.py:102, 237, 529; amp_agent.py:785"),
-    "use_vae_sphere_prior": ((False,), "amp_network_z_builder.py:238"),
-    "use_vae_sphere_posterior": ((False,), "amp_network_z_builder.py:118; humanoid_z.py:106"),
     "distill_z_model": ((False,), "humanoid_im_distill.py:43-63, 186-231 (a PULSE model as the distillation teacher)"),
 }
 
@@ -117,9 +119,19 @@ def _inactive(key, value, env):
     return any(value == v for v in ok)
 
 
+def check_vae_options(env, where="HumanoidIm"):
+    """Combinations of the VAE switches the reference itself cannot run.  use_vae_prior_regu without a prior: _optimize_kin reads
+    ``prior_mu`` / ``prior_log_var`` that were never assigned (amp_agent.py:810-813 after the else branch of :785-789)."""
+    if env.get("use_vae_prior_regu", False) and not env.get("use_vae_prior", False) and not env.get("use_vae_fixed_prior", False):
+        raise NotImplementedError(f"{where}: use_vae_prior_regu without use_vae_prior / use_vae_fixed_prior: the regulariser reads the prior's mean "
+                                  "and log-variance, which do not exist without a prior; reference: phc/learning/amp_agent.py:810-813 "
+                                  "(prior_mu is unassigned there)")
+
+
 def audit(env, where="HumanoidIm"):
     """Raise NotImplementedError if ``env`` switches on behaviour of the reference that is not built; warn (once per key) about keys
     the reference does not read on this path."""
+    check_vae_options(env, where)
     bad = [k for k in env if k in UNBUILT and not _inactive(k, env[k], env)]
     if bad:
         lines = [f"  {k} = {env[k]!r}: not built (accepted: {UNBUILT[k][0]}); reference: phc/.../{UNBUILT[k][1]}" for k in bad]

@@ -316,8 +316,12 @@ class HumanoidIm:
         self.use_ar1_prior = bool(env.get("use_ar1_prior", False))
         self.use_vae_prior = bool(env.get("use_vae_prior", False))
         self.use_vae_prior_regu = bool(env.get("use_vae_prior_regu", False))
+        self.use_vae_fixed_prior = bool(env.get("use_vae_fixed_prior", False))     # the agent reads it off the task (amp_agent.py:785)
         self._task_obs_size_detail = {k: env[k] for k in ("embedding_size", "embedding_norm", "z_type", "use_vae_prior",
-                                                          "use_vae_clamped_prior", "vae_var_clamp_max") if k in env}
+                                                          "use_vae_clamped_prior", "vae_var_clamp_max", "use_vae_fixed_prior", "use_vae_sphere_prior",
+                                                          "use_vae_sphere_posterior", "vae_prior_fixed_logvar") if k in env}
+        if "use_vae_fixed_prior" in env:                # a dict that names the fixed prior leaves use_vae_prior at the reference's default
+            self._task_obs_size_detail.setdefault("use_vae_prior", False)
         self._task_obs_size_detail.setdefault("proj_norm", True)
         # ---- AMP observations (humanoid_amp.py:91-118, 296-314): (N, numAMPObsSteps, W) history, slot 0 = current frame
         self._enable_amp_obs = bool(env.get("enable_amp_obs", False))

@@ -408,6 +408,7 @@ class _ZMixin(HumanoidZ):
         env = cfg.get("env", cfg)
         self._embedding_size = int(env.get("embedding_size", 32))
         self.num_actions = self._embedding_size
+        self._read_z_options(env)
 
     def step(self, action_z):
         self.action_z = action_z

@@ -285,7 +285,31 @@ class Plan:
 # --------------------------------------------------------------------------- #
 # PULSE VAE head algebra (include/pulse_hip.h section 4c)
 # --------------------------------------------------------------------------- #
+# The three launches in the shipped form -- learned prior, Gaussian posterior -- keep their signatures; ``*_modes`` below take the prior /
+# posterior variants as further keywords whose defaults are that form (one C entry each: a zeroed mode field is the shipped form).
+PRIOR_LEARNED, PRIOR_FIXED, PRIOR_NONE = 0, 1, 2           # PULSE_VAE_PRIOR_* (pulse_hip.h)
+
+
 def vae_embed(heads, x, ain, *, rows, embedding_size, self_obs_size, z_col, eps=None, cin=None, clamp=True, clamp_max=2.0):
+    vae_embed_modes(heads, x, ain, rows=rows, embedding_size=embedding_size, self_obs_size=self_obs_size, z_col=z_col, eps=eps, cin=cin, clamp=clamp,
+                    clamp_max=clamp_max)
+
+
+def vae_kin_loss(pred, gt, zheads, pheads, progress, dmu, partials, *, rows, num_actions, embedding_size, horizon, clamp=True, clamp_max=2.0,
+                 use_ar1=True, use_regu=False):
+    vae_kin_loss_modes(pred, gt, zheads, pheads, progress, dmu, partials, rows=rows, num_actions=num_actions, embedding_size=embedding_size,
+                       horizon=horizon, clamp=clamp, clamp_max=clamp_max, use_ar1=use_ar1, use_regu=use_regu)
+
+
+def vae_head_backward(zheads, dzheads, *, rows, embedding_size, horizon=1, pheads=None, dpheads=None, eps=None, dz=None, progress=None, clamp=True,
+                      clamp_max=2.0, c_kl=0.0, c_ar1=0.0, c_regu=0.0):
+    vae_head_backward_modes(zheads, dzheads, rows=rows, embedding_size=embedding_size, horizon=horizon, pheads=pheads, dpheads=dpheads, eps=eps, dz=dz,
+                            progress=progress, clamp=clamp, clamp_max=clamp_max, c_kl=c_kl, c_ar1=c_ar1, c_regu=c_regu)
+
+
+def vae_embed_modes(heads, x, ain, *, rows, embedding_size, self_obs_size, z_col, eps=None, cin=None, clamp=True, clamp_max=2.0,
+                    sphere_posterior=False, embedding_norm=1.0):
+    """vae_embed with the posterior mode: ``sphere_posterior`` writes project_to_norm(z, embedding_norm) (embedding_size <= 32)."""
     a = _lib.VaeEmbedArgs()
     a.heads, a.heads_stride = _p(heads, "heads"), heads.stride(0)
     a.eps, a.eps_stride = _p(eps, "eps"), (eps.stride(0) if eps is not None else 0)
@@ -294,24 +318,36 @@ def vae_embed(heads, x, ain, *, rows, embedding_size, self_obs_size, z_col, eps=
     a.cin, a.cin_stride = _p(cin, "cin"), (cin.stride(0) if cin is not None else 0)
     a.rows, a.embedding_size, a.self_obs_size, a.z_col = rows, embedding_size, self_obs_size, z_col
     a.clamp_logvar, a.clamp_max = int(bool(clamp)), float(clamp_max)
+    a.sphere_posterior, a.embedding_norm = int(bool(sphere_posterior)), float(embedding_norm)
     _launch("pulse_vae_embed", ctypes.byref(a))
 
 
-def vae_kin_loss(pred, gt, zheads, pheads, progress, dmu, partials, *, rows, num_actions, embedding_size, horizon, clamp=True, clamp_max=2.0,
-                 use_ar1=True, use_regu=False):
+def vae_project(a, out, *, rows, cols, norm, b=None):
+    """out = project_to_norm(a [+ b], norm) row by row (phc/utils/torch_utils.py:38-43); cols <= 32."""
+    _launch("pulse_vae_project", _p(a, "a"), a.stride(0), _p(b, "b"), (b.stride(0) if b is not None else 0), _p(out, "out"), out.stride(0),
+            rows, cols, float(norm))
+
+
+def vae_kin_loss_modes(pred, gt, zheads, pheads, progress, dmu, partials, *, rows, num_actions, embedding_size, horizon, clamp=True, clamp_max=2.0,
+                       use_ar1=True, use_regu=False, prior_mode=PRIOR_LEARNED, prior_fixed_logvar=0.0, sphere_prior=False, embedding_norm=1.0):
+    """``pheads``: (rows, 2E) [mu | logvar] with PRIOR_LEARNED, (rows, E) with PRIOR_FIXED, None with PRIOR_NONE."""
     a = _lib.VaeKinArgs()
     a.pred, a.pred_stride, a.gt, a.gt_stride = _p(pred, "pred"), pred.stride(0), _p(gt, "gt"), gt.stride(0)
-    a.zheads, a.zheads_stride, a.pheads, a.pheads_stride = _p(zheads, "zheads"), zheads.stride(0), _p(pheads, "pheads"), pheads.stride(0)
+    a.zheads, a.zheads_stride = _p(zheads, "zheads"), zheads.stride(0)
+    a.pheads, a.pheads_stride = _p(pheads, "pheads"), (pheads.stride(0) if pheads is not None else 0)
     a.progress = _p(progress, "progress", torch.int64)
     a.rows, a.num_actions, a.embedding_size, a.horizon = rows, num_actions, embedding_size, horizon
     a.clamp_logvar, a.clamp_max, a.use_ar1, a.use_regu = int(bool(clamp)), float(clamp_max), int(bool(use_ar1)), int(bool(use_regu))
     a.dmu, a.dmu_stride = _p(dmu, "dmu"), dmu.stride(0)
     a.partials, a.num_blocks = _p(partials, "partials"), partials.shape[0]
+    a.prior_mode, a.prior_fixed_logvar = int(prior_mode), float(prior_fixed_logvar)
+    a.sphere_prior, a.embedding_norm = int(bool(sphere_prior)), float(embedding_norm)
     _launch("pulse_vae_kin_loss", ctypes.byref(a))
 
 
-def vae_head_backward(zheads, dzheads, *, rows, embedding_size, horizon=1, pheads=None, dpheads=None, eps=None, dz=None, progress=None, clamp=True,
-                      clamp_max=2.0, c_kl=0.0, c_ar1=0.0, c_regu=0.0):
+def vae_head_backward_modes(zheads, dzheads, *, rows, embedding_size, horizon=1, pheads=None, dpheads=None, eps=None, dz=None, progress=None, clamp=True,
+                            clamp_max=2.0, c_kl=0.0, c_ar1=0.0, c_regu=0.0, prior_mode=PRIOR_LEARNED, prior_fixed_logvar=0.0, sphere_prior=False,
+                      sphere_posterior=False, embedding_norm=1.0):
     a = _lib.VaeHeadBwdArgs()
     a.zheads, a.zheads_stride = _p(zheads, "zheads"), zheads.stride(0)
     a.pheads, a.pheads_stride = _p(pheads, "pheads"), (pheads.stride(0) if pheads is not None else 0)
@@ -323,6 +359,8 @@ def vae_head_backward(zheads, dzheads, *, rows, embedding_size, horizon=1, phead
     a.c_kl, a.c_ar1, a.c_regu = float(c_kl), float(c_ar1), float(c_regu)
     a.dzheads, a.dzheads_stride = _p(dzheads, "dzheads"), dzheads.stride(0)
     a.dpheads, a.dpheads_stride = _p(dpheads, "dpheads"), (dpheads.stride(0) if dpheads is not None else 0)
+    a.prior_mode, a.prior_fixed_logvar = int(prior_mode), float(prior_fixed_logvar)
+    a.sphere_prior, a.sphere_posterior, a.embedding_norm = int(bool(sphere_prior)), int(bool(sphere_posterior)), float(embedding_norm)
     _launch("pulse_vae_head_backward", ctypes.byref(a))
 
 

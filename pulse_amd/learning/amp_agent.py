@@ -498,9 +498,11 @@ class AMPAgent(CommonAgent):
         self.train_result.update(info)
 
     def _optimize_kin(self, ws, mb, kin_dict):
-        """amp_agent.py:771-849 (z_type 'vae', learned prior): action RMSE + kld_coefficient KL(q || prior) + ar1_coefficient AR(1) latent
-        smoothness (seams masked through progress_buf) + 0.005 regulariser, own Adam(kin_lr).  Head algebra: pulse_vae_kin_loss (losses +
-        d loss / d pred_action) and pulse_vae_head_backward (encoder / prior head gradients); no autograd."""
+        """amp_agent.py:771-849 (z_type 'vae'): action RMSE + kld_coefficient KL + ar1_coefficient AR(1) latent smoothness (seams masked
+        through progress_buf) + 0.005 regulariser, own Adam(kin_lr).  The KL is kl_multi against the learned or the fixed prior, or
+        -0.5 sum(1 + logvar - mu^2 - exp(logvar)) / B without one (:785-789: the reference reads ``use_vae_prior or use_vae_fixed_prior``
+        off the task, which hands the network the same two switches).  Head algebra: pulse_vae_kin_loss (losses + d loss / d pred_action) and
+        pulse_vae_head_backward (encoder / prior head gradients); no autograd."""
         task = self.vec_env.env.task
         model = self.model
         net = model.net
@@ -508,18 +510,22 @@ class AMPAgent(CommonAgent):
         if self.z_noise_provider is not None:
             ws["z_noise"] = self.z_noise_provider(mb)
         model.forward_actor(ws, mb)
-        model.compute_prior(ws)
+        has_prior = net.prior_mode != K.PRIOR_NONE
+        if has_prior:
+            model.compute_prior(ws)                                             # (never launched without a prior)
         g = ws["g"]
         E, t = net.embedding_size, self.horizon_length
         use_ar1, use_regu = bool(getattr(task, "use_ar1_prior", False)), bool(getattr(task, "use_vae_prior_regu", False))
+        if use_regu and not has_prior:
+            raise NotImplementedError("use_vae_prior_regu without use_vae_prior / use_vae_fixed_prior: amp_agent.py:810-813 reads an unassigned prior_mu")
         # (the experience buffer stores kin_dict as floats: progress values are small integers, exact either way)
         prog = kin_dict["progress_buf"].reshape(-1).to(torch.int64).contiguous() if use_ar1 else None
         if self._kin_partials is None:
             self._kin_partials = torch.zeros(256, 8, device=self.ppo_device)
         gt = gt_action if gt_action.stride(-1) == 1 else gt_action.contiguous()
-        K.vae_kin_loss(ws["mu"], gt, g.act_bufs["zheads"], g.act_bufs["pheads"], prog, ws["dmu"], self._kin_partials, rows=mb,
-                       num_actions=self.actions_num, embedding_size=E, horizon=t, clamp=net.use_vae_clamped_prior, clamp_max=net.vae_var_clamp_max,
-                       use_ar1=use_ar1, use_regu=use_regu)
+        K.vae_kin_loss_modes(ws["mu"], gt, g.act_bufs["zheads"], g.act_bufs["pheads"] if has_prior else None, prog, ws["dmu"], self._kin_partials,
+                             rows=mb, num_actions=self.actions_num, embedding_size=E, horizon=t, clamp=net.use_vae_clamped_prior,
+                             clamp_max=net.vae_var_clamp_max, use_ar1=use_ar1, use_regu=use_regu, **net.head_modes())
         # the loss terms from the per-workgroup partials in three small launches (fixed-order column sum, one scaling, one dot product) instead of
         # a dozen scalar ops: sums = [sum sq action error -> RMSE term, KL, AR(1), four regulariser sums, -]
         n_err = (mb // t) * (t - 1)

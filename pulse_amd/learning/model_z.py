@@ -5,7 +5,8 @@ Forward of the policy follows AMPZBuilder.Network.eval_actor (amp_network_z_buil
 encoder plan -> form_embedding (log-var clamp, re-parameterisation with fresh N(0,1) noise, :82-121) ->
 cat(self_obs, z) -> decoder plan -> mu.  The (B,32) head algebra is two fused launches (pulse_amd/csrc/vae_head.hip):
 pulse_vae_embed on the way forward, pulse_vae_head_backward (d z / d mu, d z / d logvar with the clamp mask, plus the KL / AR(1) /
-regulariser terms of _optimize_kin) when the decoder's input gradient comes back from the GEMM plans.  No autograd tape.
+regulariser terms of _optimize_kin) when the decoder's input gradient comes back from the GEMM plans.  No autograd tape.  The network's
+prior mode (learned / fixed / none) and its two sphere switches travel to the launches as compile-time-folded modes (net.head_modes()).
 """
 import torch
 
@@ -44,8 +45,9 @@ class AMPZModel(GraphModel):
             if eps is None:
                 eps = ws["_eps_buf"] = torch.empty(m, E, device=self.device)
             eps.normal_(generator=self.generator)
-        K.vae_embed(heads, ws["x"], g.act_bufs["ain"], rows=m, embedding_size=E, self_obs_size=S, z_col=net.z_col, eps=eps, cin=g.act_bufs["cin"],
-                    clamp=net.use_vae_clamped_prior, clamp_max=net.vae_var_clamp_max)
+        K.vae_embed_modes(heads, ws["x"], g.act_bufs["ain"], rows=m, embedding_size=E, self_obs_size=S, z_col=net.z_col, eps=eps, cin=g.act_bufs["cin"],
+                          clamp=net.use_vae_clamped_prior, clamp_max=net.vae_var_clamp_max, sphere_posterior=net.use_vae_sphere_posterior,
+                          embedding_norm=net.embedding_norm)
         ws["eps"] = eps
 
     def forward_actor(self, ws, m, need_grad=None):
@@ -63,9 +65,12 @@ class AMPZModel(GraphModel):
         ws["G"]["fwd_critic"].run()
 
     def compute_prior(self, ws, need_grad=False):
-        """compute_prior (:226-241): runs the prior MLP; the raw heads [mu | logvar] stay in the graph buffer 'pheads' (split_heads clamps)."""
+        """compute_prior (:226-241): runs the prior MLP; the raw heads ([mu | logvar] learned, mu fixed) stay in the graph buffer 'pheads'
+        (split_heads clamps / projects).  Without a prior there is nothing to run: None."""
+        if self.net.prior_mode == K.PRIOR_NONE:
+            return None
         ws["G"]["fwd_prior"].run()
-        return self.net.split_heads(ws["g"].act_bufs["pheads"])
+        return self.net.split_heads(ws["g"].act_bufs["pheads"], prior=True)
 
     # ---- backward
     def backward_actor(self, ws, kin=None):
@@ -77,15 +82,19 @@ class AMPZModel(GraphModel):
         ws["G"]["bwd_dec"].run()
         dz = g.grad("ain")[:, zc:zc + E]
         heads = g.act_bufs["zheads"]
-        kw = dict(rows=heads.shape[0], embedding_size=E, eps=ws["eps"], dz=dz, clamp=net.use_vae_clamped_prior, clamp_max=net.vae_var_clamp_max)
+        kw = dict(rows=heads.shape[0], embedding_size=E, eps=ws["eps"], dz=dz, clamp=net.use_vae_clamped_prior, clamp_max=net.vae_var_clamp_max,
+                  sphere_posterior=net.use_vae_sphere_posterior, **net.head_modes())
         if kin is not None:
-            kw.update(pheads=g.act_bufs["pheads"], dpheads=g.grad("pheads"), progress=kin.get("progress"), horizon=kin.get("horizon", 1),
+            if net.prior_mode != K.PRIOR_NONE:
+                kw.update(pheads=g.act_bufs["pheads"], dpheads=g.grad("pheads"))
+            kw.update(progress=kin.get("progress"), horizon=kin.get("horizon", 1),
                       c_kl=kin["c_kl"], c_ar1=kin.get("c_ar1", 0.0), c_regu=kin.get("c_regu", 0.0))
-        K.vae_head_backward(heads, g.grad("zheads"), **kw)
+        K.vae_head_backward_modes(heads, g.grad("zheads"), **kw)
         ws["G"]["bwd_enc"].run()
 
     def backward_prior(self, ws):
-        ws["G"]["bwd_prior"].run()                                  # d loss / d prior heads was written by backward_actor(kin=...)
+        if self.net.prior_mode != K.PRIOR_NONE:
+            ws["G"]["bwd_prior"].run()                                  # d loss / d prior heads was written by backward_actor(kin=...)
 
     def backward(self, ws, m, grad_scale=1.0, sq_partials=None, on_bucket=None):
         """PPO backward: actor (through the VAE) + critic; weight gradients of untouched sub-nets (the prior: kin pass only) are zero.

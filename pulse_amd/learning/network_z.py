@@ -1,7 +1,10 @@
 """PULSE VAE policy network (``network: amp_z``) on the gfx950 kernels.
 
-Mirrors AMPZBuilder.Network, phc/learning/amp_network_z_builder.py (z_type "vae", learned prior,
-non-RNN branch) with the sizes of learning/im_z_fit.yaml + env/env_im_vae.yaml:
+Mirrors AMPZBuilder.Network, phc/learning/amp_network_z_builder.py (z_type "vae", non-RNN branch) with the sizes of
+learning/im_z_fit.yaml + env/env_im_vae.yaml.  The prior is learned (use_vae_prior, the shipped form), fixed (use_vae_fixed_prior:
+z_prior + z_prior_mu only, constant log-variance vae_prior_fixed_logvar, the mean optionally on the sphere of radius embedding_norm:
+use_vae_sphere_prior) or absent (neither switch: no z_prior* parameters, KL against N(0, I)); use_vae_sphere_posterior projects z after
+the re-parameterisation (:118-119).  z_all, z_readout and z_type other than "vae" raise by name.
 
   encoder   z_mlp: obs(934) -> [1536,1024,512] SiLU -> Linear(160)            :469-492
             z_mu / z_logvar: Linear(160 -> 32) each                          :507-511
@@ -14,7 +17,7 @@ The heavy part (every Linear, forward and backward) runs as launch plans of the 
 re-parameterisation) and of the losses is tiny ((B,32)/(B,69) tensors) and is done with ordinary
 tensor ops by the caller between the plans; its gradients are fed back through ``seed_*``.
 
-Physical layout notes: z_mu|z_logvar and z_prior_mu|z_prior_logvar are each ONE stacked (64, .) matrix
+Physical layout notes: z_mu|z_logvar and (learned prior) z_prior_mu|z_prior_logvar are each ONE stacked (64, .) matrix
 (one GEMM, no gradient accumulation at their shared input); cat(self_obs, z) is a 392-float buffer with
 self_obs at columns 0..357 and z at 360..391 (16-byte aligned segment), the first decoder / critic layer's
 weight carries the same column layout.  ``state_dict`` speaks the reference's names and shapes.
@@ -36,9 +39,23 @@ class AMPZNetwork(GraphNetwork):
         self.z_type = d.get("z_type", "vae")
         if self.z_type != "vae":
             raise NotImplementedError("only z_type 'vae' (the shipped PULSE configuration) is built")
+        for k, where in (("z_all", "amp_network_z_builder.py:37, 52-55 (z fed to every decoder layer)"),
+                         ("z_readout", "amp_network_z_builder.py:63-64, amp_network_z_reader_builder.py:36")):
+            if d.get(k, False):
+                raise NotImplementedError(f"amp_z with {k}: not built; reference: phc/learning/{where}")
+        # the prior: learned (state-conditioned mean and log-variance) / fixed (learned mean, constant log-variance) / none (KL against
+        # N(0, I)); both places of the reference use ``if use_vae_prior / elif use_vae_fixed_prior`` (:232-241, 514-533): learned wins
         self.use_vae_prior = bool(d.get("use_vae_prior", True))
-        if not self.use_vae_prior:
-            raise NotImplementedError("fixed / absent priors are not built (use_vae_prior: True in env_im_vae.yaml)")
+        self.use_vae_fixed_prior = bool(d.get("use_vae_fixed_prior", False))
+        self.prior_mode = K.PRIOR_LEARNED if self.use_vae_prior else K.PRIOR_FIXED if self.use_vae_fixed_prior else K.PRIOR_NONE
+        self.vae_prior_fixed_logvar = float(d.get("vae_prior_fixed_logvar", 0))
+        # use_vae_sphere_prior acts inside the fixed-prior branch only (:237-239); with a learned prior or none it has no effect
+        self.use_vae_sphere_prior = bool(d.get("use_vae_sphere_prior", False))
+        self.sphere_prior = self.use_vae_sphere_prior and self.prior_mode == K.PRIOR_FIXED
+        self.use_vae_sphere_posterior = bool(d.get("use_vae_sphere_posterior", False))
+        self.embedding_norm = float(d.get("embedding_norm", 1))
+        if (self.sphere_prior or self.use_vae_sphere_posterior) and not self.embedding_norm > 0:
+            raise ValueError(f"embedding_norm {self.embedding_norm}: the sphere projections need a positive radius")
         self.use_vae_clamped_prior = bool(d.get("use_vae_clamped_prior", True))
         self.vae_var_clamp_max = float(d.get("vae_var_clamp_max", 2))
         self.units = [int(u) for u in params["mlp"]["units"]]
@@ -74,21 +91,26 @@ class AMPZNetwork(GraphNetwork):
                               final_linear=5 * E, final_dst="zenc", tag="enc")
         g.buffer("zheads", 2 * E)
         lins["zheads"] = g.linear(Linear(book, "a2c_network.z_heads", 5 * E, 2 * E), "zenc", "zheads", grad_ranges=[(0, 5 * E, ACT_NONE, None, 0)], tag="enc")
-        lins["z_prior"] = g.mlp("a2c_network.z_prior", "x", S, T, self.task_act, ["p1", "p2", "p3"][:len(T)], tag="prior")
-        last_p = ["p1", "p2", "p3"][len(T) - 1]
-        g.buffer("pheads", 2 * E)
-        lins["pheads"] = g.linear(Linear(book, "a2c_network.z_prior_heads", T[-1], 2 * E), last_p, "pheads",
-                                  grad_ranges=[(0, T[-1], self.task_act, last_p, 0)], tag="prior")
+        if self.prior_mode != K.PRIOR_NONE:
+            lins["z_prior"] = g.mlp("a2c_network.z_prior", "x", S, T, self.task_act, ["p1", "p2", "p3"][:len(T)], tag="prior")
+            last_p = ["p1", "p2", "p3"][len(T) - 1]
+            # learned: [z_prior_mu; z_prior_logvar] stacked; fixed: z_prior_mu alone, there is no z_prior_logvar (:529-533)
+            pw, pname = (2 * E, "a2c_network.z_prior_heads") if self.prior_mode == K.PRIOR_LEARNED else (E, "a2c_network.z_prior_mu")
+            g.buffer("pheads", pw)
+            lins["pheads"] = g.linear(Linear(book, pname, T[-1], pw), last_p, "pheads", grad_ranges=[(0, T[-1], self.task_act, last_p, 0)], tag="prior")
         # _build_critic_z_mlp (:559-580): its final Linear writes the z slot of the critic's concat buffer
         lins["critic_z_mlp"] = g.mlp("a2c_network.critic_z_mlp", "x", self.obs_size, T, self.task_act, ["q1", "q2", "q3"][:len(T)],
                                      final_linear=E, final_dst="cin", final_dst_col=self.z_col, tag="critic_z")
         return {"graph": g, "lins": lins}
 
     def _plans(self, g):
-        return {"fwd_enc": g.forward_plan({"enc"}), "fwd_prior": g.forward_plan({"prior"}), "fwd_dec": g.forward_plan({"dec"}),
-                "fwd_critic": _concat_plans(g.forward_plan({"critic_z"}), g.forward_plan({"critic"})),
-                "bwd_dec": g.backward_plan({"dec"}), "bwd_enc": g.backward_plan({"enc"}), "bwd_prior": g.backward_plan({"prior"}),
-                "bwd_critic": _concat_plans(g.backward_plan({"critic"}), g.backward_plan({"critic_z"}))}
+        plans = {"fwd_enc": g.forward_plan({"enc"}), "fwd_dec": g.forward_plan({"dec"}),
+                 "fwd_critic": _concat_plans(g.forward_plan({"critic_z"}), g.forward_plan({"critic"})),
+                 "bwd_dec": g.backward_plan({"dec"}), "bwd_enc": g.backward_plan({"enc"}),
+                 "bwd_critic": _concat_plans(g.backward_plan({"critic"}), g.backward_plan({"critic_z"}))}
+        if self.prior_mode != K.PRIOR_NONE:                     # without a prior there is no sub-network, no plan, no gradient slab
+            plans.update(fwd_prior=g.forward_plan({"prior"}), bwd_prior=g.backward_plan({"prior"}))
+        return plans
 
     def _names(self):
         """The stacked heads under the reference's names: z_heads = [z_mu; z_logvar], z_prior_heads = [z_prior_mu; z_prior_logvar]."""
@@ -105,9 +127,21 @@ class AMPZNetwork(GraphNetwork):
         return out
 
     # ------------------------------------------------------------------ head algebra (form_embedding :82-121, compute_prior :226-241)
-    def split_heads(self, heads):
+    def split_heads(self, heads, prior=False):
+        """(mu, logvar) of a heads buffer as the reference's form_embedding / compute_prior return them.  ``prior`` under a fixed prior: the
+        (projected) mean and the constant, unclamped log-variance (:237-241)."""
         E = self.embedding_size
+        if prior and self.prior_mode == K.PRIOR_FIXED:
+            mu = heads[:, :E]
+            if self.sphere_prior:
+                mu = mu / (torch.norm(mu, dim=-1, keepdim=True) / self.embedding_norm + 1e-8)
+            return mu, torch.ones_like(mu) * self.vae_prior_fixed_logvar
         mu, logvar = heads[:, :E], heads[:, E:2 * E]
         if self.use_vae_clamped_prior:
             logvar = torch.clamp(logvar, min=-5, max=self.vae_var_clamp_max)
         return mu, logvar
+
+    def head_modes(self):
+        """The mode keywords of the three vae_head launches (kernels.vae_embed takes the posterior pair only)."""
+        return dict(prior_mode=self.prior_mode, prior_fixed_logvar=self.vae_prior_fixed_logvar, sphere_prior=self.sphere_prior,
+                    embedding_norm=self.embedding_norm)
