@@ -903,7 +903,9 @@ int pulse_colsum_partial(const float* x, int32_t m, int32_t n, int32_t ld, int32
  *   mode 0: y = clamp((x - mean) / sqrt(var + eps), -clip, clip);  mode 1 (unnorm): y = sqrt(var+eps)*clamp(x)+mean.
  *   x rows may be gathered: row i of y comes from x row row_idx[i] (NULL = identity) -- this is the
  *   AMPDataset minibatch gather (phc/learning/amp_datasets.py:81-94) fused with the normaliser.
- *   Columns [cols, y_cols) of y are zero-filled (GEMM-ready pitch).  If moment_partials != NULL the
+ *   Columns [cols, y_cols) of y are zero-filled (GEMM-ready pitch); cols <= y_cols <= 3072, a wider y is
+ *   PULSE_ERR_INVALID_ARG (the pad is written by the kernels' column owners, which reach 3072 columns).
+ *   If moment_partials != NULL the
  *   per-column batch sums / sums of squares (fp64) of the RAW rows are written to
  *   moment_partials[block][2][cols] for pulse_rms_update (the "update after normalise" of :98-107).
  *   mean / var are the module's fp64 buffers. */
@@ -912,7 +914,7 @@ int pulse_rms_normalize(const float* x, int64_t x_stride, const int64_t* row_idx
                         float* y, int64_t y_stride, int32_t y_cols,
                         double* moment_partials, int32_t num_blocks, pulse_stream_t s);
 /* The same normalise pass (mode 0, wide-row form: 64 <= cols, 16-byte aligned rows) also writing the THREE bf16 planes of y (section 4b's
- * operand format; planes[p * plane_stride + row * planes_ld + col], y_cols a multiple of 32, columns [cols, y_cols) zero) -- the
+ * operand format; planes[p * plane_stride + row * planes_ld + col], y_cols a multiple of 32 and <= 3072, columns [cols, y_cols) zero) -- the
  * layer-1 input of pulse_gemm_x3p split by its producer (same call site: RunningMeanStd.forward in _preproc_obs, common_agent.py:257-261). */
 int pulse_rms_normalize_planes(const float* x, int64_t x_stride, const int64_t* row_idx, int32_t rows, int32_t cols,
                                const double* mean, const double* var, float eps, float clip,

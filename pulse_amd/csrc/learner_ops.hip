@@ -672,6 +672,9 @@ int pulse_rms_normalize(const float* x, int64_t x_stride, const int64_t* row_idx
     if (rows == 0 || cols == 0) return PULSE_OK;
     PULSE_REQUIRE(x && y && mean && var, "pulse_rms_normalize: null pointer");
     PULSE_REQUIRE(cols <= 256 * kRmsMaxColsPerThread, "pulse_rms_normalize: cols %d > %d", cols, 256 * kRmsMaxColsPerThread);
+    // the column owners of the wide kernels reach 256 * 12 = 3072 columns, the zero pad [cols, y_cols) included: a wider pad would stay unwritten
+    PULSE_REQUIRE(y_cols <= 256 * kRmsMaxColsPerThread, "pulse_rms_normalize: y_cols %d > %d (the zero pad is written by the same column owners)", y_cols,
+                  256 * kRmsMaxColsPerThread);
     PULSE_REQUIRE(num_blocks >= 1, "pulse_rms_normalize: num_blocks < 1");
     PULSE_REQUIRE(y_cols >= cols && y_stride >= y_cols && x_stride >= cols, "pulse_rms_normalize: bad pitches");
     PULSE_REQUIRE(mode == 0 || mode == 1, "pulse_rms_normalize: bad mode");
@@ -716,6 +719,8 @@ int pulse_rms_normalize_planes(const float* x, int64_t x_stride, const int64_t* 
     PULSE_REQUIRE(x && y && mean && var && planes, "pulse_rms_normalize_planes: null pointer");
     PULSE_REQUIRE(num_blocks >= 1, "pulse_rms_normalize_planes: num_blocks < 1");
     PULSE_REQUIRE(y_cols >= cols && y_stride >= y_cols && x_stride >= cols, "pulse_rms_normalize_planes: bad pitches");
+    PULSE_REQUIRE(y_cols <= 256 * 4 * kRmsVecGroups, "pulse_rms_normalize_planes: y_cols %d > %d (the zero pad is written by the same column owners)", y_cols,
+                  256 * 4 * kRmsVecGroups);
     PULSE_REQUIRE(cols >= 64 && cols <= 256 * 4 * kRmsVecGroups && (x_stride % 4) == 0 && (y_stride % 4) == 0 && (y_cols % 4) == 0 &&
                   (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0 && x_stride >= ((cols + 3) & ~3),
                   "pulse_rms_normalize_planes: needs the wide-row form (64 <= cols <= %d, 16-byte aligned rows)", 256 * 4 * kRmsVecGroups);

@@ -73,6 +73,29 @@ def test_rollout_record_validation(lib):
     assert lib.pulse_rollout_record(ctypes.byref(a), None) == INVALID and "null pointer" in msg(lib)
 
 
+@pytest.mark.parametrize("entry", ["pulse_rms_normalize", "pulse_rms_normalize_planes"])
+def test_rms_normalize_refuses_a_pad_past_the_column_owners(lib, entry):
+    """The wide kernels' column owners reach 3072 columns, the zero pad [cols, y_cols) included: a wider y used to return PULSE_OK with the
+    pad's tail unwritten.  Both entries now say so; y_cols = 3072 passes the size checks and is stopped by a later one (nothing is launched:
+    the pointers are host addresses that only have to be non-null and 16-byte aligned)."""
+    buf = (ctypes.c_float * 16)()
+    p = (ctypes.addressof(buf) + 15) & ~15
+
+    def call(y_cols, y_stride, planes_ld):
+        head = (p, 3104, None, 4, 3000, p, p, 1e-5, 5.0)
+        if entry == "pulse_rms_normalize":
+            return lib.pulse_rms_normalize(*head, 0, p, y_stride, y_cols, None, 1, None)
+        return lib.pulse_rms_normalize_planes(*head, p, y_stride, y_cols, None, 1, p, 0, planes_ld, None)
+
+    assert call(3104, 3104, 3104) == INVALID
+    assert "y_cols 3104 > 3072" in msg(lib) and entry + ":" in msg(lib), msg(lib)
+    # 3072 columns: the limit itself is legal -- the call gets as far as the next check (the y pitch / the planes' pitch)
+    if entry == "pulse_rms_normalize":
+        assert call(3072, 3000, 0) == INVALID and "bad pitches" in msg(lib), msg(lib)
+    else:
+        assert call(3072, 3072, 8) == INVALID and "planes rows" in msg(lib), msg(lib)
+
+
 def test_im_step_validation(lib):
     a = _lib.ImStepArgs()
     a.num_envs, a.num_bodies, a.what = 4, 24, _lib.PULSE_IM_REWARD

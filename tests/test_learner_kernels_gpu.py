@@ -12,6 +12,7 @@ import torch
 
 from pulse_amd import kernels as K
 from pulse_amd._lib import (ACT_NONE, ACT_RELU, ACT_SILU, EPI_RELU_GRAD, EPI_SILU_GRAD, GEMM_OUT_CONTIG, GEMM_RED_CONTIG)
+from tests.rollout_record_ref import RolloutReference
 
 pytestmark = pytest.mark.gpu
 
@@ -442,7 +443,7 @@ def test_rollout_record_matches_reference_sequence(dev):
     buf_r, buf_nv = torch.zeros(n, t, 1, device=dev), torch.zeros(n, t, 1, device=dev)
     buf_d = torch.zeros(n, t, dtype=torch.uint8, device=dev)
     mask = torch.zeros(n, dtype=torch.bool, device=dev)
-    ref_r, ref_l = [1.5, 40.0], [120.0, 40.0]
+    ref = RolloutReference(cur_r, cur_l, [1.5, 40.0], [120.0, 40.0], max_size, vmean, vvar, 1e-5)
     for step in range(4):
         rew = torch.rand(n)
         dones = (torch.rand(n) < (0.0 if step == 2 else 0.3)).long()            # step 2: nobody finishes
@@ -454,21 +455,9 @@ def test_rollout_record_matches_reference_sequence(dev):
                          value_mean=vmean.to(dev), value_var=vvar.to(dev), value_eps=1e-5, buf_rewards=buf_r[:, slot], buf_next_values=buf_nv[:, slot],
                          buf_dones=buf_d[:, slot], env_stride=t, current_rewards=d["cur_r"], current_lengths=d["cur_l"], meter_rewards=d["meter_r"],
                          meter_lengths=d["meter_l"], meter_max_size=max_size, done_mask=mask)
-        # reference sequence on the CPU
-        nv = (torch.sqrt(vvar.float() + 1e-5) * torch.clamp(val[:, 0], -5, 5) + vmean.float()) * (1.0 - term.float())
-        cur_r = cur_r + rew
-        cur_l = cur_l + 1
-        idx = dones.nonzero().flatten()
-        for st, vals in ((ref_r, cur_r[idx]), (ref_l, cur_l[idx])):
-            size = vals.shape[0]
-            if size == 0:
-                continue
-            new_mean = vals.float().mean().item()
-            size = float(np.clip(size, 0, max_size))
-            old = min(max_size - size, st[1])
-            st[0], st[1] = (st[0] * old + new_mean * size) / (old + size), old + size
-        nd = 1.0 - dones.float()
-        cur_r, cur_l = cur_r * nd, cur_l * nd
+        # reference sequence on the CPU (tests/rollout_record_ref.py)
+        nv = ref.step(rew, dones, term, val[:, 0])
+        cur_r, cur_l, ref_r, ref_l = ref.cur_r, ref.cur_l, ref.meter_r, ref.meter_l
         np.testing.assert_array_equal(buf_r[:, slot, 0].cpu().numpy(), rew.numpy())
         np.testing.assert_array_equal(buf_d[:, slot].cpu().numpy(), dones.numpy().astype(np.uint8))
         np.testing.assert_allclose(buf_nv[:, slot, 0].cpu().numpy(), nv.numpy(), rtol=1e-6, atol=1e-6)
