@@ -36,7 +36,7 @@ extern "C" {
 #define PULSE_ERR_LAUNCH (-2)
 #define PULSE_ERR_UNSUPPORTED (-3)
 
-#define PULSE_ABI_VERSION 35
+#define PULSE_ABI_VERSION 36
 
 typedef void* pulse_stream_t; /* hipStream_t */
 
@@ -598,6 +598,74 @@ typedef struct pulse_traj_gen_args {
     float* verts;
 } pulse_traj_gen_args;
 int pulse_traj_generate(const pulse_traj_gen_args* args, pulse_stream_t s);
+
+/* ------------------------------------------------------------------------- *
+ * 2a'''. Crowd variant of HumanoidPedestrianTerrain (v36): envs are partitioned into contiguous groups of ``group_size`` (env e is in group
+ *     e / group_size, phc/env/tasks/humanoid.py:256-261; num_envs must be a multiple of group_size).  The three entries write the blocks
+ *     that follow the trajectory samples of pulse_traj_step (launched with num_height_points = 0) in the task observation:
+ *     [height block | people block] (humanoid_pedestrian_terrain.py:253-293, 385-439).
+ * ------------------------------------------------------------------------- */
+#define PULSE_CROWD_TOPK 5             /* neighbours per env (top_k, :1712) */
+#define PULSE_CROWD_JOINTS 10          /* bodies per neighbour: [0, 1, 5, 9, 3, 7, 16, 21, 18, 23] (:1713) */
+#define PULSE_CROWD_GROUP_OBS 165      /* 5 * 11 * 3 (:266) */
+#define PULSE_CROWD_ROOT_POINTS 200    /* 10 x 20 footprint of a person (init_root_points, :643-660) */
+
+/* compute_group_observation, humanoid_pedestrian_terrain.py:1700-1753 (appended by _compute_task_obs :431-437): the 5 nearest other members
+ * of the env's own group by root distance (the first of the 6 smallest distances, the env itself, is dropped), each as the positions of 10
+ * bodies relative to the env's root and its root linear velocity, both in the env's heading frame (remove_base_rot first when
+ * upright_start is 0); a neighbour farther than 10 m is 11 zero vectors.  obs row e, columns obs_offset .. obs_offset + 164, in the reference's
+ * flat order: 150 floats [neighbour][body][xyz], then 15 floats [neighbour][xyz] of velocity.  One wave per env; every env's state is read,
+ * only the rows selected by env_ids / env_mask are written.  group_size >= 6 (torch.topk of 6), rb bodies must cover index 23. */
+typedef struct pulse_crowd_group_obs_args {
+    int32_t num_envs, group_size;
+    const int64_t* env_ids; int32_t num_ids; const uint8_t* env_mask;
+    const float* rb; int64_t rb_env_stride; int32_t num_bodies;
+    int32_t upright_start;
+    float* obs; int64_t obs_stride; int32_t obs_offset;
+} pulse_crowd_group_obs_args;
+int pulse_sizeof_crowd_group_obs_args(void);
+int pulse_crowd_group_obs(const pulse_crowd_group_obs_args* args, pulse_stream_t s);
+
+/* People in the height map, first half (get_heights :749-761, init_root_points :643-660, Terrain.sample_height_points :1207-1221): every
+ * person's 10 x 20 grid of root points (x in linspace(-0.25, 0.25, 10), y in linspace(-0.5, 0.5, 20), x-major), rotated by the heading of
+ * its RAW root rotation and moved to its root, is mapped to cells (world_points_to_map: truncation, clip to [0, size - 2]).  Instead of one
+ * raised copy of the height field per group, ``owner`` (num_groups, map_rows, map_cols) int32 holds 0 for an empty cell and otherwise the
+ * index + 1 of the highest env whose footprint covers it (atomicMax: the winner of the reference's indexed assignment on CPU).  ``cells``
+ * (num_envs, 200) int32 lists the cell (row * map_cols + col, in the env's group) of every root point: with ``clear`` set the cells listed
+ * by the PREVIOUS call are emptied first (entries < 0 are skipped: fill the list with -1 before the first call), so no call touches the
+ * whole grid.  Two launches: clear, then stamp. */
+typedef struct pulse_crowd_stamp_args {
+    int32_t num_envs, group_size;
+    const float* rb; int64_t rb_env_stride;
+    int32_t map_rows, map_cols; float horizontal_scale;
+    int32_t* owner; int32_t* cells; int32_t clear;
+} pulse_crowd_stamp_args;
+int pulse_sizeof_crowd_stamp_args(void);
+int pulse_crowd_stamp(const pulse_crowd_stamp_args* args, pulse_stream_t s);
+
+/* People in the height map, second half, and the velocity channels (get_heights :718-772, Terrain.sample_height_points :1200-1276, tail of
+ * _compute_task_obs :414-427): the whole height block of the selected envs, one workgroup per env.  Height of a sample = min over the cell
+ * and its diagonal neighbour of heightsamples + stamp_raise where ``owner`` marks the cell in the env's group (int32 sum), times
+ * vertical_scale.  owner NULL: no stamps (group_size is then ignored).
+ * velocity_map 0: num_height_points floats per env.  velocity_map 1: 3 * num_height_points floats, [h, vx, vy] per point.  With ``owner``
+ * the velocity of a sample is the root linear velocity of the person owning cell (px, py) (zero if nobody), minus the env's own, rotated by
+ * calc_heading_quat_inv of the env's RAW root rotation, xy kept (:1236-1254); without, both channels are minus the env's own velocity in
+ * that frame (:1266-1276).  Tail: use_center_height: channel 0 = centre - h, velocities unchanged; otherwise root z - value on EVERY
+ * channel; then clip to +-3 and scale by height_meas_scale, velocities included. */
+typedef struct pulse_crowd_heights_args {
+    int32_t num_envs, group_size;
+    const int64_t* env_ids; int32_t num_ids; const uint8_t* env_mask;
+    const float* rb; int64_t rb_env_stride; int32_t num_bodies;
+    int32_t upright_start;
+    const int16_t* heightsamples; int32_t map_rows, map_cols; float horizontal_scale, vertical_scale;
+    const int32_t* owner; int32_t stamp_raise;           /* the reference's short(1.7 / vertical_scale) = 340 */
+    const float* height_points; int32_t num_height_points; int32_t sensor_body;
+    const float* center_points; int32_t num_center_points; int32_t use_center_height; float height_meas_scale;
+    int32_t velocity_map;
+    float* obs; int64_t obs_stride; int32_t obs_offset;
+} pulse_crowd_heights_args;
+int pulse_sizeof_crowd_heights_args(void);
+int pulse_crowd_heights(const pulse_crowd_heights_args* args, pulse_stream_t s);
 
 /* ------------------------------------------------------------------------- *
  * 3. GAE: CommonAgent.discount_values + returns, phc/learning/common_agent.py:493-505,

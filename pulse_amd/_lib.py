@@ -12,7 +12,7 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int6
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PULSE_HIP_LIB: another build of the SAME library (tools/im_step_repro.py compares compile variants); default = the in-tree build
 LIB_PATH = os.environ.get("PULSE_HIP_LIB") or os.path.join(_HERE, "csrc", "libpulse_hip.so")
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 PULSE_IM_SELF_OBS = 1
 PULSE_IM_TASK_OBS = 2
@@ -187,6 +187,32 @@ class TrajGenArgs(Structure):
                 ("speed_max", c_float), ("verts", c_void_p)]
 
 
+class CrowdGroupObsArgs(Structure):
+    _fields_ = [("num_envs", c_int32), ("group_size", c_int32), ("env_ids", c_void_p), ("num_ids", c_int32), ("env_mask", c_void_p),
+                ("rb", c_void_p), ("rb_env_stride", c_int64), ("num_bodies", c_int32), ("upright_start", c_int32),
+                ("obs", c_void_p), ("obs_stride", c_int64), ("obs_offset", c_int32)]
+
+
+class CrowdStampArgs(Structure):
+    _fields_ = [("num_envs", c_int32), ("group_size", c_int32), ("rb", c_void_p), ("rb_env_stride", c_int64),
+                ("map_rows", c_int32), ("map_cols", c_int32), ("horizontal_scale", c_float),
+                ("owner", c_void_p), ("cells", c_void_p), ("clear", c_int32)]
+
+
+class CrowdHeightsArgs(Structure):
+    _fields_ = [("num_envs", c_int32), ("group_size", c_int32), ("env_ids", c_void_p), ("num_ids", c_int32), ("env_mask", c_void_p),
+                ("rb", c_void_p), ("rb_env_stride", c_int64), ("num_bodies", c_int32), ("upright_start", c_int32),
+                ("heightsamples", c_void_p), ("map_rows", c_int32), ("map_cols", c_int32), ("horizontal_scale", c_float), ("vertical_scale", c_float),
+                ("owner", c_void_p), ("stamp_raise", c_int32),
+                ("height_points", c_void_p), ("num_height_points", c_int32), ("sensor_body", c_int32),
+                ("center_points", c_void_p), ("num_center_points", c_int32), ("use_center_height", c_int32), ("height_meas_scale", c_float),
+                ("velocity_map", c_int32),
+                ("obs", c_void_p), ("obs_stride", c_int64), ("obs_offset", c_int32)]
+
+
+CROWD_GROUP_OBS, CROWD_ROOT_POINTS = 165, 200        # PULSE_CROWD_GROUP_OBS, PULSE_CROWD_ROOT_POINTS
+
+
 class VaeEmbedArgs(Structure):
     _fields_ = [("heads", c_void_p), ("heads_stride", c_int64), ("eps", c_void_p), ("eps_stride", c_int64), ("x", c_void_p), ("x_stride", c_int64),
                 ("ain", c_void_p), ("ain_stride", c_int64), ("cin", c_void_p), ("cin_stride", c_int64),
@@ -318,6 +344,12 @@ SIGNATURES = {
     "pulse_traj_step": (c_int, [POINTER(TrajStepArgs), P]),
     "pulse_sizeof_traj_step_args": (c_int, []),
     "pulse_traj_generate": (c_int, [POINTER(TrajGenArgs), P]),
+    "pulse_sizeof_crowd_group_obs_args": (c_int, []),
+    "pulse_crowd_group_obs": (c_int, [POINTER(CrowdGroupObsArgs), P]),
+    "pulse_sizeof_crowd_stamp_args": (c_int, []),
+    "pulse_crowd_stamp": (c_int, [POINTER(CrowdStampArgs), P]),
+    "pulse_sizeof_crowd_heights_args": (c_int, []),
+    "pulse_crowd_heights": (c_int, [POINTER(CrowdHeightsArgs), P]),
     "pulse_vae_embed": (c_int, [POINTER(VaeEmbedArgs), P]),
     "pulse_vae_project": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_float, P]),
     "pulse_vae_kin_loss": (c_int, [POINTER(VaeKinArgs), P]),

@@ -61,6 +61,23 @@ def vae_variant_env(name, **extra):
     return dict(VAE_VARIANTS[name], **extra)
 
 
+# Crowd variant of the terrain task (humanoid.py:256-261, humanoid_pedestrian_terrain.py:253-293, 385-439, 718-772, 1200-1276): env-dict
+# overrides on top of ENV_TERRAIN_Z, e.g. make_agent("terrain_z_crowd_small", env_overrides=crowd_env("stamps_velocity", num_env_group=16)).
+# No shipped config switches them on.  'group_obs' and the two velocity kinds change the detail keys of the task observation, which rules
+# amp_sept out (learning/network_sept.py); 'stamps' leaves the widths alone.
+CROWD_ENVS = {
+    "group_obs": {"divide_group": True, "group_obs": True},                      # + the 165-float 'people' block
+    "stamps": {"divide_group": True},                                            # people stamped into the group's height map
+    "stamps_velocity": {"divide_group": True, "velocity_map": True},             # ... and the velocity of whoever covers a sample
+    "velocity": {"velocity_map": True},                                          # no groups: minus the own velocity on both channels
+}
+
+
+def crowd_env(kind, **extra):
+    """The env-dict overrides of a CROWD_ENVS entry (a copy), for make_agent / make_env's ``env_overrides``."""
+    return dict(CROWD_ENVS[kind], **extra)
+
+
 NETWORK_Z_READER = {      # phc/data/cfg/learning/pulse_z_task.yaml:10-44 (network: amp_z_reader)
     "name": "amp_z_reader", "separate": True,
     "space": {"continuous": {"mu_activation": "None", "sigma_activation": "None", "mu_init": {"name": "default"},
@@ -136,6 +153,10 @@ CONFIGS = {
     "terrain_z": {"num_envs": 1536, "horizon_length": 32, "minibatch_size": 16384, "network": "amp_sept", "env": "terrain_z", "agent": "amp"},
     "terrain_z_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_sept", "env": "terrain_z", "agent": "amp",
                         "units": [256, 128]},
+    # the crowd variant of the terrain task: 4 groups of 16, the 'people' neighbour block; amp_z_reader, a flat network (the detail keys of
+    # the crowd observations rule amp_sept out); other kinds: env_overrides=crowd_env(kind, num_env_group=16)
+    "terrain_z_crowd_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_z_reader", "env": "terrain_z",
+                              "agent": "amp", "units": [256, 128], "env_overrides": dict(CROWD_ENVS["group_obs"], num_env_group=16)},
     # PHC's second stage (learning=im_mcp, env=phc_kp_mcp_iccv): the composer over 4 frozen PNN primitives, HumanoidImMCPGetup, 1536 envs
     "mcp": {"num_envs": 1536, "horizon_length": 32, "minibatch_size": 16384, "network": "amp_mcp", "env": "mcp", "agent": "amp"},
     "mcp_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_mcp", "env": "mcp", "agent": "amp",

@@ -37,6 +37,7 @@ SOURCES = [
     ("amp_obs.hip", NO_CONTRACT),
     ("task_step.hip", NO_CONTRACT),
     ("traj_step.hip", NO_CONTRACT),
+    ("crowd_obs.hip", NO_CONTRACT),
     ("motion_state.hip", NO_CONTRACT),
     ("motion_build.hip", NO_CONTRACT),
     ("eval_metrics.hip", NO_CONTRACT),

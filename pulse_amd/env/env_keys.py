@@ -55,6 +55,12 @@ HONOURED = {
     "trajSampleTimestep", "speedMin", "speedMax", "accelMax", "sharpTurnProb", "sensor_extent", "sensor_res", "fuzzy_target",
     "terrain", "terrain_obs", "terrain_obs_type", "terrain_obs_root", "use_center_height",
     "power_usage_reward", "power_usage_coefficient",      # read by the speed / strike tasks only (humanoid_speed.py:43-53, humanoid_strike.py:37-40)
+    # crowd variant of the terrain task (humanoid.py:256-261; humanoid_pedestrian_terrain.py:35, 253-293, 385-439, 718-772, 1200-1276,
+    # 1700-1753): contiguous env groups, the 5-neighbour 'people' observation, people stamped into the height map, and the [h, vx, vy]
+    # height block (env/humanoid_tasks.py: HumanoidPedestrianTerrain; csrc/crowd_obs.hip).  Only that task class acts on them, here as in
+    # the reference.  What stays out of scope raises where it would be used: the point-net branch of amp_sept (learning/network_sept.py),
+    # _compute_flip_task_obs, Isaac collision groups (humanoid.py:919), the 'fov' sensor types (terrain_obs_type).
+    "divide_group", "group_obs", "disable_group_obs", "num_env_group", "velocity_map",
     # keys of THIS package (no reference counterpart): seeds of the synthetic stand-ins, stand-in selection
     "motion_clock_seed", "obs_noise_seed", "occl_seed", "shape_seed", "task_seed", "getup_seed", "physics", "contactBodies", "tarDistMin", "nearDist", "nearProb",
 }
@@ -76,13 +82,12 @@ INERT = {
     "enable_debug_vis": _VIEW, "show_sensors": _VIEW, "is_flag_run": _DEAD,
     "motion_file": _LOAD, "min_length": _LOAD, "hard_negative": _LOAD,
     "eval_full": _DEAD, "kin_policy": _DEAD, "partial_running_mean": _DEAD, "vae_reader": _DEAD, "z_model": _DEAD, "z_read": _DEAD,
-    "z_uniform": _DEAD, "use_vae_prior_loss": _DEAD, "velocity_map": _DEAD, "tarSpeed": _DEAD,
+    "z_uniform": _DEAD, "use_vae_prior_loss": _DEAD, "tarSpeed": _DEAD,
     "training_prim": _TEACH, "actors_to_load": _TEACH,
     "distill_model_config": "structure of the frozen PULSE networks: HumanoidZ.initialize_z_models takes the checkpoint and network params as arguments",
     "hybridInitProb": "only read when stateInit is Hybrid (humanoid_amp.py:490-505), which raises here",
     "dict_size": "VQ dictionary size: only read for z_type vq_vae variants, which raise here",
     "embedding_partion": "VQ partition count: only read for z_type vq_vae variants, which raise here",
-    "num_env_group": "only read with divide_group, which raises here",
     "small_terrain": "debug switch of the terrain mesh creation (" + _SIM + ")",
 }
 
@@ -97,9 +102,6 @@ UNBUILT = {
     "enableHistObs": ((False,), "humanoid_amp.py:320, 509-517"),
     "is_discrete": ((False,), "base_task.py:90; amp_agent.py:42-44 (discrete action heads)"),
     "control_mode": (("isaac_pd",), "humanoid.py:1250-1290 (torques computed in Python for control_mode pd)"),
-    "divide_group": ((False,), "humanoid_pedestrian_terrain.py:265-289, 431-468, 744-766 (crowd observations)"),
-    "group_obs": ((False,), "humanoid_pedestrian_terrain.py:431-437, 744-766 (crowd observations)"),
-    "disable_group_obs": ((False,), "humanoid_pedestrian_terrain.py:749"),
     "z_readout": ((False,), "amp_network_z_builder.py:63, amp_network_z_reader_builder.py:36"),
     "z_all": ((False,), "amp_network_z_builder.py:37 (z fed to every decoder layer)"),
     "vae_prior_policy": ((False,), "amp_network_z_reader_builder.py:38-57"),

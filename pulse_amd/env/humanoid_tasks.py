@@ -302,6 +302,7 @@ class HumanoidTraj(HumanoidTask):
     envs being reset by pulse_traj_generate from six uniform draws taken in the reference's order."""
     TASK = "traj"
     TERRAIN_OBS = False
+    CROWD = False                                   # the reference's HumanoidTraj never looks at the crowd keys; its terrain task does
 
     def __init__(self, cfg, sim, device="cuda:0"):
         from .humanoid_im import check_humanoid_options
@@ -315,6 +316,7 @@ class HumanoidTraj(HumanoidTask):
             if env.get("terrain_obs_type", "square") != "square":
                 raise NotImplementedError("terrain_obs_type 'square' (env_pulse_terrain.yaml) is built; 'fov' / 'square_fov' are viewer-era variants")
             self._height_points = syn.square_height_points(float(env.get("sensor_extent", 2)), int(env.get("sensor_res", 32))).to(device)
+        self._read_crowd_options(env, sim.num_envs)
         super().__init__(cfg, sim, device)
         dev = self.device
         self._speed_min, self._speed_max = float(env.get("speedMin", 0.0)), float(env.get("speedMax", 3.0))
@@ -336,11 +338,54 @@ class HumanoidTraj(HumanoidTask):
                 hs = getattr(sim, "heightsamples", None)
                 self._heightsamples = (hs if hs is not None else syn.synthetic_height_field()).to(dev).contiguous()
             self._horizontal_scale, self._vertical_scale, self.height_meas_scale = 0.1, 0.005, 5.0    # Terrain.__init__ (:1121-1122), :69
+        self._init_crowd(dev)
+
+    # ---- crowd variant (humanoid.py:256-261; humanoid_pedestrian_terrain.py:253-293, 385-439, 718-772, 1200-1276, 1700-1753)
+    def _read_crowd_options(self, env, num_envs):
+        """divide_group / group_obs / disable_group_obs / num_env_group / velocity_map.  ``flags.divide_group``, the global the reference
+        also consults in get_heights (:749), is False in training and treated as such."""
+        on = self.CROWD
+        self._divide_group = on and bool(env.get("divide_group", False))
+        self._group_obs = on and bool(env.get("group_obs", False))
+        self._disable_group_obs = on and bool(env.get("disable_group_obs", False))
+        self.velocity_map = on and self.terrain_obs and bool(env.get("velocity_map", False))
+        self._group_num_people = 0
+        if self._divide_group:
+            g = self._group_num_people = min(int(env.get("num_env_group", 128)), num_envs)       # humanoid.py:259
+            if g < 1 or num_envs % g != 0:
+                raise ValueError(f"divide_group: num_envs = {num_envs} is not a multiple of the group size {g} (num_env_group): the reference's "
+                                 "group ids, arange(num_envs / G).repeat(G) (phc/env/tasks/humanoid.py:260), have no meaning there")
+            if self._group_obs and g < 6:
+                raise ValueError(f"group_obs: group size {g} < 6: compute_group_observation takes the 6 smallest group distances "
+                                 "(torch.topk, phc/env/tasks/humanoid_pedestrian_terrain.py:1724)")
+        self._people_obs = self._divide_group and self._group_obs                        # the 165-float neighbour block (:264-267, 431-437)
+        # people stamped into the height map (get_heights :749): only where there is a height map to stamp
+        self._stamps = self._divide_group and not self._group_obs and not self._disable_group_obs and self.terrain_obs
+        terrain_type = env.get("terrain", {}).get("terrainType", "trimesh")
+        if self.velocity_map and terrain_type == "plane":
+            raise NotImplementedError("velocity_map on terrainType 'plane': get_heights returns (num_envs, num_height_points) zeros there "
+                                      "(phc/env/tasks/humanoid_pedestrian_terrain.py:721-725) and _compute_task_obs then views them as "
+                                      "(num_envs, -1, 3) (:418-421) or concatenates a block a third as wide as get_task_obs_size says "
+                                      "(:260-263): the reference cannot run this combination")
+        # on a plane get_heights returns zeros BEFORE it looks at the root points (:721-725): stamps change nothing there
+        self._crowd_heights = (self._stamps or self.velocity_map) and terrain_type != "plane"
+
+    def _init_crowd(self, dev):
+        self._owner = self._stamp_cells = None
+        if self._stamps and self._crowd_heights:
+            rows, cols = self._heightsamples.shape
+            self._owner = torch.zeros(self.num_envs // self._group_num_people, rows, cols, dtype=torch.int32, device=dev)
+            self._stamp_cells = torch.full((self.num_envs, 200), -1, dtype=torch.int32, device=dev)
+
+    def _height_block_width(self):
+        if self._height_points is None:
+            return 0
+        return self._height_points.shape[0] * (3 if self.velocity_map else 1)
 
     def _task_obs_width(self, env):
-        w = 2 * self._num_traj_samples                                                   # get_task_obs_size (:253-270)
-        if self._height_points is not None:
-            w += self._height_points.shape[0]
+        w = 2 * self._num_traj_samples + self._height_block_width()                      # get_task_obs_size (:253-270)
+        if self._people_obs:
+            w += 5 * 11 * 3
         return w
 
     def _reward_raw_width(self):
@@ -349,7 +394,9 @@ class HumanoidTraj(HumanoidTask):
     def get_task_obs_size_detail(self):
         d = {"traj": 2 * self._num_traj_samples}                                         # get_task_obs_size_detail (:273-290)
         if self.terrain_obs:
-            d["heightmap"] = self._height_points.shape[0]
+            d["heightmap_velocity" if self.velocity_map else "heightmap"] = self._height_block_width()
+        if self._people_obs:
+            d["people"] = 5 * 11 * 3
         return d
 
     def _task_due(self):
@@ -379,11 +426,11 @@ class HumanoidTraj(HumanoidTask):
 
     def _task_step(self, what, env_mask=None):
         terrain = {}
-        if self.terrain_obs:
+        if self.terrain_obs and not self._crowd_heights:
             terrain = dict(heightsamples=self._heightsamples, horizontal_scale=self._horizontal_scale, vertical_scale=self._vertical_scale,
                            height_points=self._height_points, sensor_body=self._sensor_body, center_points=self._center_points,
                            use_center_height=self._use_center_height, height_meas_scale=self.height_meas_scale)
-        return ops.traj_step(self.sim.rigid_body_state, self._traj_verts, self.progress_buf, what=what, dt=self.dt, episode_dur=self._episode_dur,
+        out = ops.traj_step(self.sim.rigid_body_state, self._traj_verts, self.progress_buf, what=what, dt=self.dt, episode_dur=self._episode_dur,
                              num_samples=self._num_traj_samples, sample_timestep=self._traj_sample_timestep, upright=self._has_upright_start,
                              dof_force=self.sim.dof_force, dof_vel=self.sim.dof_vel, power_coef=self.power_coefficient, power_reward=self.power_reward,
                              fuzzy_target=self.fuzzy_target, contact_forces=self.sim.contact_forces, contact_body_ids=self._contact_body_ids,
@@ -391,14 +438,46 @@ class HumanoidTraj(HumanoidTask):
                              fail_dist=self._fail_dist, enable_early_termination=self._enable_early_termination, terrain_reset=self.terrain_obs,
                              obs=self._obs_store, obs_offset=self._self_obs_size, rew=self.rew_buf, rew_raw=self.reward_raw, reset=self.reset_buf,
                              terminate=self._terminate_buf, env_mask=env_mask, **terrain)
+        if (what & TASK_OBS) and (self._crowd_heights or self._people_obs):
+            self._crowd_obs(env_mask)
+        return out
+
+    def _crowd_obs(self, env_mask):
+        """[height block | people block] behind the trajectory samples pulse_traj_step wrote (it ran without a height sensor when the height
+        block is the crowd kernels').  Stamps and neighbours come from EVERY env's state; only the rows of ``env_mask`` are written, as the
+        reference indexes the whole-group result by env_ids (:433-435)."""
+        rb, col = self.sim.rigid_body_state, self._self_obs_size + 2 * self._num_traj_samples
+        if self._crowd_heights:
+            if self._stamps:
+                ops.crowd_stamp(rb, self._group_num_people, self._owner, self._stamp_cells, horizontal_scale=self._horizontal_scale)
+            ops.crowd_heights(rb, self._heightsamples, self._height_points, group_size=self._group_num_people, owner=self._owner,
+                              velocity_map=self.velocity_map, upright=self._has_upright_start, sensor_body=self._sensor_body,
+                              center_points=self._center_points, use_center_height=self._use_center_height,
+                              horizontal_scale=self._horizontal_scale, vertical_scale=self._vertical_scale,
+                              height_meas_scale=self.height_meas_scale, obs=self._obs_store, obs_offset=col, env_mask=env_mask)
+        if self._people_obs:
+            ops.crowd_group_obs(rb, self._group_num_people, upright=self._has_upright_start, obs=self._obs_store,
+                                obs_offset=col + self._height_block_width(), env_mask=env_mask)
 
 
 class HumanoidPedestrianTerrain(HumanoidTraj):
     """HumanoidPedestrianTerrain (phc/env/tasks/humanoid_pedestrian_terrain.py:31-890; env_pulse_terrain.yaml): the trajectory task over a height
     field -- the task observation gains the 32 x 32 height map under the head (:384-440), a fall is a summed non-foot contact force above
     50 N (:1476-1531), the reward keeps a power term (:871-890).  The terrain itself (isaacgym.terrain_utils, PhysX tri-mesh) is a synthetic
-    height field here; crowds (``_divide_group``, the 'people' point-net input of amp_sept) are not built -- no shipped config enables them."""
+    height field here.
+
+    Crowd variant (no shipped config enables it; configs.crowd_env): ``divide_group`` partitions the envs into contiguous groups of
+    min(num_env_group, num_envs) (humanoid.py:256-261).  With ``group_obs`` the task observation gains the 165-float 'people' block,
+    the 5 nearest other members of the env's group (compute_group_observation, :1700-1753); without it (and without
+    ``disable_group_obs``) every person is stamped into its group's copy of the height map as a 10 x 20 footprint 1.7 m high
+    (get_heights :749-761, sample_height_points :1207-1259).  ``velocity_map``, with or without groups, makes the height block
+    [h, vx, vy] per point ('heightmap_velocity', :1236-1276).  In these modes pulse_traj_step runs without its height sensor and the
+    kernels of csrc/crowd_obs.hip write [height block | people block] behind the trajectory samples.  Not built, and rejected where they
+    would be used: the 'people' point-net branch of amp_sept (learning/network_sept.py -- the flat networks read the wider observation as
+    it is), _compute_flip_task_obs (mirroring augmentation, :442-478), Isaac collision groups per env group (humanoid.py:919) and the 'fov'
+    sensor types."""
     TERRAIN_OBS = True
+    CROWD = True
 
 
 class _ZMixin(HumanoidZ):

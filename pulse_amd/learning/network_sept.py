@@ -8,7 +8,12 @@ read cat(self_obs, task_out) (358 + 256).
 One reference quirk is structural and mirrored: with ``separate: True`` the constructor calls ``_build_task_mlp()`` twice
 (:33-36) and both calls assign ``self._task_mlp`` -- so there is ONE task MLP, shared by eval_actor (:92-101) and eval_critic
 (:77-90), and its weights receive the sum of both gradients.  (The first instance is garbage-collected; only its RNG draws remain.)
-The 'people' point-net branch (:45-60, 152-165) belongs to the crowd variant (``_divide_group``), which no shipped config enables.
+The crowd variant of the terrain task (env/humanoid_tasks.py: divide_group / group_obs / velocity_map) is built, this network's side of it
+is not -- and cannot follow the reference: eval_task (:48-60) feeds the slice [traj | people] to ``_task_mlp``, which was built for
+traj + heightmap inputs (:107-111), so the 'people' branch fails in the first matmul, and ``_build_task_mlp`` asserts 'heightmap' in the
+detail (:107), which a velocity_map observation ('heightmap_velocity') does not carry.  Both raise here, saying so; the flat networks
+(amp, amp_z_reader) read the wider observation as it is.  People stamped into the height map without velocity_map leave the widths alone
+and train on this network unchanged.
 
 Physical layout (learning/graph.py): the task MLP reads the observation buffer from column 356 (16-byte aligned; the two self-observation
 columns in front carry zero weights through the layer's column map), its last layer writes straight into columns 360..615 of the actor's
@@ -24,7 +29,14 @@ class AMPSeptNetwork(GraphNetwork):
     def __init__(self, params, *, actions_num, self_obs_size, task_obs_size, task_obs_size_detail, device="cuda:0", split_k=8):
         d = dict(task_obs_size_detail or {})
         if "people" in d:
-            raise NotImplementedError("amp_sept's point-net branch ('people': the crowd variant of the terrain task) is not built")
+            raise NotImplementedError("amp_sept with a 'people' block (divide_group + group_obs) is not built: the reference's eval_task "
+                                      "(phc/learning/amp_network_sept_builder.py:48-60) feeds a [traj | people] slice to the task MLP, which was built "
+                                      "for traj + heightmap inputs (:107-111), so it cannot run either; use a flat network (amp, amp_z_reader), which "
+                                      "reads the wider observation as it is")
+        if "heightmap_velocity" in d:
+            raise ValueError("amp_sept needs 'heightmap' in task_obs_size_detail, got 'heightmap_velocity' (velocity_map): the reference asserts "
+                             "'heightmap' when it builds the task MLP (phc/learning/amp_network_sept_builder.py:107) and cannot run with "
+                             "velocity_map either; use a flat network (amp, amp_z_reader)")
         if "traj" not in d or "heightmap" not in d:
             raise ValueError("amp_sept needs task_obs_size_detail with 'traj' and 'heightmap' (amp_network_sept_builder.py:107)")
         if d["traj"] + d["heightmap"] != task_obs_size:

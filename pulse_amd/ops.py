@@ -837,6 +837,105 @@ def traj_step(rb, verts, progress, *, what, dt, episode_dur, num_samples=10, sam
 
 
 # --------------------------------------------------------------------------- #
+# crowd variant of the terrain task (include/pulse_hip.h section 2a''')
+# --------------------------------------------------------------------------- #
+def _crowd_rb(rb, group_size, min_group=1):
+    rb = _dev(rb, "rb")
+    if rb.dim() != 3 or rb.shape[2] != 13 or rb.stride(2) != 1 or rb.stride(1) != 13:
+        raise ValueError(f"rb: (N, J, 13) rigid-body records with packed bodies expected, got shape {tuple(rb.shape)} strides {tuple(rb.stride())}")
+    n, g = rb.shape[0], int(group_size)
+    if g < min_group:
+        raise ValueError(f"group_size = {g} < {min_group}" + (": the reference takes the 6 smallest group distances (torch.topk, "
+                         "humanoid_pedestrian_terrain.py:1724)" if min_group > 1 else ""))
+    if n % g != 0:
+        raise ValueError(f"num_envs = {n} is not a multiple of group_size = {g} (the reference's group ids, humanoid.py:259-261, have no meaning there)")
+    return rb, n, g
+
+
+def crowd_group_obs(rb, group_size, *, upright=True, obs=None, obs_offset=0, env_ids=None, env_mask=None):
+    """compute_group_observation (humanoid_pedestrian_terrain.py:1700-1753): one launch of pulse_crowd_group_obs.  ``rb`` (N, J >= 24, 13);
+    envs are grouped contiguously by ``group_size`` (>= 6).  Writes 165 floats per selected env at ``obs[:, obs_offset:]`` (allocated when
+    None) and returns ``obs``."""
+    from ._lib import CROWD_GROUP_OBS, CrowdGroupObsArgs
+    rb, n, g = _crowd_rb(rb, group_size, 6)
+    if rb.shape[1] < 24:
+        raise ValueError(f"rb: the neighbour observation reads bodies up to index 23, got {rb.shape[1]} bodies")
+    a, P = CrowdGroupObsArgs(), Filler()
+    a.num_envs, a.group_size = n, g
+    select_envs(a, P, env_ids, env_mask)
+    a.rb, a.rb_env_stride, a.num_bodies, a.upright_start = rb.data_ptr(), rb.stride(0), rb.shape[1], int(bool(upright))
+    if obs is None:
+        obs = torch.zeros(n, (obs_offset + CROWD_GROUP_OBS + 3) // 4 * 4, dtype=torch.float32, device=rb.device)
+    a.obs, a.obs_stride = rows2d(obs, "obs", n, obs_offset + CROWD_GROUP_OBS)
+    a.obs_offset = int(obs_offset)
+    _launch("pulse_crowd_group_obs", ctypes.byref(a))
+    return obs
+
+
+def _crowd_map(heightsamples):
+    if not isinstance(heightsamples, torch.Tensor) or heightsamples.dtype != torch.int16 or heightsamples.dim() != 2 or not heightsamples.is_contiguous() \
+            or not heightsamples.is_cuda:
+        raise TypeError("heightsamples: contiguous (rows, cols) int16 CUDA tensor expected")
+    return heightsamples.shape[0], heightsamples.shape[1]
+
+
+def crowd_stamp(rb, group_size, owner, cells, *, horizontal_scale=0.1, clear=True):
+    """People into the height map (get_heights :749-761, sample_height_points :1207-1221): every person's 10 x 20 root-point footprint marks
+    ``owner`` (num_groups, rows, cols) int32 with its env index + 1 (the highest index wins a shared cell) and lists its cells in ``cells``
+    (N, 200) int32.  ``clear``: first empty the cells ``cells`` lists from the previous call (fill it with -1 before the first).  Returns
+    ``owner``."""
+    from ._lib import CROWD_ROOT_POINTS, CrowdStampArgs
+    rb, n, g = _crowd_rb(rb, group_size)
+    _dev(owner, "owner", torch.int32), _dev(cells, "cells", torch.int32)
+    if owner.dim() != 3 or owner.shape[0] != n // g or not owner.is_contiguous():
+        raise ValueError(f"owner: contiguous ({n // g}, rows, cols) int32 expected, got {tuple(owner.shape)}")
+    if tuple(cells.shape) != (n, CROWD_ROOT_POINTS) or not cells.is_contiguous():
+        raise ValueError(f"cells: contiguous ({n}, {CROWD_ROOT_POINTS}) int32 expected, got {tuple(cells.shape)}")
+    a = CrowdStampArgs()
+    a.num_envs, a.group_size, a.rb, a.rb_env_stride = n, g, rb.data_ptr(), rb.stride(0)
+    a.map_rows, a.map_cols, a.horizontal_scale = owner.shape[1], owner.shape[2], float(horizontal_scale)
+    a.owner, a.cells, a.clear = owner.data_ptr(), cells.data_ptr(), int(bool(clear))
+    _launch("pulse_crowd_stamp", ctypes.byref(a))
+    return owner
+
+
+def crowd_heights(rb, heightsamples, height_points, *, group_size=0, owner=None, velocity_map=False, upright=True, sensor_body=0,
+                  center_points=None, use_center_height=False, horizontal_scale=0.1, vertical_scale=0.005, height_meas_scale=5.0, obs=None,
+                  obs_offset=0, env_ids=None, env_mask=None):
+    """The height block of the crowd / velocity modes (get_heights :718-772, sample_height_points :1200-1276, tail of _compute_task_obs
+    :414-427): one launch of pulse_crowd_heights.  ``owner`` (from crowd_stamp) raises stamped cells by short(1.7 / vertical_scale) and, with
+    ``velocity_map``, supplies each sample's velocity; ``velocity_map`` makes the block (N, 3 * P) interleaved [h, vx, vy].  Writes at
+    ``obs[:, obs_offset:]`` (allocated when None) and returns ``obs``."""
+    from ._lib import CrowdHeightsArgs
+    rb, n, g = _crowd_rb(rb, group_size if owner is not None else 1)
+    rows, cols = _crowd_map(heightsamples)
+    a, P = CrowdHeightsArgs(), Filler()
+    a.num_envs, a.group_size = n, g
+    select_envs(a, P, env_ids, env_mask)
+    a.rb, a.rb_env_stride, a.num_bodies, a.upright_start = rb.data_ptr(), rb.stride(0), rb.shape[1], int(bool(upright))
+    a.heightsamples, a.map_rows, a.map_cols = heightsamples.data_ptr(), rows, cols
+    a.horizontal_scale, a.vertical_scale = float(horizontal_scale), float(vertical_scale)
+    if owner is not None:
+        _dev(owner, "owner", torch.int32)
+        if tuple(owner.shape) != (n // g, rows, cols) or not owner.is_contiguous():
+            raise ValueError(f"owner: contiguous ({n // g}, {rows}, {cols}) int32 expected, got {tuple(owner.shape)}")
+        a.owner = owner.data_ptr()
+    a.stamp_raise = int(ctypes.c_float(1.7 / float(vertical_scale)).value)                # torch.tensor(1.7 / vertical_scale).short(), :1226
+    nh = height_points.shape[0]
+    a.height_points, a.num_height_points, a.sensor_body = P(height_points, "height_points", shape=(nh, 2)), nh, int(sensor_body)
+    if center_points is not None:
+        a.center_points, a.num_center_points = P(center_points, "center_points"), center_points.shape[0]
+    a.use_center_height, a.height_meas_scale, a.velocity_map = int(bool(use_center_height)), float(height_meas_scale), int(bool(velocity_map))
+    w = (3 if velocity_map else 1) * nh
+    if obs is None:
+        obs = torch.zeros(n, (obs_offset + w + 3) // 4 * 4, dtype=torch.float32, device=rb.device)
+    a.obs, a.obs_stride = rows2d(obs, "obs", n, obs_offset + w)
+    a.obs_offset = int(obs_offset)
+    _launch("pulse_crowd_heights", ctypes.byref(a))
+    return obs
+
+
+# --------------------------------------------------------------------------- #
 # MCP composer stage (include/pulse_hip.h section 4e)
 # --------------------------------------------------------------------------- #
 def mcp_compose(weights, x, out=None, *, num_actions=None, discrete=False):
