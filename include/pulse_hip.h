@@ -341,6 +341,50 @@ typedef struct pulse_amp_hist_args {
 int pulse_sizeof_amp_hist_args(void);
 int pulse_amp_hist_init(const pulse_amp_hist_args* args, pulse_stream_t s);
 
+/* Reference-state reset of the downstream tasks in one launch: HumanoidAMP._reset_ref_state_init / _sample_ref_state
+ * (phc/env/tasks/humanoid_amp.py:447-488) with the task's override of _sample_ref_state.  For every env e with env_mask[e] != 0 the clip
+ * motion_ids[e] is blended at times[e] exactly as pulse_motion_state does (MotionLibBase.get_motion_state, no root offset), the task's root
+ * transform is applied, and the 13-float records of all bodies (rb + e * rb_env_stride), dof_pos / dof_vel (num_envs, 3 (J - 1)),
+ * start_times[e] = times[e] and sampled_ids[e] = motion_ids[e] are written; clear0 / clear1 / clear2[e] = 0 when given (progress, reset,
+ * terminate).  An env outside the mask costs one flag read and writes nothing; so does one whose motion id is outside [0, num_motions).
+ *   PULSE_TASK_RESET_NONE            HumanoidTraj: the motion's state as it is (humanoid_amp.py:447-466).
+ *   PULSE_TASK_RESET_ZERO_XY         HumanoidReach / HumanoidStrike: root xy = 0 (humanoid_reach.py:46-49, humanoid_strike.py:147-150).
+ *   PULSE_TASK_RESET_REMOVE_HEADING  HumanoidSpeed: everything turned by calc_heading_quat_inv of the root rotation (of remove_base_rot
+ *                                    of it when upright_start is 0), about the root (humanoid_speed.py:251-270).
+ *   PULSE_TASK_RESET_TERRAIN         HumanoidPedestrianTerrain: root xy = new_root_xy[e], z lifted by the mean of the centre-grid heights
+ *                                    under the moved root, the grid turned by the root's yaw only (humanoid_pedestrian_terrain.py:553-563,
+ *                                    get_center_heights :690-716; upright_start as there).  heightsamples NULL = terrainType 'plane'
+ *                                    (zero heights).  1 .. 32 centre points.
+ * What the records hold.  The reference writes two tensors that disagree on the reset frame: _humanoid_root_states gets the transformed
+ * root, the _rigid_body_* cache gets bodies that are (speed) turned except body_ang_vel, which is returned as it was
+ * (humanoid_speed.py:262-270); (reach / strike) not translated; (terrain) moved in xy but never lifted -- key_pos is lifted twice instead
+ * (humanoid_pedestrian_terrain.py:563-567).  Isaac's next refresh overwrites that cache from the root and dof state.  Here there is ONE
+ * record tensor whose body 0 is the root, so the consistent state is written: the root record holds exactly the reference's root-state
+ * values and every other body is carried rigidly by the same root transform (positions about / with the root, rotations, linear and
+ * angular velocities).  fix_trans_height (_get_fixed_smpl_state_from_motionlib, humanoid_amp.py:382-430: SMPL mesh parsers) is out of
+ * scope as for the motion query: the motion's heights are used as they are.
+ * Mapping: a 32-lane half-wave per env, lane = body (num_bodies <= 32), eight envs per 256-thread workgroup; rows are put together in LDS
+ * and stored coalesced. */
+#define PULSE_TASK_RESET_NONE 0
+#define PULSE_TASK_RESET_ZERO_XY 1
+#define PULSE_TASK_RESET_REMOVE_HEADING 2
+#define PULSE_TASK_RESET_TERRAIN 3
+typedef struct pulse_task_reset_args {
+    pulse_motion_tables tab;
+    int32_t num_envs; int32_t transform; int32_t upright_start;
+    const uint8_t* env_mask; const int64_t* motion_ids; const float* times;
+    /* TERRAIN */
+    const float* new_root_xy;                    /* (num_envs, 2) */
+    const int16_t* heightsamples; int32_t map_rows, map_cols; float horizontal_scale, vertical_scale;
+    const float* center_points; int32_t num_center_points;
+    /* outputs */
+    float* rb; int64_t rb_env_stride; float* dof_pos; float* dof_vel;
+    float* start_times; int64_t* sampled_ids;
+    int64_t* clear0; int64_t* clear1; int64_t* clear2;
+} pulse_task_reset_args;
+int pulse_sizeof_task_reset_args(void);
+int pulse_task_ref_state_init(const pulse_task_reset_args* args, pulse_stream_t s);
+
 /* ------------------------------------------------------------------------- *
  * 2b. Reference-motion query: MotionLibBase.get_motion_state / get_root_pos_smpl /
  *     _calc_frame_blend (phc/utils/motion_lib_base.py:434-565).

@@ -132,6 +132,20 @@ class AmpHistArgs(Structure):
                 ("limb_weights", c_void_p), ("limb_stride", c_int64), ("num_limb", c_int32)]
 
 
+TASK_RESET_NONE, TASK_RESET_ZERO_XY, TASK_RESET_REMOVE_HEADING, TASK_RESET_TERRAIN = 0, 1, 2, 3      # PULSE_TASK_RESET_*
+
+
+class TaskResetArgs(Structure):
+    _fields_ = [("tab", MotionTables), ("num_envs", c_int32), ("transform", c_int32), ("upright_start", c_int32),
+                ("env_mask", c_void_p), ("motion_ids", c_void_p), ("times", c_void_p),
+                ("new_root_xy", c_void_p),
+                ("heightsamples", c_void_p), ("map_rows", c_int32), ("map_cols", c_int32), ("horizontal_scale", c_float), ("vertical_scale", c_float),
+                ("center_points", c_void_p), ("num_center_points", c_int32),
+                ("rb", c_void_p), ("rb_env_stride", c_int64), ("dof_pos", c_void_p), ("dof_vel", c_void_p),
+                ("start_times", c_void_p), ("sampled_ids", c_void_p),
+                ("clear0", c_void_p), ("clear1", c_void_p), ("clear2", c_void_p)]
+
+
 class MotionStateArgs(Structure):
     _fields_ = [("tab", MotionTables), ("n", c_int64), ("motion_ids", c_void_p), ("motion_times", c_void_p),
                 ("progress", c_void_p), ("step_shift", c_int32), ("dt", c_float), ("start_times", c_void_p), ("start_offsets", c_void_p),
@@ -324,6 +338,8 @@ SIGNATURES = {
     "pulse_amp_obs": (c_int, [POINTER(AmpObsArgs), P]),
     "pulse_sizeof_amp_hist_args": (c_int, []),
     "pulse_amp_hist_init": (c_int, [POINTER(AmpHistArgs), P]),
+    "pulse_sizeof_task_reset_args": (c_int, []),
+    "pulse_task_ref_state_init": (c_int, [POINTER(TaskResetArgs), P]),
     "pulse_sizeof_rollout_record_args": (c_int, []),
     "pulse_rollout_record": (c_int, [POINTER(RolloutRecordArgs), P]),
     "pulse_rollout_meters": (c_int, [P, c_int32, c_int32, P, P, c_float, P]),

@@ -83,6 +83,7 @@ NETWORK_Z_READER = {      # phc/data/cfg/learning/pulse_z_task.yaml:10-44 (netwo
     "space": {"continuous": {"mu_activation": "None", "sigma_activation": "None", "mu_init": {"name": "default"},
                              "sigma_init": {"name": "const_initializer", "val": -1.0}, "fixed_sigma": True, "learn_sigma": False}},
     "mlp": {"units": [2048, 1024, 512], "activation": "silu", "d2rl": False, "initializer": {"name": "default"}},
+    "disc": {"units": [1024, 512], "activation": "relu", "initializer": {"name": "default"}},       # :35-40; built when the env hands out AMP windows
 }
 
 NETWORK_SEPT = {          # phc/data/cfg/learning/pulse_z_terrain.yaml:12-51 (network: amp_sept)
@@ -91,6 +92,7 @@ NETWORK_SEPT = {          # phc/data/cfg/learning/pulse_z_terrain.yaml:12-51 (ne
                              "sigma_init": {"name": "const_initializer", "val": -1.0}, "fixed_sigma": True, "learn_sigma": False}},
     "mlp": {"units": [2048, 1024, 512], "activation": "silu", "d2rl": False, "initializer": {"name": "default"}},
     "task_mlp": {"units": [512, 256], "activation": "silu", "d2rl": False, "initializer": {"name": "default"}},
+    "disc": {"units": [1024, 512], "activation": "relu", "initializer": {"name": "default"}},       # :46-51; built when the env hands out AMP windows
 }
 
 NETWORK_MCP = {           # phc/data/cfg/learning/im_mcp.yaml:11-45 (network: amp_mcp; ending_act is read by nothing in the reference)
@@ -127,6 +129,11 @@ ENV_SPEED_Z = {"local_root_obs": True, "root_height_obs": True, "enableEarlyTerm
                "tarSpeedMin": 0.0, "tarSpeedMax": 5.0, "speedChangeStepsMin": 100, "speedChangeStepsMax": 200, "power_reward": True,
                "embedding_size": 32, "z_type": "vae"}     # phc/data/cfg/env/env_pulse_amp.yaml (HumanoidSpeedZ)
 
+# the AMP layer of the downstream tasks: env switches (env_pulse_amp.yaml:66) and the learning keys of pulse_z_task.yaml:90-91
+ENV_AMP_TASK = {"enable_amp_obs": True, "numAMPObsSteps": 10}
+AMP_TASK_SMALL = {"task_reward_w": 1, "disc_reward_w": 0, "amp_minibatch_size": 64, "amp_obs_demo_buffer_size": 4096, "amp_replay_buffer_size": 4096,
+                  "amp_batch_size": 128}
+
 CONFIGS = {
     # BASELINE.json configs[0]: 64-env synthetic rollout (horizon 16), 2x512 MLP, one PPO+GAE epoch
     "cfg1": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "units": [512, 512]},
@@ -153,6 +160,13 @@ CONFIGS = {
     "terrain_z": {"num_envs": 1536, "horizon_length": 32, "minibatch_size": 16384, "network": "amp_sept", "env": "terrain_z", "agent": "amp"},
     "terrain_z_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_sept", "env": "terrain_z", "agent": "amp",
                         "units": [256, 128]},
+    # the same two tasks with the HumanoidAMP layer (enable_amp_obs): state init from the motion library, the 10-step AMP window and the
+    # discriminator training beside the policy at task_reward_w 1 / disc_reward_w 0 (pulse_z_task.yaml:90-91, pulse_z_terrain.yaml:100-101:
+    # its gradients enter the same optimiser step and the same grad_norm clip); the small ring sizes of cfg5_small
+    "speed_z_amp_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_z_reader", "env": "speed_z", "agent": "amp",
+                          "units": [256, 128], "extra": dict(AMP_TASK_SMALL), "env_overrides": dict(ENV_AMP_TASK)},
+    "terrain_z_amp_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_sept", "env": "terrain_z", "agent": "amp",
+                            "units": [256, 128], "extra": dict(AMP_TASK_SMALL), "env_overrides": dict(ENV_AMP_TASK)},
     # the crowd variant of the terrain task: 4 groups of 16, the 'people' neighbour block; amp_z_reader, a flat network (the detail keys of
     # the crowd observations rule amp_sept out); other kinds: env_overrides=crowd_env(kind, num_env_group=16)
     "terrain_z_crowd_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_z_reader", "env": "terrain_z",
@@ -241,10 +255,17 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
         env_cfg = dict(ENV_TERRAIN_Z if env_kind == "terrain_z" else ENV_SPEED_Z)
         env_cfg.update(env_overrides or {})
         # the terrain task's humanoids walk inside the synthetic height field (cells of 0.1 m): start them near its middle
-        sim = HT.SyntheticTaskSim(num_envs, horizon + 1, device, seed=seed, rank=rank, xy_offset=(13.0, 15.0) if env_kind == "terrain_z" else (0.0, 0.0))
+        amp = bool(env_cfg.get("enable_amp_obs", False))
+        sim = HT.SyntheticTaskSim(num_envs, horizon + 1, device, seed=seed, rank=rank, xy_offset=(13.0, 15.0) if env_kind == "terrain_z" else (0.0, 0.0),
+                                  dof_pos_bank=amp)
+        motion = None
+        if amp:                                          # the HumanoidAMP layer resets from, looks back into and demonstrates with a motion library
+            from . import synthetic as syn
+            from .env.motion_lib import MotionLib
+            motion = MotionLib.from_tables(syn.synthetic_motion_library(syn.make_generator(seed + 5, rank), min(num_envs, 1024)), device)
         cls = {"speed_z": HT.HumanoidSpeedZ, "reach_z": HT.HumanoidReachZ, "strike_z": HT.HumanoidStrikeZ,
                "terrain_z": HT.HumanoidPedestrianTerrainZ}[env_kind]
-        task = cls({"env": env_cfg} if humanoid == "smpl" else {"env": env_cfg, "robot": robot}, sim, device=device)
+        task = cls({"env": env_cfg} if humanoid == "smpl" else {"env": env_cfg, "robot": robot}, sim, device=device, motion_lib=motion)
         znet = AMPZNetwork(NETWORK_Z, actions_num=69, self_obs_size=task.get_self_obs_size(), task_obs_size=576,
                            task_obs_size_detail=dict({"embedding_size": 32, "z_type": "vae", "use_vae_prior": True, "use_vae_clamped_prior": True,
                                                       "vae_var_clamp_max": 2}, **task._z_detail), device=device)   # (the env dict's prior / posterior variant)

@@ -39,6 +39,7 @@ SOURCES = [
     ("traj_step.hip", NO_CONTRACT),
     ("crowd_obs.hip", NO_CONTRACT),
     ("motion_state.hip", NO_CONTRACT),
+    ("task_reset.hip", NO_CONTRACT),
     ("motion_build.hip", NO_CONTRACT),
     ("eval_metrics.hip", NO_CONTRACT),
     ("rollout_ops.hip", NO_CONTRACT),

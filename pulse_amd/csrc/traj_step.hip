@@ -17,14 +17,9 @@
 // -ffp-contract=off: the expressions follow the reference's operation order.
 #include "common.h"
 #include "rot_math.h"
+#include "terrain_math.h"
 
 namespace pulse {
-
-// isaacgym.torch_utils.quat_apply (3P): b + w t + xyz x t, t = 2 xyz x b
-__device__ __forceinline__ V3 q_apply(const Q4 a, const V3 b) {
-    const V3 t{(a.y * b.z - a.z * b.y) * 2.0f, (a.z * b.x - a.x * b.z) * 2.0f, (a.x * b.y - a.y * b.x) * 2.0f};
-    return V3{b.x + a.w * t.x + (a.y * t.z - a.z * t.y), b.y + a.w * t.y + (a.z * t.x - a.x * t.z), b.z + a.w * t.z + (a.x * t.y - a.y * t.x)};
-}
 
 // TrajGenerator.calc_pos for one (trajectory, time)
 __device__ __forceinline__ V3 traj_pos(const float* verts, int num_verts, float traj_dur, float time) {
@@ -38,21 +33,6 @@ __device__ __forceinline__ V3 traj_pos(const float* verts, int num_verts, float 
     const float* p1 = verts + 3 * (int)f1;
     const float a = 1.0f - lerp;
     return V3{a * p0[0] + lerp * p1[0], a * p0[1] + lerp * p1[1], a * p0[2] + lerp * p1[2]};
-}
-
-// world_points_to_map: (points / horizontal_scale).long() truncates toward zero, then clip to [0, size - 2]; the two cells get_heights compares
-__device__ __forceinline__ void height_cells(const pulse_traj_step_args& a, float wx, float wy, long long& c1, long long& c2) {
-    long long px = (long long)(wx / a.horizontal_scale), py = (long long)(wy / a.horizontal_scale);
-    px = px < 0 ? 0 : (px > a.map_rows - 2 ? a.map_rows - 2 : px);
-    py = py < 0 ? 0 : (py > a.map_cols - 2 ? a.map_cols - 2 : py);
-    c1 = px * a.map_cols + py;
-    c2 = (px + 1) * a.map_cols + py + 1;
-}
-__device__ __forceinline__ float sample_height(const pulse_traj_step_args& a, float wx, float wy) {
-    long long c1, c2;
-    height_cells(a, wx, wy, c1, c2);
-    const short h1 = a.heightsamples[c1], h2 = a.heightsamples[c2];
-    return (float)(h1 < h2 ? h1 : h2) * a.vertical_scale;
 }
 
 __global__ void __launch_bounds__(256) traj_step_kernel(const pulse_traj_step_args a) {
@@ -71,6 +51,7 @@ __global__ void __launch_bounds__(256) traj_step_kernel(const pulse_traj_step_ar
     if (!a.upright_start) root_q = qmul(root_q, Q4{-0.5f, -0.5f, -0.5f, 0.5f});          // remove_base_rot
     const float* verts = a.verts + e * (int64_t)a.num_verts * 3;
     const float time = (float)a.progress[e] * a.dt;                                       // progress_buf * self.dt
+    const HeightField hf = height_field_of(a);
 
     if (a.what & PULSE_TASK_OBS) {
         float* o = a.obs + e * a.obs_stride + a.obs_offset;
@@ -93,10 +74,9 @@ __global__ void __launch_bounds__(256) traj_step_kernel(const pulse_traj_step_ar
                     // get_center_heights: 3 x 3 grid under the root, rotated by the root's yaw-only quaternion (quat_apply_yaw).  One thread per
                     // point (their dependent gathers overlap), summed by thread 0 in the reference's order
                     if (tid < a.num_center_points) {
-                        const float n = fmaxf(sqrtf(root_q.z * root_q.z + root_q.w * root_q.w), 1e-9f);
-                        const Q4 qy{0.0f / n, 0.0f / n, root_q.z / n, root_q.w / n};
+                        const Q4 qy = yaw_quat(root_q);
                         const V3 w = q_apply(qy, V3{a.center_points[2 * tid], a.center_points[2 * tid + 1], 0.0f});
-                        s_cpt[tid] = sample_height(a, w.x + root_p.x, w.y + root_p.y);
+                        s_cpt[tid] = sample_height(hf, w.x + root_p.x, w.y + root_p.y);
                     }
                     __syncthreads();
                     if (tid == 0) {
@@ -119,7 +99,7 @@ __global__ void __launch_bounds__(256) traj_step_kernel(const pulse_traj_step_ar
                     for (int i = 0; i < 4; ++i) {
                         const int p = min(p0 + 256 * i, a.num_height_points - 1);
                         const V3 w = q_apply(hq, V3{a.height_points[2 * p], a.height_points[2 * p + 1], 0.0f});
-                        height_cells(a, w.x + sb[0], w.y + sb[1], i1[i], i2[i]);
+                        height_cells(hf, w.x + sb[0], w.y + sb[1], i1[i], i2[i]);
                     }
                     short h1[4], h2[4];
 #pragma unroll

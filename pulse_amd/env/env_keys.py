@@ -62,7 +62,7 @@ HONOURED = {
     # _compute_flip_task_obs, Isaac collision groups (humanoid.py:919), the 'fov' sensor types (terrain_obs_type).
     "divide_group", "group_obs", "disable_group_obs", "num_env_group", "velocity_map",
     # keys of THIS package (no reference counterpart): seeds of the synthetic stand-ins, stand-in selection
-    "motion_clock_seed", "obs_noise_seed", "occl_seed", "shape_seed", "task_seed", "getup_seed", "physics", "contactBodies", "tarDistMin", "nearDist", "nearProb",
+    "motion_clock_seed", "obs_noise_seed", "occl_seed", "shape_seed", "task_seed", "getup_seed", "amp_seed", "physics", "contactBodies", "tarDistMin", "nearDist", "nearProb",
 }
 
 _SIM = "Isaac Gym scene / actor / asset creation (closed-source physics: out of scope, SURVEY.md section 2 #20, #36)"

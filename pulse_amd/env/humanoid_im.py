@@ -27,24 +27,14 @@ samples future reference frames -- HumanoidIm.{_compute_task_obs, _compute_rewar
 _sample_time} (humanoid_im.py:652-654, 708-919, 920-926, 1119-1192) in three launches per control step.
 """
 import contextlib
-import os
 
 import torch
 
 from .. import ops
 from .. import synthetic as syn
 from . import env_keys
+from .amp_window import AmpWindow, Box          # noqa: F401  (Box: imported from here by the other env modules)
 from .._lib import PULSE_IM_RESET, PULSE_IM_REWARD, PULSE_IM_SELF_OBS, PULSE_IM_TASK_OBS
-
-
-class Box:
-    """Minimal gym.spaces.Box stand-in (gym is not installed)."""
-
-    def __init__(self, low, high, shape):
-        import numpy as np
-        self.shape = tuple(shape)
-        self.low = np.full(self.shape, low, dtype=np.float32)
-        self.high = np.full(self.shape, high, dtype=np.float32)
 
 
 def _env_dict(cfg):
@@ -326,40 +316,19 @@ class HumanoidIm:
         # ---- AMP observations (humanoid_amp.py:91-118, 296-314): (N, numAMPObsSteps, W) history, slot 0 = current frame
         self._enable_amp_obs = bool(env.get("enable_amp_obs", False))
         if self._enable_amp_obs:
-            self._num_amp_obs_steps = int(env.get("numAMPObsSteps", 10))
-            self._amp_root_height_obs = bool(env.get("ampRootHeightObs", env.get("root_height_obs", True)))
-            self._key_body_ids = torch.tensor([names.index(b) for b in env.get("key_bodies", sk["key_bodies"])],
-                                              dtype=torch.int32, device=dev)
-            # dof_subset (humanoid.py:396-421): every joint but L_Hand / R_Hand / L_Toe / R_Toe; applied when the robot config says
-            # has_dof_subset (True in robot/smpl_humanoid.yaml:6) -> 19 joints, 196 floats per frame, 1960 per window.  For SMPL the
-            # subset tensor always exists, so the in-place zeroing of the toe / hand dofs (humanoid_amp.py:636-639, guarded by
-            # ``dof_subset is None``) never runs on this humanoid.
-            self._has_dof_subset = bool(env.get("has_dof_subset", True))
-            nj = self._dof_size // 3
-            self._amp_joint_ids = [d // 3 for d in sk["dof_subset"][::3]] if self._has_dof_subset else None
-            self._amp_zero_joints = ()
-            # the frame's shape / limb rows (humanoid_amp.py:311-314, 963-966): the env's for simulated frames, the motion's for reference frames
-            self._amp_shape_rows = self.humanoid_shapes[:, :-6] if self._has_shape_obs_disc else None            # smpl_params[:, :-6], :672
-            self._amp_limb_rows = self.humanoid_limb_and_weights if self._has_limb_weight_obs_disc else None
-            self._amp_motion_shape_rows = self._amp_motion_limb_rows = None
-            if self._use_motion_lib:
-                if self._has_shape_obs_disc:
-                    self._amp_motion_shape_rows = motion_lib.motion_bodies[:, :-6]
-                if self._has_limb_weight_obs_disc:
-                    self._amp_motion_limb_rows = motion_lib.motion_limb_weights
-            self._amp_variant = {"upright": self._has_upright_start, "version": self.amp_obs_v}
-            self._num_amp_obs_per_step = ops.amp_obs_width(len(self._amp_joint_ids) if self._has_dof_subset else nj, self._key_body_ids.numel(),
-                                                           self._amp_root_height_obs, version=self.amp_obs_v,
-                                                           num_shape=11 * self._has_shape_obs_disc, num_limb=10 * self._has_limb_weight_obs_disc)
-            if self._amp_joint_ids is not None:
-                self._amp_joint_ids = torch.tensor(self._amp_joint_ids, dtype=torch.int32, device=dev)
-            self._amp_obs_buf = torch.zeros(n, self._num_amp_obs_steps, self._num_amp_obs_per_step, device=dev)
-            self._amp_fused = os.environ.get("PULSE_AMP_FUSED", "1") != "0"      # fused history update / history init kernels (0: the op-by-op path)
-            self._amp_obs_sink = None
-            self._add_amp_input_noise = bool(env.get("add_amp_input_noise", False))        # humanoid_amp.py:135, 281-283: demo windows + 0.01 N(0, 1)
-            self._curr_amp_obs_buf = self._amp_obs_buf[:, 0]
-            self._hist_amp_obs_buf = self._amp_obs_buf[:, 1:]
-            self._amp_obs_space = Box(-float("inf"), float("inf"), (self.get_num_amp_obs(),))
+            # the window, its options and its demo fetch live in env/amp_window.py (shared with the downstream tasks); the frame's shape /
+            # limb rows (humanoid_amp.py:311-314, 963-966) are the env's for simulated frames, the motion's for reference frames
+            lib_rows = self._use_motion_lib
+            self._amp = w = AmpWindow(env, num_envs=n, device=dev, skeleton=sk, local_root_obs=self._local_root_obs, upright=self._has_upright_start,
+                                      amp_obs_v=self.amp_obs_v,
+                                      shape_rows=self.humanoid_shapes[:, :-6] if self._has_shape_obs_disc else None,            # smpl_params[:, :-6], :672
+                                      limb_rows=self.humanoid_limb_and_weights if self._has_limb_weight_obs_disc else None,
+                                      motion_shape_rows=motion_lib.motion_bodies[:, :-6] if lib_rows and self._has_shape_obs_disc else None,
+                                      motion_limb_rows=motion_lib.motion_limb_weights if lib_rows and self._has_limb_weight_obs_disc else None)
+            # under the names the reference's HumanoidAMP keeps them (the get-up task, the agent's env info and the tests read them)
+            self._num_amp_obs_steps, self._num_amp_obs_per_step, self._amp_fused = w.num_steps, w.per_step, w.fused
+            self._key_body_ids, self._amp_joint_ids = w.key_body_ids, w.joint_ids
+            self._amp_obs_buf, self._curr_amp_obs_buf, self._hist_amp_obs_buf, self._amp_obs_space = w.buf, w.curr, w.hist, w.space
         if self.save_kin_info:        # HumanoidImDistill.kin_dict (humanoid_im_distill.py:73-80, 204-205)
             self.kin_dict = {"gt_action": torch.zeros(n, self.num_actions, device=dev),
                              "progress_buf": torch.zeros(n, dtype=torch.int64, device=dev)}
@@ -431,12 +400,12 @@ class HumanoidIm:
         return (self.get_obs_size(),)
 
     def get_num_amp_obs(self):
-        return self._num_amp_obs_steps * self._num_amp_obs_per_step
+        return self._amp.num_obs()
 
     def set_amp_obs_sink(self, rows):
         """The NEXT post_physics_step writes its finished AMP window into ``rows`` ((N, >= S W) float32, any row pitch) as well, and hands
         that view out as extras['amp_obs'] -- the agent passes the experience-buffer slot of the step, so recording the window costs no copy."""
-        self._amp_obs_sink = rows
+        self._amp.set_sink(rows)
 
     def set_obs_sink(self, rows):
         """The NEXT post_physics_step also writes its observation rows into ``rows`` ((N, >= obs pitch) float32, any row pitch: the agent passes
@@ -451,77 +420,35 @@ class HumanoidIm:
         return True
 
     def _update_hist_amp_obs(self):
-        """humanoid_amp.py:622-631: shift the history by one slot."""
-        self._hist_amp_obs_buf.copy_(self._amp_obs_buf[:, 0:self._num_amp_obs_steps - 1].clone())
+        self._amp.update_hist()
 
     def _compute_amp_observations(self, env_mask=None):
-        """humanoid_amp.py:632-667 -> current frame into slot 0 of the history."""
-        ops.build_amp_observations_smpl(self.sim.rigid_body_state, self.sim.dof_pos, self.sim.dof_vel, self._key_body_ids,
-                                        joint_ids=self._amp_joint_ids, zero_joints=self._amp_zero_joints, local_root_obs=self._local_root_obs,
-                                        root_height_obs=self._amp_root_height_obs, out=self._curr_amp_obs_buf, env_mask=env_mask,
-                                        shape_params=self._amp_shape_rows, limb_weights=self._amp_limb_rows, **self._amp_variant)
+        self._amp.compute(self.sim, env_mask=env_mask)
 
     def _init_amp_obs(self, mask):
-        """_init_amp_obs (humanoid_amp.py:519-563) for the masked envs.  Slot 0 is the current simulated frame.  With the motion
-        library the envs were reference-state initialised, so the history slots hold the AMP frames of the motion at
-        start - dt * (k + 1) (_init_amp_obs_ref, :531-563; times before the clip clamp to its first frame); with recorded
-        frames there is no motion to look back into and the history repeats the first frame (_init_amp_obs_default, :526-529)."""
-        self._compute_amp_observations(env_mask=mask)
-        s = self._num_amp_obs_steps - 1
-        if self._use_motion_lib and self._amp_fused:
-            ops.amp_hist_init(self._motion_lib, self._sampled_motion_ids, self._motion_start_times, self.dt, mask, self._amp_obs_buf, self._key_body_ids,
-                              joint_ids=self._amp_joint_ids, local_root_obs=self._local_root_obs, root_height_obs=self._amp_root_height_obs,
-                              shape_params=self._amp_motion_shape_rows, limb_weights=self._amp_motion_limb_rows, **self._amp_variant)
-            return
+        """_init_amp_obs (humanoid_amp.py:519-563) for the masked envs: from the motion the envs were reference-state initialised from, or,
+        with recorded frames, copies of the first frame (AmpWindow.init)."""
         if self._use_motion_lib:
-            steps = -self.dt * (torch.arange(0, s, device=self.device) + 1)
-            times = (self._motion_start_times.unsqueeze(-1) + steps).view(-1)
-            n = self.num_envs
-            bufs = self._ref_bufs.setdefault("hist", {})
-            ids = self._sampled_motion_ids.repeat_interleave(s)
-            res = self._motion_lib.query(ids, times, out=bufs, fields=("rb_records", "dof_pos", "dof_vel"))
-            hist = ops.build_amp_observations_smpl(res["rb_records"], res["dof_pos"], res["dof_vel"], self._key_body_ids, joint_ids=self._amp_joint_ids, zero_joints=(),
-                                                   local_root_obs=self._local_root_obs, root_height_obs=self._amp_root_height_obs,
-                                                   **self._amp_motion_rows(ids), **self._amp_variant)
-            hist = hist.view(n, s, self._num_amp_obs_per_step)
+            self._amp.init(self.sim, mask, lib=self._motion_lib, motion_ids=self._sampled_motion_ids, start_times=self._motion_start_times, dt=self.dt,
+                           bufs=self._ref_bufs.setdefault("hist", {}))
         else:
-            hist = self._curr_amp_obs_buf.unsqueeze(1).expand(-1, s, -1)
-        self._hist_amp_obs_buf.copy_(torch.where(mask[:, None, None], hist, self._hist_amp_obs_buf))
-
-    def _amp_motion_rows(self, motion_ids):
-        """The shape / limb rows of reference-motion frames: motion_bodies[ids][:, :-6] / motion_limb_weights[ids] (humanoid_amp.py:243-250,
-        548-555, 672), one row per queried frame."""
-        return {"shape_params": self._amp_motion_shape_rows[motion_ids] if self._amp_motion_shape_rows is not None else None,
-                "limb_weights": self._amp_motion_limb_rows[motion_ids] if self._amp_motion_limb_rows is not None else None}
+            self._amp.init(self.sim, mask)
 
     def fetch_amp_obs_demo(self, num_samples):
-        """humanoid_amp.py:215-284: AMP observation windows of reference motion (synthetic poses here)."""
-        s = self._num_amp_obs_steps
+        """humanoid_amp.py:215-284: AMP observation windows of reference motion (synthetic poses here).  _sample_time (:223-224) resolves
+        to HumanoidIm._sample_time (humanoid_im.py:652-654; HumanoidAMP's own :376-380 does the same for smpl)."""
+        w = self._amp
         if self._use_motion_lib:
-            lib = self._motion_lib
-            ids = lib.sample_motions(num_samples, generator=self._clock_gen)
-            # _sample_time (humanoid_amp.py:223-224) resolves to HumanoidIm._sample_time (humanoid_im.py:652-654; HumanoidAMP's own
-            # :376-380 does the same for smpl): start times on the 1/30 s grid, no frame blending
-            t0 = lib.sample_time_interval(ids, generator=self._clock_gen)
-            steps = -self.dt * torch.arange(0, s, device=self.device)                  # build_amp_obs_demo, :256-262
-            times = (t0.unsqueeze(-1) + steps).view(-1)
-            bufs = self._ref_bufs["demo"] if self._ref_bufs["demo"].get("dof_pos", torch.empty(0)).shape[0] == num_samples * s else {}
-            res = lib.query(ids.repeat_interleave(s), times, out=bufs, with_records=True)
-            self._ref_bufs["demo"] = res
-            rb, dp, dv = res["rb_records"], res["dof_pos"], res["dof_vel"]
-            rows = self._amp_motion_rows(ids.repeat_interleave(s))
+            out, self._ref_bufs["demo"], _, _ = w.fetch_demo(num_samples, self._motion_lib, self.dt, self._clock_gen, bufs=self._ref_bufs["demo"])
         else:
+            s = w.num_steps
             rb, dp, dv = self._motion_lib.sample_demo_states(num_samples * s)
             # recorded frames have no motions to take rows from: the synthetic demo poses wear the envs' own rows, one body per window
             body = (torch.arange(num_samples, device=self.device) % self.num_envs).repeat_interleave(s)
-            rows = {"shape_params": self._amp_shape_rows[body] if self._amp_shape_rows is not None else None,
-                    "limb_weights": self._amp_limb_rows[body] if self._amp_limb_rows is not None else None}
-        out = ops.build_amp_observations_smpl(rb, dp, dv, self._key_body_ids, joint_ids=self._amp_joint_ids, zero_joints=(), local_root_obs=self._local_root_obs,
-                                              root_height_obs=self._amp_root_height_obs, **rows, **self._amp_variant)
-        out = out.view(num_samples, s * self._num_amp_obs_per_step)
-        if self._add_amp_input_noise:                      # build_amp_obs_demo's last statement (humanoid_amp.py:281-283)
-            self._last_amp_noise = torch.randn(out.shape, device=self.device, generator=self._clock_gen if self._use_motion_lib else None)
-            out = out + self._last_amp_noise * 0.01
+            rows = {"shape_params": w.shape_rows[body] if w.shape_rows is not None else None,
+                    "limb_weights": w.limb_rows[body] if w.limb_rows is not None else None}
+            out = w.demo_windows(rb, dp, dv, rows, num_samples)
+        self._last_amp_noise = w.last_noise
         return out
 
     def get_task_obs_size_detail(self):
@@ -678,10 +605,7 @@ class HumanoidIm:
             if getattr(lib, "reloads", False):
                 env = _env_dict(self.cfg)
                 lib.load_motions(random_sample=not bool(env.get("seq_motions", False)), max_len=int(env.get("max_len", -1)))
-                if getattr(self, "_amp_motion_shape_rows", None) is not None:
-                    self._amp_motion_shape_rows = lib.motion_bodies[:, :-6]
-                if getattr(self, "_amp_motion_limb_rows", None) is not None:
-                    self._amp_motion_limb_rows = lib.motion_limb_weights
+                self._refresh_amp_motion_rows()
             else:
                 lib.load_motions()
             if self._use_motion_lib:
@@ -716,13 +640,17 @@ class HumanoidIm:
             self._eval_state["accum"].zero_()
         self.reset()
 
+    def _refresh_amp_motion_rows(self):
+        w, lib = getattr(self, "_amp", None), self._motion_lib
+        if w is not None and w.motion_shape_rows is not None:
+            w.motion_shape_rows = lib.motion_bodies[:, :-6]
+        if w is not None and w.motion_limb_rows is not None:
+            w.motion_limb_rows = lib.motion_limb_weights
+
     def _refresh_motion_rows(self):
         """What depends on which clips are resident: the per-env motion lengths and the AMP frame's per-motion shape / limb rows."""
         lib = self._motion_lib
-        if getattr(self, "_amp_motion_shape_rows", None) is not None:
-            self._amp_motion_shape_rows = lib.motion_bodies[:, :-6]
-        if getattr(self, "_amp_motion_limb_rows", None) is not None:
-            self._amp_motion_limb_rows = lib.motion_limb_weights
+        self._refresh_amp_motion_rows()
         self._motion_len_env = lib.get_motion_length(self._sampled_motion_ids).contiguous()
 
     def eval_curr_motion_ids(self):
@@ -867,21 +795,7 @@ class HumanoidIm:
         self.extras["terminate"] = self._terminate_buf
         self.extras["reward_raw"] = self.reward_raw
         if self._enable_amp_obs:                      # HumanoidAMP.post_physics_step (humanoid_amp.py:194-210)
-            if self._amp_fused:
-                # history shift + current frame (+ the finished window straight into the caller's row, e.g. the experience-buffer slot
-                # the agent registered with set_amp_obs_sink) in ONE launch
-                sink = self._amp_obs_sink
-                ops.build_amp_observations_smpl(self.sim.rigid_body_state, self.sim.dof_pos, self.sim.dof_vel, self._key_body_ids,
-                                                joint_ids=self._amp_joint_ids, zero_joints=self._amp_zero_joints, local_root_obs=self._local_root_obs,
-                                                root_height_obs=self._amp_root_height_obs, out=self._curr_amp_obs_buf,
-                                                hist_steps=self._num_amp_obs_steps, window_out=sink,
-                                                shape_params=self._amp_shape_rows, limb_weights=self._amp_limb_rows, **self._amp_variant)
-                self._amp_obs_sink = None
-                self.extras["amp_obs"] = sink[:, :self.get_num_amp_obs()] if sink is not None else self._amp_obs_buf.view(-1, self.get_num_amp_obs())
-            else:
-                self._update_hist_amp_obs()
-                self._compute_amp_observations()
-                self.extras["amp_obs"] = self._amp_obs_buf.view(-1, self.get_num_amp_obs())
+            self.extras["amp_obs"] = self._amp.step(self.sim)
         if self._eval_state is not None:
             self._eval_accumulate()
 

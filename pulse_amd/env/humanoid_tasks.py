@@ -11,6 +11,21 @@ and pulse_task_step (task observation at its column offset of the same GEMM-read
 The target bookkeeping (_update_task / _reset_task: new target speed / position every tarChangeSteps) is sync-free masked
 tensor code -- the reference reads ``nonzero()`` back every step.
 
+The HumanoidAMP layer every one of these classes inherits in the reference (HumanoidAMPTask -> HumanoidAMP, humanoid_amp_task.py:33,
+humanoid_amp.py:72) is opt-in through ``enable_amp_obs`` (default False: nothing below runs, same launches, draws and buffers) and needs
+a MotionLib (``motion_lib=``):
+  reset from motion      _reset_ref_state_init with the task's _sample_ref_state (humanoid_amp.py:447-488; humanoid_speed.py:251-270,
+                         humanoid_reach.py:46-49, humanoid_strike.py:147-150, humanoid_pedestrian_terrain.py:488-589): a new clip and start
+                         time per reset, ONE launch of pulse_task_ref_state_init (csrc/task_reset.hip) that writes the simulator's state
+                         tensors, the start time, the motion id and clears the episode words
+  AMP window             numAMPObsSteps frames, initialised from that clip (pulse_amp_hist_init), advanced by one fused launch per step
+  AMP observation        extras["amp_obs"], set_amp_obs_sink, _amp_obs_space (AMPAgent then trains its discriminator beside the policy)
+  demonstration windows  fetch_amp_obs_demo
+The window itself is env/amp_window.py, shared with HumanoidIm.  The state the reset writes is the consistent one: the root record is
+the reference's root state, every other body is carried rigidly by the same root transform (include/pulse_hip.h).
+Out of scope: stateInit Default / Hybrid, shape rows for the discriminator, fix_trans_height, a real walkable map
+(Terrain.sample_valid_locations: the terrain task draws its new location uniformly from the interior of the height field).
+
 Physics is out of scope (Isaac Gym): ``sim`` is any object with the tensor surface of pulse_amd/env/sim.py (rigid_body_state,
 dof_force, dof_vel, contact_forces and, for strike, target_states / target_contact_forces).
 """
@@ -22,13 +37,15 @@ from .. import ops
 from .. import synthetic as syn
 from .._lib import PULSE_IM_SELF_OBS, TASK_OBS, TASK_RESET, TASK_REWARD
 from . import env_keys
+from .amp_window import AmpWindow
 from .humanoid_z import HumanoidZ
 
 
 class HumanoidTask:
     TASK = None
+    REF_STATE_TRANSFORM = "none"                    # the class's _sample_ref_state override, as a transform of ops.task_ref_state_init
 
-    def __init__(self, cfg, sim, device="cuda:0"):
+    def __init__(self, cfg, sim, device="cuda:0", motion_lib=None):
         from .humanoid_im import check_humanoid_options
         check_humanoid_options(cfg, type(self).__name__)     # cfg.robot.humanoid_type: the downstream tasks are built for SMPL (raises by name otherwise)
         env = cfg.get("env", cfg)
@@ -83,6 +100,74 @@ class HumanoidTask:
         self.temp_running_mean = bool(env.get("temp_running_mean", True))
         self.save_kin_info = self.only_kin_loss = False
         self.z_type = env.get("z_type", None)
+        self._enable_amp_obs = bool(env.get("enable_amp_obs", False))
+        self._motion_lib = motion_lib
+        if self._enable_amp_obs:
+            self._init_amp(cfg, env)
+
+    # ---- the HumanoidAMP layer (humanoid_amp.py:72-135, 194-284, 447-563)
+    def _init_amp(self, cfg, env):
+        from .humanoid_im import check_amp_options
+        name, lib, dev, n = type(self).__name__, self._motion_lib, self.device, self.num_envs
+        if isinstance(cfg.get("robot", None), dict):                            # robot/*.yaml switches (humanoid.py:266-280 reads cfg.robot)
+            env = dict({k: v for k, v in cfg["robot"].items() if k in ("has_dof_subset", "has_shape_obs_disc", "has_weight_obs_disc")}, **env)
+        if lib is None:
+            raise ValueError(f"{name}: enable_amp_obs needs motion_lib: the reset state, the AMP window's history and the demonstration windows "
+                             "all come from the motion library (humanoid_amp.py:215-284, 447-488, 535-563)")
+        state_init = env.get("stateInit", "Random")
+        if state_init not in ("Random", "Start"):
+            raise NotImplementedError(f"{name}: stateInit {state_init!r}: Random and Start are built (Default / Hybrid need the simulator's "
+                                      "default pose, humanoid_amp.py:447-505)")
+        for key in ("has_shape_obs_disc", "has_weight_obs_disc"):
+            if env.get(key, False):
+                raise NotImplementedError(f"{name}: {key}: the downstream tasks carry no shape rows (humanoid_shapes / humanoid_limb_and_weights, "
+                                          "humanoid.py:739-878; humanoid_amp.py:311-314, 963-966): only HumanoidIm appends them to the AMP frame")
+        if getattr(lib, "num_bodies", self.num_bodies) != self.num_bodies:
+            raise ValueError(f"{name}: the motion library has {lib.num_bodies} bodies, the task {self.num_bodies}")
+        if getattr(self.sim, "dof_pos", None) is None:
+            raise ValueError(f"{name}: enable_amp_obs needs the simulator's dof_pos tensor")
+        self._state_init_random = state_init != "Start"
+        self._amp_gen = torch.Generator(device=dev)
+        self._amp_gen.manual_seed(int(env.get("amp_seed", 4242)))
+        self._sampled_motion_ids = torch.zeros(n, dtype=torch.int64, device=dev)
+        self._motion_start_times = torch.zeros(n, device=dev)
+        self._reset_ref_motion_ids = self._reset_ref_motion_times = None             # the draws of the last reset, every env's (humanoid_amp.py:481-483)
+        self._zero_times = torch.zeros(n, device=dev)
+        self._demo_bufs, self._last_demo = {}, None
+        self._amp = w = AmpWindow(env, num_envs=n, device=dev, skeleton=syn.skeleton("smpl"), local_root_obs=self._local_root_obs,
+                                  upright=self._has_upright_start, amp_obs_v=check_amp_options(env, lib))
+        self._num_amp_obs_steps, self._num_amp_obs_per_step, self._amp_obs_buf, self._amp_obs_space = w.num_steps, w.per_step, w.buf, w.space
+
+    def get_num_amp_obs(self):
+        return self._amp.num_obs()
+
+    def set_amp_obs_sink(self, rows):
+        """The NEXT post_physics_step writes its finished AMP window into ``rows`` as well and hands that view out as extras['amp_obs']."""
+        self._amp.set_sink(rows)
+
+    def fetch_amp_obs_demo(self, num_samples):
+        """humanoid_amp.py:215-284: ``num_samples`` AMP windows of reference motion, drawn with the task's own generator."""
+        out, self._demo_bufs, ids, t0 = self._amp.fetch_demo(num_samples, self._motion_lib, self.dt, self._amp_gen, bufs=self._demo_bufs)
+        self._last_demo = (ids, t0)
+        return out
+
+    def _ref_state_kwargs(self):
+        """The transform arguments of ops.task_ref_state_init beside ``transform`` (the terrain task adds its location and height field)."""
+        return {}
+
+    def _reset_ref_state_init(self, mask):
+        """_reset_ref_state_init (humanoid_amp.py:468-488): a clip and a start time per env (sample_motions / _sample_time draw for every env;
+        the masked ones use theirs), then the simulator's state, the start time, the motion id and the episode words in one launch."""
+        lib, n = self._motion_lib, self.num_envs
+        ids = lib.sample_motions(n, generator=self._amp_gen)
+        times = lib.sample_time_interval(ids, generator=self._amp_gen) if self._state_init_random else self._zero_times
+        self._reset_ref_motion_ids, self._reset_ref_motion_times = ids, times
+        sim = self.sim
+        ops.task_ref_state_init(lib, ids, times, mask, sim.rigid_body_state, sim.dof_pos, sim.dof_vel, self._motion_start_times, self._sampled_motion_ids,
+                                clears=(self.progress_buf, self.reset_buf, self._terminate_buf), transform=self.REF_STATE_TRANSFORM,
+                                upright=self._has_upright_start, **self._ref_state_kwargs())
+        if hasattr(sim, "on_reset"):
+            sim.on_reset(mask)
 
     # ---- sizes
     def _task_obs_width(self, env):
@@ -163,6 +248,8 @@ class HumanoidTask:
         self._compute_observations()
         self.extras["terminate"] = self._terminate_buf
         self.extras["reward_raw"] = raw
+        if self._enable_amp_obs:                      # HumanoidAMP.post_physics_step (humanoid_amp.py:194-210)
+            self.extras["amp_obs"] = self._amp.step(self.sim)
 
     def _add_power_usage_reward(self, raw):
         """humanoid_speed.py:225-238 / humanoid_strike.py:186-198, statement for statement on the kernel's reward (torch ops, as in the
@@ -194,22 +281,28 @@ class HumanoidTask:
 
     def reset_masked(self, mask):
         """_reset_envs (humanoid.py:574-587) + HumanoidAMPTask._reset_envs (task reset before the observation)."""
-        keep = ~mask
-        self.sim.set_env_states_masked(mask)
-        self.progress_buf.mul_(keep)
-        self.reset_buf.mul_(keep)
-        self._terminate_buf.mul_(keep)
+        if self._enable_amp_obs:
+            self._reset_ref_state_init(mask)                    # state from the motion; progress / reset / terminate cleared in the launch
+        else:
+            keep = ~mask
+            self.sim.set_env_states_masked(mask)
+            self.progress_buf.mul_(keep)
+            self.reset_buf.mul_(keep)
+            self._terminate_buf.mul_(keep)
         if self.power_usage_reward and self.TASK == "speed":
             self.power_acc.masked_fill_(mask[:, None], 0.0)     # HumanoidSpeed._reset_ref_state_init (humanoid_speed.py:247-249); the strike task never clears it
         self._reset_task(mask)
         self._compute_observations(env_mask=mask)
+        if self._enable_amp_obs:                                # _init_amp_obs (humanoid_amp.py:519-563): current frame, then the clip's past
+            self._amp.init(self.sim, mask, lib=self._motion_lib, motion_ids=self._sampled_motion_ids, start_times=self._motion_start_times, dt=self.dt)
 
 
 class HumanoidSpeed(HumanoidTask):
     TASK = "speed"
+    REF_STATE_TRANSFORM = "remove_heading"          # humanoid_speed.py:251-270
 
-    def __init__(self, cfg, sim, device="cuda:0"):
-        super().__init__(cfg, sim, device)
+    def __init__(self, cfg, sim, device="cuda:0", motion_lib=None):
+        super().__init__(cfg, sim, device, motion_lib)
         env = cfg.get("env", cfg)
         self._tar_speed_min, self._tar_speed_max = float(env.get("tarSpeedMin", 0.0)), float(env.get("tarSpeedMax", 5.0))
         self._speed_change_steps_min = int(env.get("speedChangeStepsMin", 100))
@@ -233,9 +326,10 @@ class HumanoidSpeed(HumanoidTask):
 
 class HumanoidReach(HumanoidTask):
     TASK = "reach"
+    REF_STATE_TRANSFORM = "zero_xy"                 # humanoid_reach.py:46-49
 
-    def __init__(self, cfg, sim, device="cuda:0"):
-        super().__init__(cfg, sim, device)
+    def __init__(self, cfg, sim, device="cuda:0", motion_lib=None):
+        super().__init__(cfg, sim, device, motion_lib)
         env = cfg.get("env", cfg)
         self._tar_change_steps_min, self._tar_change_steps_max = int(env.get("tarChangeStepsMin", 100)), int(env.get("tarChangeStepsMax", 200))
         self._tar_dist_max = float(env.get("tarDistMax", 1.0))
@@ -262,9 +356,10 @@ class HumanoidReach(HumanoidTask):
 
 class HumanoidStrike(HumanoidTask):
     TASK = "strike"
+    REF_STATE_TRANSFORM = "zero_xy"                 # humanoid_strike.py:147-150
 
-    def __init__(self, cfg, sim, device="cuda:0"):
-        super().__init__(cfg, sim, device)
+    def __init__(self, cfg, sim, device="cuda:0", motion_lib=None):
+        super().__init__(cfg, sim, device, motion_lib)
         env = cfg.get("env", cfg)
         self._tar_dist_min, self._tar_dist_max = float(env.get("tarDistMin", 0.5)), float(env.get("tarDistMax", 10.0))
         self._near_dist, self._near_prob = float(env.get("nearDist", 1.5)), float(env.get("nearProb", 0.5))
@@ -304,7 +399,7 @@ class HumanoidTraj(HumanoidTask):
     TERRAIN_OBS = False
     CROWD = False                                   # the reference's HumanoidTraj never looks at the crowd keys; its terrain task does
 
-    def __init__(self, cfg, sim, device="cuda:0"):
+    def __init__(self, cfg, sim, device="cuda:0", motion_lib=None):
         from .humanoid_im import check_humanoid_options
         check_humanoid_options(cfg, type(self).__name__)     # before the height points go to the device
         env = cfg.get("env", cfg)
@@ -317,7 +412,7 @@ class HumanoidTraj(HumanoidTask):
                 raise NotImplementedError("terrain_obs_type 'square' (env_pulse_terrain.yaml) is built; 'fov' / 'square_fov' are viewer-era variants")
             self._height_points = syn.square_height_points(float(env.get("sensor_extent", 2)), int(env.get("sensor_res", 32))).to(device)
         self._read_crowd_options(env, sim.num_envs)
-        super().__init__(cfg, sim, device)
+        super().__init__(cfg, sim, device, motion_lib)
         dev = self.device
         self._speed_min, self._speed_max = float(env.get("speedMin", 0.0)), float(env.get("speedMax", 3.0))
         self._accel_max, self._sharp_turn_prob = float(env.get("accelMax", 2.0)), float(env.get("sharpTurnProb", 0.02))
@@ -478,6 +573,23 @@ class HumanoidPedestrianTerrain(HumanoidTraj):
     sensor types."""
     TERRAIN_OBS = True
     CROWD = True
+    REF_STATE_TRANSFORM = "terrain"                 # humanoid_pedestrian_terrain.py:527-589
+
+    def _ref_state_kwargs(self):
+        """The new location of every env (:531) and the height field the root is lifted over (:553-563).  Terrain.sample_valid_locations
+        draws from the walkable map of the Isaac scene; here: uniform over the interior of the height field, a sensor reach from its
+        edges, from the generator the motions are drawn with."""
+        hs = self._heightsamples
+        rows, cols = hs.shape if hs is not None else (260, 300)                   # terrainType 'plane': the extent of the synthetic field
+        scale = getattr(self, "_horizontal_scale", 0.1)
+        extent = torch.tensor([rows * scale, cols * scale], device=self.device)
+        margin = 3.0
+        xy = margin + torch.rand(self.num_envs, 2, device=self.device, generator=self._amp_gen) * (extent - 2 * margin)
+        self._new_root_xy = xy
+        kw = {"new_root_xy": xy}
+        if hs is not None:
+            kw.update(heightsamples=hs, horizontal_scale=self._horizontal_scale, vertical_scale=self._vertical_scale, center_points=self._center_points)
+        return kw
 
 
 class _ZMixin(HumanoidZ):
@@ -498,28 +610,28 @@ class _ZMixin(HumanoidZ):
 
 
 class HumanoidSpeedZ(_ZMixin, HumanoidSpeed):
-    def __init__(self, cfg, sim, device="cuda:0"):
-        super().__init__(cfg, sim, device)
+    def __init__(self, cfg, sim, device="cuda:0", motion_lib=None):
+        super().__init__(cfg, sim, device, motion_lib)
         self._init_z(cfg)
 
 
 class HumanoidReachZ(_ZMixin, HumanoidReach):
-    def __init__(self, cfg, sim, device="cuda:0"):
-        super().__init__(cfg, sim, device)
+    def __init__(self, cfg, sim, device="cuda:0", motion_lib=None):
+        super().__init__(cfg, sim, device, motion_lib)
         self._init_z(cfg)
 
 
 class HumanoidStrikeZ(_ZMixin, HumanoidStrike):
-    def __init__(self, cfg, sim, device="cuda:0"):
-        super().__init__(cfg, sim, device)
+    def __init__(self, cfg, sim, device="cuda:0", motion_lib=None):
+        super().__init__(cfg, sim, device, motion_lib)
         self._init_z(cfg)
 
 
 class HumanoidPedestrianTerrainZ(_ZMixin, HumanoidPedestrianTerrain):
     """humanoid_pedestrian_terrain.py:957-972: the terrain task driven through a frozen PULSE decoder (learning=pulse_z_terrain)."""
 
-    def __init__(self, cfg, sim, device="cuda:0"):
-        super().__init__(cfg, sim, device)
+    def __init__(self, cfg, sim, device="cuda:0", motion_lib=None):
+        super().__init__(cfg, sim, device, motion_lib)
         self._init_z(cfg)
 
 
@@ -527,7 +639,7 @@ class SyntheticTaskSim:
     """Physics stand-in for the downstream tasks: a bank of recorded frames (rigid bodies with a drifting root, sparse contact
     forces, a target object) replayed one per control step.  Actions are accepted and ignored, exactly like RecordedSim."""
 
-    def __init__(self, num_envs, frames, device, seed=1234, rank=0, fall_rate=0.01, xy_offset=(0.0, 0.0)):
+    def __init__(self, num_envs, frames, device, seed=1234, rank=0, fall_rate=0.01, xy_offset=(0.0, 0.0), dof_pos_bank=False):
         g = syn.make_generator(seed + 31, rank)
         n, j, f = num_envs, syn.NUM_BODIES, frames
         self.num_envs, self.frames, self.frame = n, f, 0
@@ -548,6 +660,11 @@ class SyntheticTaskSim:
         self.contact_forces = self.bank["contact"][0].clone()
         self.dof_force, self.dof_vel = self.bank["dof_force"][0].clone(), self.bank["dof_vel"][0].clone()
         self.dof_pos = torch.zeros(n, syn.NUM_DOF, device=device)
+        if dof_pos_bank:
+            # joint angles per frame for the AMP frame (enable_amp_obs), from a generator of their own: every other tensor is the same draw
+            # for draw with and without them
+            self.bank["dof_pos"] = (0.5 * torch.randn(f, n, syn.NUM_DOF, generator=syn.make_generator(seed + 57, rank))).to(device)
+            self.dof_pos.copy_(self.bank["dof_pos"][0])
         self.target_states = torch.zeros(n, 13, device=device)
         self.target_states[:, 6] = 1.0
         self.target_contact_forces = self.bank["tar_contact"][0].clone()
@@ -564,6 +681,8 @@ class SyntheticTaskSim:
         self.dof_force.copy_(b["dof_force"][f])
         self.dof_vel.copy_(b["dof_vel"][f])
         self.target_contact_forces.copy_(b["tar_contact"][f])
+        if "dof_pos" in b:
+            self.dof_pos.copy_(b["dof_pos"][f])
 
     def set_env_states_masked(self, mask):
         return

@@ -713,6 +713,60 @@ def amp_hist_init(motion_lib, motion_ids, start_times, dt, env_mask, hist, key_b
     return hist
 
 
+TASK_RESET_TRANSFORMS = {"none": _lib.TASK_RESET_NONE, "zero_xy": _lib.TASK_RESET_ZERO_XY, "remove_heading": _lib.TASK_RESET_REMOVE_HEADING,
+                         "terrain": _lib.TASK_RESET_TERRAIN}
+
+
+def task_ref_state_init(motion_lib, motion_ids, times, env_mask, rb, dof_pos, dof_vel, start_times, sampled_ids, *, clears=(), transform="none",
+                        upright=True, new_root_xy=None, heightsamples=None, horizontal_scale=0.1, vertical_scale=0.005, center_points=None):
+    """_reset_ref_state_init of the downstream tasks (humanoid_amp.py:447-488 with the task's _sample_ref_state) for the masked envs in one
+    launch (pulse_task_ref_state_init): the clip ``motion_ids[e]`` blended at ``times[e]``, the task's root ``transform`` ('none' traj |
+    'zero_xy' reach, strike | 'remove_heading' speed, takes ``upright`` | 'terrain', takes ``new_root_xy`` (N, 2), the int16 height field
+    (None: terrainType 'plane'), its two scales and the (P, 2) centre grid) written into the simulator's tensors ``rb`` (N, J, 13),
+    ``dof_pos`` / ``dof_vel`` (N, 3 (J - 1)) and into ``start_times`` (N,) float32 / ``sampled_ids`` (N,) int64; up to three (N,) int64
+    ``clears`` are zeroed.  Rows outside the mask are left untouched.  The root record is the reference's root state, every other body is
+    carried rigidly by the same transform (include/pulse_hip.h)."""
+    from ._lib import TaskResetArgs
+    if transform not in TASK_RESET_TRANSFORMS:
+        raise ValueError(f"task_ref_state_init: transform must be one of {sorted(TASK_RESET_TRANSFORMS)}, got {transform!r}")
+    rb = _dev(rb, "rb")
+    n, j = rb.shape[0], motion_lib.num_bodies
+    if rb.dim() != 3 or rb.shape[1] != j or rb.shape[2] != 13 or rb.stride(2) != 1 or rb.stride(1) != 13:
+        raise ValueError(f"rb: (N, {j}, 13) records with contiguous rows expected, got shape {tuple(rb.shape)} strides {tuple(rb.stride())}")
+    nd = 3 * (j - 1)
+    f32, i64 = torch.float32, torch.int64
+    for t, name, dtype, shape in ((dof_pos, "dof_pos", f32, (n, nd)), (dof_vel, "dof_vel", f32, (n, nd)), (start_times, "start_times", f32, (n,)),
+                                  (sampled_ids, "sampled_ids", i64, (n,))) + tuple((c, f"clears[{i}]", i64, (n,)) for i, c in enumerate(clears)):
+        _dev(t, name, dtype)
+        if tuple(t.shape) != shape or not t.is_contiguous():              # outputs: a temporary copy would swallow the result
+            raise ValueError(f"{name}: contiguous {shape} expected, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
+    if len(clears) > 3:
+        raise ValueError("task_ref_state_init: at most three clears")
+    a = TaskResetArgs()
+    P = Filler()
+    motion_lib.fill_tables(a.tab)
+    a.num_envs, a.transform, a.upright_start = n, TASK_RESET_TRANSFORMS[transform], int(bool(upright))
+    a.env_mask = P(mask_u8(env_mask), "env_mask", torch.uint8, (n,))
+    a.motion_ids, a.times = P(motion_ids, "motion_ids", i64, (n,)), P(times, "times", f32, (n,))
+    if transform == "terrain":
+        if new_root_xy is None:
+            raise TypeError("task_ref_state_init: transform 'terrain' needs new_root_xy")
+        a.new_root_xy = P(new_root_xy, "new_root_xy", f32, (n, 2))
+        if heightsamples is not None:
+            if heightsamples.dtype != torch.int16 or heightsamples.dim() != 2 or not heightsamples.is_contiguous() or not heightsamples.is_cuda:
+                raise TypeError("heightsamples: contiguous (rows, cols) int16 CUDA tensor expected")
+            if center_points is None:
+                raise TypeError("task_ref_state_init: transform 'terrain' over a height field needs center_points")
+            a.heightsamples, a.map_rows, a.map_cols = heightsamples.data_ptr(), heightsamples.shape[0], heightsamples.shape[1]
+            a.center_points, a.num_center_points = P(center_points, "center_points", f32, (center_points.shape[0], 2)), center_points.shape[0]
+        a.horizontal_scale, a.vertical_scale = float(horizontal_scale), float(vertical_scale)
+    a.rb, a.rb_env_stride = rb.data_ptr(), rb.stride(0)
+    a.dof_pos, a.dof_vel, a.start_times, a.sampled_ids = dof_pos.data_ptr(), dof_vel.data_ptr(), start_times.data_ptr(), sampled_ids.data_ptr()
+    for i, c in enumerate(clears):
+        setattr(a, f"clear{i}", c.data_ptr())
+    _launch("pulse_task_ref_state_init", ctypes.byref(a))
+
+
 # --------------------------------------------------------------------------- #
 # GAE
 # --------------------------------------------------------------------------- #
