@@ -1001,6 +1001,25 @@ int pulse_mcp_head_forward(const float* h, int64_t h_stride, int32_t rows, int32
 int pulse_mcp_head_backward(const float* dmu, int64_t dmu_stride, const float* mu, int64_t mu_stride, const float* aux, int64_t aux_stride,
                             int32_t activation, int32_t rows, int32_t num_prim, float* dz, int64_t dz_stride, pulse_stream_t s);
 
+/* ------------------------------------------------------------------------- *
+ * 4f. The actuation stage of the env step: action -> PD targets, one launch (added without an ABI bump: no existing struct or signature changes).
+ * ------------------------------------------------------------------------- */
+/* The agent's action clamp (phc/learning/im_amp.py:68-73, rl_games' env_step), Humanoid.pre_physics_step (phc/env/tasks/humanoid.py:1222-1247),
+ * Humanoid._action_to_pd_targets (humanoid.py:1392-1394) and HumanoidIm._action_to_pd_targets (phc/env/tasks/humanoid_im.py:1096-1101);
+ * offset / scale are the tables of Humanoid._build_pd_action_offset_scale (humanoid.py:1037-1111).  For e < rows, c < num_dof:
+ *   v = clamp(action[e][c], -clip, clip)                 (torch.clamp: a NaN passes through; clip = inf clamps nothing)
+ *   clamped[e][c] = v                                    (the copy the reference keeps as self.actions; clamped == NULL: not written;
+ *                                                         clamped may alias action)
+ *   plain form    (ref_dof_pos == NULL): t = offset[c] + scale[c] * v                      (offset == NULL: 0)
+ *   residual form (ref_dof_pos != NULL): t = max(min(ref_dof_pos[e][c] + scale[c] * v, sim_dof_pos[e][c] + pi/2), sim_dof_pos[e][c] - pi/2)
+ *                                        (torch.minimum / torch.maximum: a NaN on either side wins; pi/2 rounded to fp32)
+ *   target[e][c] = freeze[c] ? 0 : t                     (freeze: num_dof bytes, the freeze_hand / freeze_toe columns; NULL: none)
+ * The product is rounded to fp32 before the sum (no FMA).  Every row stride is in floats and >= num_dof; columns past num_dof are not touched.
+ * rows * num_dof < 2^31.  rows == 0 is a no-op. */
+int pulse_pd_targets(const float* action, int64_t action_stride, int32_t rows, int32_t num_dof, float clip, const float* offset, const float* scale,
+                     const uint8_t* freeze, const float* ref_dof_pos, int64_t ref_stride, const float* sim_dof_pos, int64_t sim_stride,
+                     float* clamped, int64_t clamped_stride, float* target, int64_t target_stride, pulse_stream_t s);
+
 /* out[i] = scale * sum_s slabs[s*slab_stride + i]  (deterministic split-K / partial-sum reduction) */
 int pulse_reduce_slabs(const float* slabs, int32_t num_slabs, int64_t slab_stride, int64_t count, float* out,
                        float scale, pulse_stream_t s);

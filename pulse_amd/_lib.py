@@ -376,6 +376,7 @@ SIGNATURES = {
     "pulse_mcp_compose": (c_int, [P, c_int64, P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, P, c_int64, P]),
     "pulse_mcp_head_forward": (c_int, [P, c_int64, c_int32, c_int32, P, c_int64, P]),
     "pulse_mcp_head_backward": (c_int, [P, c_int64, P, c_int64, P, c_int64, c_int32, c_int32, c_int32, P, c_int64, P]),
+    "pulse_pd_targets": (c_int, [P, c_int64, c_int32, c_int32, c_float, P, P, P, P, c_int64, P, c_int64, P, c_int64, P, c_int64, P]),
     "pulse_sizeof_gemm_x3p_desc": (c_int, []),
     "pulse_split_planes": (c_int, [P, c_int64, c_int32, c_int32, P, c_int64, c_int32, c_int32, P, P]),
     "pulse_reduce_slabs": (c_int, [P, c_int32, c_int64, c_int64, P, c_float, P]),

@@ -202,6 +202,16 @@ CONFIGS = {
 # cfg.robot of the two shipped humanoids (robot/smpl_humanoid.yaml, robot/smplx_humanoid.yaml: humanoid_type and has_upright_start)
 ROBOTS = {"smpl": {"humanoid_type": "smpl", "has_upright_start": True}, "smplx": {"humanoid_type": "smplx", "has_upright_start": False},
           "smplh": {"humanoid_type": "smplh", "has_upright_start": False}}
+# the actuation switches as all three shipped robot files spell them (robot/smpl_humanoid.yaml:2, 8, 19-20 and the same lines of the other two):
+# robot_config() carries them explicitly, so what a config computes does not hang on a default (env/robot_keys.py, "defaults")
+ROBOT_ACTUATION = {"bias_offset": False, "has_smpl_pd_offset": False, "freeze_toe": False, "freeze_hand": False}
+
+
+def robot_config(humanoid="smpl", **overrides):
+    """cfg.robot of a shipped humanoid with the actuation switches spelled out, plus ``overrides``."""
+    if humanoid not in ROBOTS:
+        raise NotImplementedError(f"humanoid {humanoid!r}: 'smpl', 'smplh' and 'smplx' are built")
+    return {**ROBOTS[humanoid], **ROBOT_ACTUATION, **overrides}
 
 
 def agent_config(name, **overrides):
@@ -237,16 +247,20 @@ def agent_config(name, **overrides):
 
 
 def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kind="im", reference="recorded", env_overrides=None, humanoid="smpl",
-             num_clips=None):
+             num_clips=None, robot_overrides=None, dof_limits=None):
     """``humanoid``: 'smpl' (24 bodies) | 'smplx' / 'smplh' (52 bodies) -- the robot config handed to the task as cfg.robot.
     ``reference``: 'recorded' = pre-recorded rigid-body / reference frames (RecordedRollout, what the CPU oracle agent replays);
     'motion_lib' = reference motion queried from the HBM-resident MotionLib every step, physics stand-in tracking it;
     'motion_data' = the same, with the library built on the device from synthetic RAW clips (MotionLib.from_motion_data: one resident clip per
-    env out of ``num_clips`` unique ones -- min(num_envs, 1024) / 2 + 1 unless given -- re-drawn by resample_motions)."""
+    env out of ``num_clips`` unique ones -- min(num_envs, 1024) / 2 + 1 unless given -- re-drawn by resample_motions).
+    ``robot_overrides``: cfg.robot keys on top of the humanoid's (bias_offset, has_smpl_pd_offset, freeze_toe, freeze_hand, ...).
+    ``dof_limits``: the joint limits the stand-in simulator publishes -- None (none: the PD-target table stays offset 0 / scale 1), True
+    (synthetic.synthetic_dof_limits of the humanoid) or a (lower, upper) pair."""
     from .env.humanoid_im import HumanoidIm, VecTaskPythonWrapper, check_humanoid_options
-    if humanoid not in ROBOTS:
-        raise NotImplementedError(f"humanoid {humanoid!r}: 'smpl', 'smplh' and 'smplx' are built")
-    robot = dict(ROBOTS[humanoid])
+    robot = robot_config(humanoid, **(robot_overrides or {}))
+    if dof_limits is True:
+        from . import synthetic as _syn
+        dof_limits = _syn.synthetic_dof_limits(humanoid)
     if env_kind in ("speed_z", "reach_z", "strike_z", "terrain_z"):
         # HumanoidSpeedZ & co: synthetic task physics, the frozen decoder initialised from a (random-init) PULSE checkpoint
         import torch
@@ -257,7 +271,7 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
         # the terrain task's humanoids walk inside the synthetic height field (cells of 0.1 m): start them near its middle
         amp = bool(env_cfg.get("enable_amp_obs", False))
         sim = HT.SyntheticTaskSim(num_envs, horizon + 1, device, seed=seed, rank=rank, xy_offset=(13.0, 15.0) if env_kind == "terrain_z" else (0.0, 0.0),
-                                  dof_pos_bank=amp)
+                                  dof_pos_bank=amp, dof_limits=dof_limits)
         motion = None
         if amp:                                          # the HumanoidAMP layer resets from, looks back into and demonstrates with a motion library
             from . import synthetic as syn
@@ -265,7 +279,7 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
             motion = MotionLib.from_tables(syn.synthetic_motion_library(syn.make_generator(seed + 5, rank), min(num_envs, 1024)), device)
         cls = {"speed_z": HT.HumanoidSpeedZ, "reach_z": HT.HumanoidReachZ, "strike_z": HT.HumanoidStrikeZ,
                "terrain_z": HT.HumanoidPedestrianTerrainZ}[env_kind]
-        task = cls({"env": env_cfg} if humanoid == "smpl" else {"env": env_cfg, "robot": robot}, sim, device=device, motion_lib=motion)
+        task = cls({"env": env_cfg, "robot": robot}, sim, device=device, motion_lib=motion)
         znet = AMPZNetwork(NETWORK_Z, actions_num=69, self_obs_size=task.get_self_obs_size(), task_obs_size=576,
                            task_obs_size_detail=dict({"embedding_size": 32, "z_type": "vae", "use_vae_prior": True, "use_vae_clamped_prior": True,
                                                       "vae_var_clamp_max": 2}, **task._z_detail), device=device)   # (the env dict's prior / posterior variant)
@@ -281,11 +295,11 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
         from .env.sim import KinematicSim, PdSim
         env_cfg = dict(ENV_MCP)
         env_cfg.update(env_overrides or {})
-        cfg = {"env": env_cfg} if humanoid == "smpl" else {"env": env_cfg, "robot": robot}
+        cfg = {"env": env_cfg, "robot": robot}
         opts = check_mcp_options(cfg, "HumanoidImMCPGetup")
         motion = MotionLib.from_tables(syn.synthetic_motion_library(syn.make_generator(seed + 5, rank), min(num_envs, 1024)), device)
         sim_cls = PdSim if env_cfg.pop("physics", "tracking") == "pd" else KinematicSim
-        sim = sim_cls(num_envs, horizon + 1, device, seed=seed, rank=rank)
+        sim = sim_cls(num_envs, horizon + 1, device, seed=seed, rank=rank, dof_limits=dof_limits)
         # env.models given: that checkpoint (path or dict); otherwise the synthetic one, sized once the env knows its observation width
         make = None if env_cfg.get("models") else (lambda t: syn.synthetic_pnn_checkpoint(opts["num_prim"], in_dim=t.num_obs, seed=seed + 11,
                                                                                           has_lateral=opts["has_lateral"]))
@@ -301,9 +315,9 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
         from . import synthetic as syn
         from .env.motion_lib import MotionLib
         from .env.sim import KinematicSim, PdSim
-        cfg = {"env": env_cfg} if humanoid == "smpl" else {"env": env_cfg, "robot": robot}
+        cfg = {"env": env_cfg, "robot": robot}
         check_humanoid_options(cfg)                     # an unbuilt combination raises by name before anything is allocated
-        disc_rows = any(bool(dict(robot if humanoid != "smpl" else {}, **env_cfg).get(k, False)) for k in ("has_shape_obs_disc", "has_weight_obs_disc"))
+        disc_rows = any(bool(dict(robot, **env_cfg).get(k, False)) for k in ("has_shape_obs_disc", "has_weight_obs_disc"))
         if reference == "motion_data":
             g = syn.make_generator(seed + 5, rank)
             data, trees = syn.synthetic_motion_data(g, min(num_envs, 1024) // 2 + 1 if num_clips is None else int(num_clips), humanoid=humanoid,
@@ -314,16 +328,16 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
             tables = syn.synthetic_motion_library(syn.make_generator(seed + 5, rank), min(num_envs, 1024), humanoid=humanoid, shape_rows=disc_rows)
             motion = MotionLib.from_tables(tables, device)
         sim_cls = PdSim if env_cfg.pop("physics", "tracking") == "pd" else KinematicSim        # "pd": action-dependent stand-in
-        sim = sim_cls(num_envs, horizon + 1, device, seed=seed, rank=rank, humanoid=humanoid)
+        sim = sim_cls(num_envs, horizon + 1, device, seed=seed, rank=rank, humanoid=humanoid, dof_limits=dof_limits)
         task = HumanoidIm(cfg, sim, motion, device=device)
         return VecTaskPythonWrapper(task, rl_device=device), None
     from .env.sim import RecordedMotion, RecordedRollout, RecordedSim
-    cfg = {"env": env_cfg} if humanoid == "smpl" else {"env": env_cfg, "robot": robot}
+    cfg = {"env": env_cfg, "robot": robot}
     check_humanoid_options(cfg)
     if rollout is None:
         rollout = RecordedRollout(num_envs, horizon + 1, seed=seed, rank=rank, humanoid=humanoid)
     rollout.to(device)
-    sim = RecordedSim(rollout)
+    sim = RecordedSim(rollout, dof_limits=dof_limits)
     motion = RecordedMotion(rollout, sim)
     task = HumanoidIm(cfg, sim, motion, device=device)
     task.progress_buf.copy_(rollout.init_progress)

@@ -61,6 +61,7 @@ SOURCES = [
     ("b16_ops.hip", NO_CONTRACT),
     ("vae_head.hip", NO_CONTRACT),
     ("mcp.hip", NO_CONTRACT),
+    ("pd_targets.hip", NO_CONTRACT),
 ]
 
 

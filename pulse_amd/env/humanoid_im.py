@@ -32,7 +32,8 @@ import torch
 
 from .. import ops
 from .. import synthetic as syn
-from . import env_keys
+from . import env_keys, robot_keys
+from .actuation import Actuation
 from .amp_window import AmpWindow, Box          # noqa: F401  (Box: imported from here by the other env modules)
 from .._lib import PULSE_IM_RESET, PULSE_IM_REWARD, PULSE_IM_SELF_OBS, PULSE_IM_TASK_OBS
 
@@ -119,6 +120,7 @@ class HumanoidIm:
                                                                      "has_shape_obs_disc", "has_weight_obs_disc")}, **env)
         self.amp_obs_v = check_amp_options(env, motion_lib)                    # (first: an amp_obs_v that does not exist is a ValueError)
         env_keys.audit(env, type(self).__name__)                               # every key is honoured, inert by contract, or raises by name
+        robot_keys.audit(cfg.get("robot", None), type(self).__name__, sk["body_names"])        # the same for cfg.robot
         self.cfg = cfg
         self.device = torch.device(device)
         self.sim, self._motion_lib = sim, motion_lib
@@ -218,8 +220,9 @@ class HumanoidIm:
                                                   device=self.device)
         self._termination_distances = torch.full((self.num_bodies,), float(env.get("terminationDistance", 0.25)), device=self.device)
         self._dof_size = sk["num_dof"]
-        self._pd_action_offset = torch.zeros(self._dof_size, device=self.device)
-        self._pd_action_scale = torch.ones(self._dof_size, device=self.device)
+        # the actuation stage (humanoid.py:1037-1111, 1222-1247): the table from the simulator's joint limits, the freeze switches of cfg.robot
+        self._actuation = Actuation(sk, cfg.get("robot", None), sim, self.device, upright=self._has_upright_start)
+        self._pd_action_offset, self._pd_action_scale = self._actuation.offset, self._actuation.scale
         self.clip_obs = float("inf")                                            # parse_task.py:68
         # ---- sizes (humanoid.py:653, humanoid_im.py:457-491)
         lib = ops._lib.load()
@@ -467,24 +470,25 @@ class HumanoidIm:
         self._physics_step()
         self.post_physics_step()
 
-    def _action_to_pd_targets(self, action):
-        if self._res_action:
-            # humanoid_im.py:1096-1101: residual action around the reference pose the last _compute_task_obs stored (ref_dof_pos = the t + 1
-            # reference's dof positions, :841-848 -- here the buffer the fused step writes for the physics stand-in), clamped to +- pi / 2
-            # around the simulated pose
-            pd_tar = self._track["dof_pos"] + self._pd_action_scale * action
-            pd_lower = self.sim.dof_pos - torch.pi / 2
-            pd_upper = self.sim.dof_pos + torch.pi / 2
-            return torch.maximum(torch.minimum(pd_tar, pd_upper), pd_lower)
-        return torch.addcmul(self._pd_action_offset, self._pd_action_scale, action)   # offset + scale * action, humanoid.py:1392-1394
+    def set_action_clip(self, clip):
+        """VecTaskPythonWrapper hands its clip_actions down: the clamp runs inside the actuation launch.  True = taken; a
+        subclass whose step() does not take the PD action itself (the latent / composer envs) returns False and the wrapper clamps."""
+        self._actuation.clip = float(clip)
+        return True
 
     def pre_physics_step(self, actions):
-        self.actions = actions
         if (self.cycle_motion or (self.zero_out_far and self.zero_out_far_train)) and self._use_motion_lib:
             self._update_cycle_count()                      # (the counter only ever leaves zero in these modes)
         if self._occl_training:
             self._update_occl_training()                    # humanoid_im.py:1114-1115
-        self.sim.set_dof_position_target_tensor(self._action_to_pd_targets(actions))
+        # humanoid.py:1226-1247, 1392-1394: self.actions (the clamped copy) and offset + scale * action, frozen joints at 0, in one launch.
+        # res_action (humanoid_im.py:1096-1101): around the reference pose the last _compute_task_obs stored (ref_dof_pos = the t + 1 reference's
+        # dof positions, :841-848 -- here the buffer the fused step writes for the physics stand-in), held inside +- pi / 2 of the simulated pose
+        if self._res_action:
+            self.actions, pd_tar = self._actuation(actions, self._track["dof_pos"], self.sim.dof_pos)
+        else:
+            self.actions, pd_tar = self._actuation(actions)
+        self.sim.set_dof_position_target_tensor(pd_tar)
 
     def _physics_step(self):
         self.sim.simulate_and_refresh()                                         # Isaac Gym: OUT OF SCOPE
@@ -871,6 +875,9 @@ class VecTaskPythonWrapper:
         self.num_obs = task.num_obs
         self.num_actions = task.num_actions
         self.clip_obs, self.clip_actions = clip_observations, clip_actions
+        # the task clamps inside its actuation launch where its step() takes the PD action itself (set_action_clip); otherwise the clamp runs here
+        take = getattr(task, "set_action_clip", None)
+        self._task_clips = bool(take(clip_actions)) if take is not None else False
         self.obs_space = Box(-float("inf"), float("inf"), (self.num_obs,))
         self.act_space = Box(-1.0, 1.0, (self.num_actions,))
         self.rl_device = rl_device
@@ -883,7 +890,7 @@ class VecTaskPythonWrapper:
         self.obs_carries_over = True
 
     def step(self, actions):
-        actions_tensor = torch.clamp(actions, -self.clip_actions, self.clip_actions)
+        actions_tensor = actions if self._task_clips else torch.clamp(actions, -self.clip_actions, self.clip_actions)
         self.task.step(actions_tensor)
         obs = self.task.obs_buf
         if self.clip_obs != float("inf"):

@@ -77,6 +77,10 @@ class HumanoidImMCP(HumanoidIm):
         ops.mcp_compose(weights, x_all, self._mcp_actions, num_actions=self._dof_size, discrete=self.discrete_mcp)
         return self._mcp_actions
 
+    def set_action_clip(self, clip):
+        """The wrapper's clip_actions bounds the composer's weights, not the composed PD action: the clamp stays in the wrapper."""
+        return False
+
     def step(self, weights):
         super().step(self.compose_actions(weights))
 

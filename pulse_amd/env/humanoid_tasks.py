@@ -36,7 +36,8 @@ import torch
 from .. import ops
 from .. import synthetic as syn
 from .._lib import PULSE_IM_SELF_OBS, TASK_OBS, TASK_RESET, TASK_REWARD
-from . import env_keys
+from . import env_keys, robot_keys
+from .actuation import Actuation
 from .amp_window import AmpWindow
 from .humanoid_z import HumanoidZ
 
@@ -50,6 +51,9 @@ class HumanoidTask:
         check_humanoid_options(cfg, type(self).__name__)     # cfg.robot.humanoid_type: the downstream tasks are built for SMPL (raises by name otherwise)
         env = cfg.get("env", cfg)
         env_keys.audit(env, type(self).__name__)             # every key is honoured, inert by contract, or raises by name
+        robot_keys.audit(cfg.get("robot", None), type(self).__name__, syn.SMPL_BODY_NAMES, unread=robot_keys.TASK_UNREAD)   # the same for cfg.robot
+        if isinstance(cfg.get("robot", None), dict) and "has_upright_start" in cfg["robot"]:    # humanoid.py:355 reads it from cfg.robot; the env dict's wins
+            env = dict({"has_upright_start": cfg["robot"]["has_upright_start"]}, **env)
         self.cfg, self.sim = cfg, sim
         self.device = torch.device(device)
         self.num_envs, self.num_bodies = sim.num_envs, syn.NUM_BODIES
@@ -63,6 +67,9 @@ class HumanoidTask:
         self.power_reward = bool(env.get("power_reward", False))
         self.power_coefficient = float(env.get("power_coefficient", 0.0005))
         self._dof_size = syn.NUM_DOF
+        # the actuation stage (humanoid.py:1037-1111, 1222-1247): the table from the simulator's joint limits, the freeze switches of cfg.robot
+        self._actuation = Actuation(syn.skeleton("smpl"), cfg.get("robot", None), sim, self.device, upright=self._has_upright_start)
+        self._pd_action_offset, self._pd_action_scale = self._actuation.offset, self._actuation.scale
         # power_usage_reward (humanoid_speed.py:43-53, 225-238; humanoid_strike.py:37-40, 186-198): a penalty on the difference between the
         # accumulated |torque x velocity| of the left and the right joints.  Only those two task classes read the key.
         self.power_usage_reward = bool(env.get("power_usage_reward", False)) and self.TASK in ("speed", "strike")
@@ -227,10 +234,16 @@ class HumanoidTask:
         if self._enable_task_obs:
             self._task_step(TASK_OBS, env_mask=env_mask)
 
+    def set_action_clip(self, clip):
+        """VecTaskPythonWrapper hands its clip_actions down: the clamp runs inside the actuation launch."""
+        self._actuation.clip = float(clip)
+        return True
+
     def pre_physics_step(self, actions):
-        self.actions = actions
         self._prev_root_pos.copy_(self.sim.rigid_body_state[:, 0, 0:3])                 # humanoid_speed.py:72-75
-        self.sim.set_dof_position_target_tensor(actions)
+        # humanoid.py:1226-1247, 1392-1394: self.actions (the clamped copy) and offset + scale * action, frozen joints at 0, in one launch
+        self.actions, pd_tar = self._actuation(actions)
+        self.sim.set_dof_position_target_tensor(pd_tar)
         self._update_task()          # HumanoidAMPTask.pre_physics_step (humanoid_amp_task.py:57-59): BEFORE progress_buf advances
 
     def step(self, actions):
@@ -639,7 +652,7 @@ class SyntheticTaskSim:
     """Physics stand-in for the downstream tasks: a bank of recorded frames (rigid bodies with a drifting root, sparse contact
     forces, a target object) replayed one per control step.  Actions are accepted and ignored, exactly like RecordedSim."""
 
-    def __init__(self, num_envs, frames, device, seed=1234, rank=0, fall_rate=0.01, xy_offset=(0.0, 0.0), dof_pos_bank=False):
+    def __init__(self, num_envs, frames, device, seed=1234, rank=0, fall_rate=0.01, xy_offset=(0.0, 0.0), dof_pos_bank=False, dof_limits=None):
         g = syn.make_generator(seed + 31, rank)
         n, j, f = num_envs, syn.NUM_BODIES, frames
         self.num_envs, self.frames, self.frame = n, f, 0
@@ -669,6 +682,8 @@ class SyntheticTaskSim:
         self.target_states[:, 6] = 1.0
         self.target_contact_forces = self.bank["tar_contact"][0].clone()
         self.pd_targets = None
+        from .sim import publish_dof_limits
+        publish_dof_limits(self, dof_limits, syn.NUM_DOF, device)
 
     def set_dof_position_target_tensor(self, pd_tar):
         self.pd_targets = pd_tar

@@ -72,6 +72,11 @@ class HumanoidZ:
         G["fwd_dec"].run()
         return g.act_bufs["mu"][:, :self._dof_size]
 
+    def set_action_clip(self, clip):
+        """The wrapper's clip_actions bounds what step() takes, the latent: the decoded PD action is not clamped (the reference's wrapper never
+        sees it), so the clamp stays in the wrapper."""
+        return False
+
     def step_z(self, action_z):
         self.action_z = action_z
         actions = self.compute_z_actions(action_z)
@@ -89,6 +94,8 @@ class HumanoidImZ(HumanoidIm, HumanoidZ):
         self._embedding_size = int(env.get("embedding_size", 32))
         self.num_actions = self._embedding_size                                # _setup_character_props_z (:65-67)
         self._read_z_options(env)
+
+    set_action_clip = HumanoidZ.set_action_clip
 
     def step(self, action_z):
         self.step_z(action_z)

@@ -19,6 +19,17 @@ from .._lib import PdSimArgs
 from .._marshal import Filler, launch, ptr
 
 
+def publish_dof_limits(sim, dof_limits, num_dof, device):
+    """``dof_limits``: None, or the (lower, upper) pair of (D,) joint limits the stand-in publishes as ``dof_limits_lower`` / ``dof_limits_upper``
+    (Isaac's get_actor_dof_properties, humanoid.py:867-896; e.g. synthetic.synthetic_dof_limits): the envs build their PD-target table from them."""
+    if dof_limits is None:
+        return
+    lo, hi = (torch.as_tensor(t, dtype=torch.float32).to(device) for t in dof_limits)
+    if tuple(lo.shape) != (num_dof,) or tuple(hi.shape) != (num_dof,):
+        raise ValueError(f"dof_limits: two ({num_dof},) arrays expected, got {tuple(lo.shape)} and {tuple(hi.shape)}")
+    sim.dof_limits_lower, sim.dof_limits_upper = lo, hi
+
+
 class RecordedRollout:
     """frames[f] for f in 0..num_frames-1: everything one env step reads."""
 
@@ -77,7 +88,7 @@ class RecordedRollout:
 class RecordedSim:
     """Isaac-Gym-shaped tensor API over a RecordedRollout (device resident)."""
 
-    def __init__(self, rollout):
+    def __init__(self, rollout, dof_limits=None):
         self.rollout = rollout
         dev = rollout.data["rb"].device
         n = rollout.num_envs
@@ -89,6 +100,7 @@ class RecordedSim:
         self.dof_pos = rollout.data["dof_pos"][0].clone()
         self.skeleton = rollout.skeleton
         self.pd_targets = torch.zeros(n, self.skeleton["num_dof"], device=dev)
+        publish_dof_limits(self, dof_limits, self.skeleton["num_dof"], dev)
 
     @property
     def gt_action(self):
@@ -165,7 +177,7 @@ class KinematicSim:
     (humanoid_amp.py:447-488, humanoid_im.py:966-986) writes the motion state unperturbed.  Same tensor surface as
     RecordedSim.  The noise bank is generated on the CPU (pulse_amd/synthetic.py generator) so a CPU twin can replay it."""
 
-    def __init__(self, num_envs, bank_frames, device, seed=1234, rank=0, drift_rate=0.01, humanoid="smpl"):
+    def __init__(self, num_envs, bank_frames, device, seed=1234, rank=0, drift_rate=0.01, humanoid="smpl", dof_limits=None):
         g = syn.make_generator(seed + 17, rank)
         self.skeleton = sk = syn.skeleton(humanoid)
         n, j, f, nd = num_envs, sk["num_bodies"], bank_frames, sk["num_dof"]
@@ -188,6 +200,7 @@ class KinematicSim:
         self.dof_vel = torch.zeros(n, nd, device=device)
         self.dof_pos = torch.zeros(n, nd, device=device)
         self.pd_targets = torch.zeros(n, nd, device=device)
+        publish_dof_limits(self, dof_limits, nd, device)
         self._target = None
 
     @property
@@ -219,8 +232,8 @@ class PdSim(KinematicSim):
     by the return-parity experiment (tools/return_parity.py) -- the bench keeps KinematicSim.  The CPU twin is
     oracle/pd_sim_oracle.py; both draw the disturbance bank with the same generator recipe."""
 
-    def __init__(self, num_envs, bank_frames, device, seed=1234, rank=0, humanoid="smpl"):
-        super().__init__(num_envs, bank_frames, device, seed=seed, rank=rank, humanoid=humanoid)
+    def __init__(self, num_envs, bank_frames, device, seed=1234, rank=0, humanoid="smpl", dof_limits=None):
+        super().__init__(num_envs, bank_frames, device, seed=seed, rank=rank, humanoid=humanoid, dof_limits=dof_limits)
         g = syn.make_generator(seed + 23, rank)
         nd = self.skeleton["num_dof"]
         self.bank["acc"] = (syn.PD_SIM["noise_acc"] * torch.randn(bank_frames, num_envs, nd, generator=g)).to(device)

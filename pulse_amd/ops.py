@@ -1011,3 +1011,41 @@ def mcp_compose(weights, x, out=None, *, num_actions=None, discrete=False):
     op, os_ = rows2d(out, "out", n, a)
     _launch("pulse_mcp_compose", wp, ws, _ptr(x), x.stride(0) if n else p * x.stride(1), x.stride(1), n, p, a, int(bool(discrete)), op, os_)
     return out[:, :a]
+
+
+# --------------------------------------------------------------------------- #
+# Actuation stage (include/pulse_hip.h section 4f)
+# --------------------------------------------------------------------------- #
+def pd_targets(action, scale, *, clip=float("inf"), offset=None, freeze=None, ref_dof_pos=None, sim_dof_pos=None, clamped=None, target=None):
+    """The env step's actuation stage in one launch (the agent's action clamp, phc/learning/im_amp.py:68-73; Humanoid.pre_physics_step,
+    phc/env/tasks/humanoid.py:1222-1247; _action_to_pd_targets, humanoid.py:1392-1394 and humanoid_im.py:1096-1101): ``action`` (N, D), rows may
+    be a pitched view -> (clamped, target), both (N, D) (allocated when None; pitched views are written in their first D columns only).
+    clamped = clamp(action, -clip, clip); target = offset + scale * clamped, or with ``ref_dof_pos`` / ``sim_dof_pos`` (res_action) ref + scale *
+    clamped held inside sim_dof_pos -+ pi / 2; columns whose ``freeze`` byte is set get target 0.  ``offset`` / ``scale`` (D,) float32, ``freeze``
+    (D,) uint8 / bool."""
+    _dev(action, "action")
+    if action.dim() != 2:
+        raise ValueError(f"pd_targets: action (N, D) expected, got {tuple(action.shape)}")
+    n, d = action.shape
+    clip = float(clip)
+    if not clip >= 0.0:
+        raise ValueError(f"pd_targets: clip = {clip!r}: a bound >= 0 (inf for none)")
+    if (ref_dof_pos is None) != (sim_dof_pos is None):
+        raise ValueError("pd_targets: the residual form takes ref_dof_pos and sim_dof_pos together")
+    P = Filler()
+    ap, as_ = rows2d(action, "action", n, d)
+    sp = P(scale, "scale", shape=(d,))
+    op = P(offset, "offset", shape=(d,))
+    fp = P(None if freeze is None else mask_u8(freeze), "freeze", torch.uint8, shape=(d,))
+    rp, rs, mp, ms = None, 0, None, 0
+    if ref_dof_pos is not None:
+        rp, rs = rows2d(ref_dof_pos, "ref_dof_pos", n, d)
+        mp, ms = rows2d(sim_dof_pos, "sim_dof_pos", n, d)
+    if clamped is None:
+        clamped = torch.empty(n, d, dtype=torch.float32, device=action.device)
+    if target is None:
+        target = torch.empty(n, d, dtype=torch.float32, device=action.device)
+    cp, cs = rows2d(clamped, "clamped", n, d)
+    tp, ts = rows2d(target, "target", n, d)
+    _launch("pulse_pd_targets", ap, as_, n, d, clip, op, sp, fp, rp, rs, mp, ms, cp, cs, tp, ts)
+    return clamped[:, :d], target[:, :d]

@@ -328,6 +328,18 @@ def synthetic_motion_data(g, num_clips, humanoid="smpl", frames=None, min_frames
 PD_SIM = {"kp": 400.0, "kd": 40.0, "substeps": 2, "action_scale": 0.25, "lever": 0.3, "noise_acc": 2.0}
 
 
+def synthetic_dof_limits(humanoid="smpl", seed=0):
+    """Joint limits a simulator would publish (Isaac's get_actor_dof_properties, humanoid.py:867-896): (lower, upper), two (D,) float32 CPU
+    tensors with lower < upper.  Half-widths in 0.3 .. 3.0 rad, so that some joints' 1.2 max|limit| passes pi and others' does not (the cap of
+    _build_pd_action_offset_scale, humanoid.py:1050-1054); about half of the dofs are off-centre, so the two bias_offset branches differ."""
+    sk = skeleton(humanoid)
+    g = make_generator(9100 + seed)
+    d = sk["num_dof"]
+    half = 0.3 + 2.7 * _rand(g, d)
+    centre = torch.where(_rand(g, d) < 0.5, (_rand(g, d) - 0.5) * half, torch.zeros(d))
+    return (centre - half).contiguous(), (centre + half).contiguous()
+
+
 def pd_sim_tables(humanoid="smpl"):
     """(sag (num_dof,), lever_dir (num_bodies, 3)): a constant per-joint offset of the PD set point the policy has to learn to cancel, and the
     unit 'bone' directions that turn a joint-angle error into a body displacement.  Deterministic (no RNG state involved)."""
