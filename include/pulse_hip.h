@@ -938,6 +938,31 @@ typedef struct pulse_vae_embed_args {
     int32_t sphere_posterior; float embedding_norm;   /* needs embedding_size <= 32 */
 } pulse_vae_embed_args;
 int pulse_vae_embed(const pulse_vae_embed_args* args, pulse_stream_t s);
+/* The generation step: form_embedding under flags.debug, amp_network_z_builder.py:101-119, 226-248 -- z is drawn from the PRIOR and the encoder
+ * heads are never read (added without an ABI bump: no existing struct or signature changes).  Per row, in the reference's operation order:
+ *   LEARNED / FIXED  (mu, logvar) as compute_prior returns them (:226-241: learned log-variance clamped under clamp_logvar; fixed mean through
+ *                    project_to_norm under sphere_prior, constant unclamped log-variance);  z = mu + eps * exp(0.5 logvar)  (reparameterize, :245-248)
+ *                    logvar_override != 0: logvar = logvar_override_value instead (the temperature variants commented at :110-111; not clamped)
+ *                    eps == NULL: z = mu (the prior-mean variant, :109)
+ *   NONE             z = eps (:116); eps == NULL is an argument error
+ *   sphere_posterior z = project_to_norm(z, embedding_norm) afterwards (:118-119)
+ * Outputs as pulse_vae_embed lays them out: x[:, :self_obs_size] -> ain (and cin), z -> ain[:, z_col : z_col + E] (and z_out, for a recorder);
+ * columns [self_obs_size, z_col) and past z_col + E are not written.  embedding_size <= 32. */
+typedef struct pulse_vae_embed_prior_args {
+    const float* pheads; int64_t pheads_stride; /* prior heads: (rows, >= 2E) LEARNED, (rows, >= E) FIXED, NULL allowed with NONE */
+    const float* eps; int64_t eps_stride;       /* N(0,1) noise (rows, E); NULL: z = mu; required with NONE */
+    const float* x; int64_t x_stride;           /* normalised observation; its first self_obs_size columns are copied */
+    float* ain; int64_t ain_stride;             /* decoder input: [self obs | .. | z at column z_col] */
+    float* cin; int64_t cin_stride;             /* optional: critic input, self obs columns only */
+    float* z_out; int64_t z_out_stride;         /* optional: z again, (rows, E) */
+    int32_t rows, embedding_size, self_obs_size, z_col;
+    int32_t prior_mode; float prior_fixed_logvar;
+    int32_t clamp_logvar; float clamp_max;
+    int32_t logvar_override; float logvar_override_value;
+    int32_t sphere_prior, sphere_posterior; float embedding_norm;
+} pulse_vae_embed_prior_args;
+int pulse_vae_embed_prior(const pulse_vae_embed_prior_args* args, pulse_stream_t s);
+int pulse_sizeof_vae_embed_prior_args(void);
 /* HumanoidZ.compute_z_actions under the sphere posterior (humanoid_z.py:101-107): out = project_to_norm(a [+ b], norm); b may be NULL; cols <= 32 */
 int pulse_vae_project(const float* a, int64_t a_stride, const float* b, int64_t b_stride, float* out, int64_t out_stride, int32_t rows, int32_t cols,
                       float norm, pulse_stream_t s);

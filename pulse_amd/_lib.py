@@ -234,6 +234,15 @@ class VaeEmbedArgs(Structure):
                 ("clamp_logvar", c_int32), ("clamp_max", c_float), ("sphere_posterior", c_int32), ("embedding_norm", c_float)]
 
 
+class VaeEmbedPriorArgs(Structure):
+    _fields_ = [("pheads", c_void_p), ("pheads_stride", c_int64), ("eps", c_void_p), ("eps_stride", c_int64), ("x", c_void_p), ("x_stride", c_int64),
+                ("ain", c_void_p), ("ain_stride", c_int64), ("cin", c_void_p), ("cin_stride", c_int64), ("z_out", c_void_p), ("z_out_stride", c_int64),
+                ("rows", c_int32), ("embedding_size", c_int32), ("self_obs_size", c_int32), ("z_col", c_int32),
+                ("prior_mode", c_int32), ("prior_fixed_logvar", c_float), ("clamp_logvar", c_int32), ("clamp_max", c_float),
+                ("logvar_override", c_int32), ("logvar_override_value", c_float),
+                ("sphere_prior", c_int32), ("sphere_posterior", c_int32), ("embedding_norm", c_float)]
+
+
 class VaeKinArgs(Structure):
     _fields_ = [("pred", c_void_p), ("pred_stride", c_int64), ("gt", c_void_p), ("gt_stride", c_int64),
                 ("zheads", c_void_p), ("zheads_stride", c_int64), ("pheads", c_void_p), ("pheads_stride", c_int64), ("progress", c_void_p),
@@ -367,6 +376,8 @@ SIGNATURES = {
     "pulse_sizeof_crowd_heights_args": (c_int, []),
     "pulse_crowd_heights": (c_int, [POINTER(CrowdHeightsArgs), P]),
     "pulse_vae_embed": (c_int, [POINTER(VaeEmbedArgs), P]),
+    "pulse_vae_embed_prior": (c_int, [POINTER(VaeEmbedPriorArgs), P]),
+    "pulse_sizeof_vae_embed_prior_args": (c_int, []),
     "pulse_vae_project": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_float, P]),
     "pulse_vae_kin_loss": (c_int, [POINTER(VaeKinArgs), P]),
     "pulse_vae_head_backward": (c_int, [POINTER(VaeHeadBwdArgs), P]),

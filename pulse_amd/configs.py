@@ -356,3 +356,27 @@ def make_agent(name="cfg2", device="cuda:0", seed=1234, rank=0, rollout=None, re
     cfg.update({"vec_env": vec_env, "device": device, "seed": seed})
     cls = AMPAgent if cfg["_agent_kind"] == "amp" else CommonAgent
     return cls("pulse_amd", cfg), rollout
+
+
+def make_player(name="cfg3_small", device="cuda:0", seed=1234, rank=0, rollout=None, reference="recorded", env_overrides=None, humanoid=None,
+                z_source="posterior", prior_logvar=None, player=None, **overrides):
+    """A player (learning/players.py) on the config ``name``, built as make_agent builds the agent.  ``z_source`` / ``prior_logvar``: where an
+    amp_z policy's latent comes from -- make_player("cfg3_small", z_source="prior").generate(300, record=True) is motion generated from the
+    PULSE prior alone (amp_network_z_builder.py:101-119).  ``player``: further config["player"] keys.  The options are validated against the
+    config's network and env dict before the env or any device buffer is built."""
+    from .learning import players
+    num_envs_override = overrides.pop("num_envs_override", None)
+    cfg, num_envs = agent_config(name, **overrides)
+    if num_envs_override is not None:
+        num_envs = int(num_envs_override)
+    env_over = dict(cfg["_env_overrides"], **(env_overrides or {}))
+    cfg["player"] = dict(player or {}, z_source=z_source, prior_logvar=prior_logvar)
+    env = dict(ENV_IM_VAE if cfg["_env_kind"] in ("vae", "vae_ppo") else {}, **env_over)
+    if "use_vae_fixed_prior" in env:                    # (as the env builds its task_obs_size_detail, env/humanoid_im.py)
+        env.setdefault("use_vae_prior", False)
+    players.check_z_source_options(cfg, detail=env)
+    vec_env, _ = make_env(num_envs, cfg["horizon_length"], device, seed=seed, rank=rank, rollout=rollout, env_kind=cfg["_env_kind"],
+                          reference=reference, env_overrides=env_over or None, humanoid=humanoid if humanoid is not None else cfg["_humanoid"])
+    cfg.update({"vec_env": vec_env, "device": device, "seed": seed})
+    cls = players.AMPPlayerContinuous if cfg["_agent_kind"] == "amp" else players.CommonPlayer
+    return cls(cfg)

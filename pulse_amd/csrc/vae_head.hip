@@ -14,6 +14,7 @@
 //   PRIOR   learned [mu | logvar] heads / fixed: mu heads (E wide) and a constant, unclamped log-variance / none: KL against N(0, I)
 //   SPRIOR  the fixed prior's mean goes through project_to_norm(., embedding_norm) first
 //   SPOST   z is projected after the re-parameterisation; the heads themselves (KL, AR(1), regulariser) stay unprojected
+// A fourth launch, pulse_vae_embed_prior, is the generation step: z drawn from the prior instead of the posterior (:101-119).
 #include "common.h"
 
 namespace pulse {
@@ -88,6 +89,55 @@ __global__ void __launch_bounds__(256) vae_embed_kernel(const pulse_vae_embed_ar
             }
             z = sphere_project(z, a.embedding_norm);
             if (l < E) a.ain[r * a.ain_stride + a.z_col + l] = z;
+        }
+    }
+}
+
+// ---- form_embedding under flags.debug (amp_network_z_builder.py:101-119): z is drawn from the PRIOR, the encoder heads are not read.
+//   kLearned / kFixed  z = prior_mu + eps * exp(0.5 prior_logvar) with (prior_mu, prior_logvar) as compute_prior returns them (:226-248):
+//                      learned heads [mu | logvar], the log-variance clamped; fixed heads = the mean (projected when SPRIOR) and the constant,
+//                      unclamped log-variance.  logvar_override replaces the log-variance by a constant (the commented variants of :110-111);
+//                      eps == NULL: z = prior_mu (:109)
+//   kNone              z = eps (:116)
+// SPOST projects z afterwards (:118-119).  Half-wave per row whatever the mode; the self-observation columns are copied element-wise.
+template <int PRIOR, bool SPRIOR, bool SPOST>
+__global__ void __launch_bounds__(256) vae_embed_prior_kernel(const pulse_vae_embed_prior_args a) {
+    const int E = a.embedding_size, S = a.self_obs_size;
+    const long long total = (long long)a.rows * S;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / S;
+        const int c = (int)(i - r * S);
+        const float v = a.x[r * a.x_stride + c];
+        a.ain[r * a.ain_stride + c] = v;
+        if (a.cin) a.cin[r * a.cin_stride + c] = v;
+    }
+    const int slot = threadIdx.x / kVL, l = threadIdx.x % kVL;
+    for (long long base = (long long)blockIdx.x * 8; base < a.rows; base += (long long)gridDim.x * 8) {
+        const long long r = base + slot;
+        if (r >= a.rows) continue;
+        const bool on = l < E;
+        float z = 0.f;
+        if (PRIOR == kNone) {
+            if (on) z = a.eps[r * a.eps_stride + l];
+        } else {
+            float mu = on ? a.pheads[r * a.pheads_stride + l] : 0.f;
+            if (SPRIOR) mu = sphere_project(mu, a.embedding_norm);
+            z = mu;
+            if (on && a.eps) {
+                float lv;
+                if (a.logvar_override) lv = a.logvar_override_value;
+                else if (PRIOR == kFixed) lv = a.prior_fixed_logvar;
+                else {
+                    lv = a.pheads[r * a.pheads_stride + E + l];
+                    if (a.clamp_logvar) lv = vclamp(lv, -5.0f, a.clamp_max);
+                }
+                z = mu + a.eps[r * a.eps_stride + l] * expf(0.5f * lv);
+            }
+        }
+        if (SPOST) z = sphere_project(z, a.embedding_norm);
+        if (on) {
+            a.ain[r * a.ain_stride + a.z_col + l] = z;
+            if (a.z_out) a.z_out[r * a.z_out_stride + l] = z;
         }
     }
 }
@@ -292,7 +342,45 @@ static void launch_head_backward(const pulse_vae_head_bwd_args& a, dim3 grid, pu
     else hipLaunchKernelGGL((vae_head_backward_kernel<PRIOR, SPRIOR, false>), grid, dim3(256), 0, as_stream(s), a);
 }
 
+template <int PRIOR, bool SPRIOR>
+static void launch_embed_prior(const pulse_vae_embed_prior_args& a, dim3 grid, pulse_stream_t s) {
+    if (a.sphere_posterior) hipLaunchKernelGGL((vae_embed_prior_kernel<PRIOR, SPRIOR, true>), grid, dim3(256), 0, as_stream(s), a);
+    else hipLaunchKernelGGL((vae_embed_prior_kernel<PRIOR, SPRIOR, false>), grid, dim3(256), 0, as_stream(s), a);
+}
+
 extern "C" {
+
+int pulse_sizeof_vae_embed_prior_args(void) { return (int)sizeof(pulse_vae_embed_prior_args); }
+
+int pulse_vae_embed_prior(const pulse_vae_embed_prior_args* args, pulse_stream_t s) {
+    PULSE_REQUIRE(args != nullptr, "pulse_vae_embed_prior: null args");
+    const pulse_vae_embed_prior_args& a = *args;
+    if (a.rows == 0) return PULSE_OK;
+    PULSE_REQUIRE(a.rows > 0 && a.embedding_size >= 1 && a.embedding_size <= kVL && a.self_obs_size >= 0,
+                  "pulse_vae_embed_prior: bad sizes (embedding_size <= 32)");
+    PULSE_REQUIRE(a.prior_mode == kLearned || a.prior_mode == kFixed || a.prior_mode == kNone, "pulse_vae_embed_prior: unknown prior_mode");
+    PULSE_REQUIRE(a.x && a.ain, "pulse_vae_embed_prior: null pointer");
+    PULSE_REQUIRE(a.x_stride >= a.self_obs_size && a.ain_stride >= (int64_t)a.z_col + a.embedding_size && a.z_col >= a.self_obs_size,
+                  "pulse_vae_embed_prior: strides / column offsets do not cover the rows");
+    PULSE_REQUIRE(a.prior_mode == kNone || a.pheads, "pulse_vae_embed_prior: a learned / fixed prior needs the prior heads");
+    PULSE_REQUIRE(a.prior_mode == kNone || a.pheads_stride >= prior_width(a.prior_mode, a.embedding_size),
+                  "pulse_vae_embed_prior: pheads_stride too small (2E learned, E fixed)");
+    PULSE_REQUIRE(a.prior_mode != kNone || a.eps, "pulse_vae_embed_prior: without a prior z is the noise itself: eps must be given");
+    PULSE_REQUIRE(!a.eps || a.eps_stride >= a.embedding_size, "pulse_vae_embed_prior: eps_stride too small");
+    PULSE_REQUIRE(!a.cin || a.cin_stride >= a.self_obs_size, "pulse_vae_embed_prior: cin_stride too small");
+    PULSE_REQUIRE(!a.z_out || a.z_out_stride >= a.embedding_size, "pulse_vae_embed_prior: z_out_stride too small");
+    const bool sprior = a.prior_mode == kFixed && a.sphere_prior;       // acts under the fixed prior only (amp_network_z_builder.py:237-239)
+    PULSE_REQUIRE(!(sprior || a.sphere_posterior) || a.embedding_norm > 0.f, "pulse_vae_embed_prior: the sphere projections need embedding_norm > 0");
+    long long blocks = ((long long)a.rows * a.self_obs_size + 255) / 256, row_blocks = ((long long)a.rows + 7) / 8;
+    if (blocks < row_blocks) blocks = row_blocks;
+    if (blocks > 4096) blocks = 4096;
+    const dim3 grid((unsigned)blocks);
+    if (a.prior_mode == kLearned) launch_embed_prior<kLearned, false>(a, grid, s);
+    else if (a.prior_mode == kNone) launch_embed_prior<kNone, false>(a, grid, s);
+    else if (sprior) launch_embed_prior<kFixed, true>(a, grid, s);
+    else launch_embed_prior<kFixed, false>(a, grid, s);
+    return check_launch("pulse_vae_embed_prior");
+}
 
 int pulse_sizeof_vae_embed_args(void) { return (int)sizeof(pulse_vae_embed_args); }
 int pulse_sizeof_vae_kin_args(void) { return (int)sizeof(pulse_vae_kin_args); }

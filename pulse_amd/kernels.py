@@ -322,6 +322,27 @@ def vae_embed_modes(heads, x, ain, *, rows, embedding_size, self_obs_size, z_col
     _launch("pulse_vae_embed", ctypes.byref(a))
 
 
+def vae_embed_prior(pheads, x, ain, *, rows, embedding_size, self_obs_size, z_col, eps=None, cin=None, z_out=None, prior_mode=PRIOR_LEARNED,
+                    prior_fixed_logvar=0.0, clamp=True, clamp_max=2.0, logvar_override=None, sphere_prior=False, sphere_posterior=False,
+                    embedding_norm=1.0):
+    """The generation step (form_embedding under flags.debug, amp_network_z_builder.py:101-119): z drawn from the prior into ``ain`` beside
+    the self observation, as vae_embed lays it out.  ``pheads`` as vae_kin_loss_modes takes them (None with PRIOR_NONE, where z = eps);
+    ``eps`` None: z = the prior mean; ``logvar_override``: a constant log-variance instead of the prior's; ``z_out``: (rows, E), z again."""
+    a = _lib.VaeEmbedPriorArgs()
+    a.pheads, a.pheads_stride = _p(pheads, "pheads"), (pheads.stride(0) if pheads is not None else 0)
+    a.eps, a.eps_stride = _p(eps, "eps"), (eps.stride(0) if eps is not None else 0)
+    a.x, a.x_stride = _p(x, "x"), x.stride(0)
+    a.ain, a.ain_stride = _p(ain, "ain"), ain.stride(0)
+    a.cin, a.cin_stride = _p(cin, "cin"), (cin.stride(0) if cin is not None else 0)
+    a.z_out, a.z_out_stride = _p(z_out, "z_out"), (z_out.stride(0) if z_out is not None else 0)
+    a.rows, a.embedding_size, a.self_obs_size, a.z_col = rows, embedding_size, self_obs_size, z_col
+    a.prior_mode, a.prior_fixed_logvar = int(prior_mode), float(prior_fixed_logvar)
+    a.clamp_logvar, a.clamp_max = int(bool(clamp)), float(clamp_max)
+    a.logvar_override, a.logvar_override_value = int(logvar_override is not None), float(logvar_override or 0.0)
+    a.sphere_prior, a.sphere_posterior, a.embedding_norm = int(bool(sphere_prior)), int(bool(sphere_posterior)), float(embedding_norm)
+    _launch("pulse_vae_embed_prior", ctypes.byref(a))
+
+
 def vae_project(a, out, *, rows, cols, norm, b=None):
     """out = project_to_norm(a [+ b], norm) row by row (phc/utils/torch_utils.py:38-43); cols <= 32."""
     _launch("pulse_vae_project", _p(a, "a"), a.stride(0), _p(b, "b"), (b.stride(0) if b is not None else 0), _p(out, "out"), out.stride(0),

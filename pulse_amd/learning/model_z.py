@@ -7,13 +7,16 @@ cat(self_obs, z) -> decoder plan -> mu.  The (B,32) head algebra is two fused la
 pulse_vae_embed on the way forward, pulse_vae_head_backward (d z / d mu, d z / d logvar with the clamp mask, plus the KL / AR(1) /
 regulariser terms of _optimize_kin) when the decoder's input gradient comes back from the GEMM plans.  No autograd tape.  The network's
 prior mode (learned / fixed / none) and its two sphere switches travel to the launches as compile-time-folded modes (net.head_modes()).
+
+Generation (form_embedding under flags.debug, :101-119): with ``z_source`` 'prior' / 'prior_mean' / 'normal' the latent comes from the prior
+(pulse_vae_embed_prior) and the encoder plan is not launched: prior plan -> one head launch -> decoder plan.  Inference only.
 """
 import torch
 
 from .. import kernels as K
 
 from .graph import GraphModel
-from .network_z import AMPZNetwork
+from .network_z import AMPZNetwork, check_z_source
 
 
 class AMPZModel(GraphModel):
@@ -23,10 +26,62 @@ class AMPZModel(GraphModel):
         super().__init__(params, **kw)
         self.embedding_size = self.net.embedding_size
         self.generator = generator
+        self._z_source, self._prior_logvar = "posterior", None
+
+    # ---- where z comes from: the encoder's posterior (training, tracking) or the prior (generation; inference only)
+    @property
+    def z_source(self):
+        return self._z_source
+
+    @z_source.setter
+    def z_source(self, value):
+        self.set_z_source(value, self._prior_logvar)
+
+    @property
+    def prior_logvar(self):
+        return self._prior_logvar
+
+    @prior_logvar.setter
+    def prior_logvar(self, value):
+        self.set_z_source(self._z_source, value)
+
+    def set_z_source(self, z_source, prior_logvar=None):
+        """Both switches at once, validated against the network's prior (network_z.check_z_source) before either changes."""
+        check_z_source(z_source, prior_logvar, self.net.prior_mode)
+        self._z_source, self._prior_logvar = z_source, None if prior_logvar is None else float(prior_logvar)
 
     def _fill_workspace(self, ws, m):
         super()._fill_workspace(ws, m)
         ws["z_noise"] = None                                        # (a test's injected re-parameterisation noise, _embed)
+        zc = self.net.z_col
+        ws["z"] = ws["g"].act_bufs["ain"][:, zc:zc + self.net.embedding_size]     # the z the decoder read, whatever its source
+        ws["z_record"] = None                                       # (a recorder's (m, E) rows: the prior launch writes z there as well)
+
+    def _noise(self, ws, m):
+        """ws['z_noise'] when a test injected it, a fresh draw from self.generator otherwise."""
+        if ws["z_noise"] is not None:
+            return ws["z_noise"]
+        eps = ws.get("_eps_buf")
+        if eps is None:
+            eps = ws["_eps_buf"] = torch.empty(m, self.net.embedding_size, device=self.device)
+        eps.normal_(generator=self.generator)
+        return eps
+
+    def _embed_prior(self, ws):
+        """form_embedding under flags.debug (amp_network_z_builder.py:101-119): the prior plan (when there is a prior), then one launch that
+        draws z from it and places z and the self observation in the decoder's (and the critic's) concat buffer.  No encoder plan."""
+        net, g = self.net, ws["g"]
+        m = ws["x"].shape[0]
+        pheads = None
+        if net.prior_mode != K.PRIOR_NONE:
+            ws["G"]["fwd_prior"].run()
+            pheads = g.act_bufs["pheads"]
+        eps = None if self._z_source == "prior_mean" else self._noise(ws, m)
+        K.vae_embed_prior(pheads, ws["x"], g.act_bufs["ain"], rows=m, embedding_size=net.embedding_size, self_obs_size=net.self_obs_size,
+                          z_col=net.z_col, eps=eps, cin=g.act_bufs["cin"], z_out=ws["z_record"], clamp=net.use_vae_clamped_prior,
+                          clamp_max=net.vae_var_clamp_max, logvar_override=self._prior_logvar, sphere_posterior=net.use_vae_sphere_posterior,
+                          **net.head_modes())
+        ws["eps"] = eps
 
     def _embed(self, ws):
         """form_embedding (amp_network_z_builder.py:79-121) on the encoder heads in one launch: clamp, re-parameterise, and place z and the
@@ -36,23 +91,18 @@ class AMPZModel(GraphModel):
         E, S = net.embedding_size, net.self_obs_size
         heads = g.act_bufs["zheads"]
         m = heads.shape[0]
-        if getattr(self, "deterministic_z", False):
-            eps = None
-        elif ws["z_noise"] is not None:
-            eps = ws["z_noise"]
-        else:
-            eps = ws.get("_eps_buf")
-            if eps is None:
-                eps = ws["_eps_buf"] = torch.empty(m, E, device=self.device)
-            eps.normal_(generator=self.generator)
+        eps = None if getattr(self, "deterministic_z", False) else self._noise(ws, m)
         K.vae_embed_modes(heads, ws["x"], g.act_bufs["ain"], rows=m, embedding_size=E, self_obs_size=S, z_col=net.z_col, eps=eps, cin=g.act_bufs["cin"],
                           clamp=net.use_vae_clamped_prior, clamp_max=net.vae_var_clamp_max, sphere_posterior=net.use_vae_sphere_posterior,
                           embedding_norm=net.embedding_norm)
         ws["eps"] = eps
 
     def forward_actor(self, ws, m, need_grad=None):
-        ws["G"]["fwd_enc"].run()
-        self._embed(ws)
+        if self._z_source == "posterior":
+            ws["G"]["fwd_enc"].run()
+            self._embed(ws)
+        else:                                                        # generation: the encoder plan is not launched
+            self._embed_prior(ws)
         ws["G"]["fwd_dec"].run()
 
     def eval_critic(self, ws, m):
@@ -77,6 +127,9 @@ class AMPZModel(GraphModel):
         """d loss/d mu is already in ws['dmu'].  Back-propagates decoder -> z -> encoder.  ``kin``: the head-level terms of _optimize_kin
         (dict c_kl, c_ar1, c_regu, progress, horizon) whose gradients join the re-parameterisation path at the encoder / prior heads; one
         launch of pulse_vae_head_backward either way."""
+        if self._z_source != "posterior":
+            raise RuntimeError(f"backward_actor with z_source {self._z_source!r}: a latent drawn from the prior is inference only (there is no "
+                               "re-parameterisation path through the encoder to differentiate); set z_source = 'posterior' to train")
         g, net = ws["g"], self.net
         E, zc = net.embedding_size, net.z_col
         ws["G"]["bwd_dec"].run()

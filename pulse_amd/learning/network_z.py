@@ -29,6 +29,35 @@ from .._lib import ACT_NONE
 from .graph import GraphNetwork, Linear, _concat_plans, r4
 
 
+Z_SOURCES = ("posterior", "prior", "prior_mean", "normal")
+
+
+def prior_mode_of(detail):
+    """The prior an env's task_obs_size_detail asks for: learned wins when both switches are on (``if use_vae_prior / elif
+    use_vae_fixed_prior``, amp_network_z_builder.py:232-241, 514-533); use_vae_prior defaults to on."""
+    return K.PRIOR_LEARNED if bool(detail.get("use_vae_prior", True)) else K.PRIOR_FIXED if bool(detail.get("use_vae_fixed_prior", False)) else K.PRIOR_NONE
+
+
+def check_z_source(z_source, prior_logvar, prior_mode):
+    """Where the policy's latent comes from (form_embedding, amp_network_z_builder.py:79-121): 'posterior' = the encoder (training, tracking);
+    under flags.debug (:101-116) 'prior' = reparameterize(prior_mu, prior_logvar), 'prior_mean' = prior_mu (:109), 'normal' = randn_like, the
+    branch of a network WITHOUT a prior (:116).  ``prior_logvar``: None or the constant log-variance of :110-111.  Needs no device."""
+    if z_source not in Z_SOURCES:
+        raise ValueError(f"z_source {z_source!r}: one of {', '.join(Z_SOURCES)}")
+    if prior_logvar is not None and (isinstance(prior_logvar, bool) or not isinstance(prior_logvar, (int, float)) or prior_logvar != prior_logvar):
+        raise ValueError(f"prior_logvar {prior_logvar!r}: None or a float (the constant log-variance, amp_network_z_builder.py:110-111)")
+    if prior_logvar is not None and z_source != "prior":
+        raise ValueError(f"prior_logvar with z_source {z_source!r}: the constant log-variance replaces the prior's, which only 'prior' reads")
+    if prior_mode is None:                                      # (the network is not known yet: the options alone)
+        return
+    if z_source in ("prior", "prior_mean") and prior_mode == K.PRIOR_NONE:
+        raise ValueError(f"z_source {z_source!r} needs a prior: the network has neither use_vae_prior nor use_vae_fixed_prior "
+                         "(z_source 'normal' is the reference's branch there, amp_network_z_builder.py:116)")
+    if z_source == "normal" and prior_mode != K.PRIOR_NONE:
+        raise ValueError("z_source 'normal' is the reference's branch for a network without a prior (amp_network_z_builder.py:115-116); with "
+                         "use_vae_prior / use_vae_fixed_prior on it cannot be reached: use 'prior'")
+
+
 class AMPZNetwork(GraphNetwork):
     def __init__(self, params, *, actions_num, self_obs_size, task_obs_size, task_obs_size_detail, device="cuda:0", split_k=8):
         d = task_obs_size_detail
@@ -47,7 +76,7 @@ class AMPZNetwork(GraphNetwork):
         # N(0, I)); both places of the reference use ``if use_vae_prior / elif use_vae_fixed_prior`` (:232-241, 514-533): learned wins
         self.use_vae_prior = bool(d.get("use_vae_prior", True))
         self.use_vae_fixed_prior = bool(d.get("use_vae_fixed_prior", False))
-        self.prior_mode = K.PRIOR_LEARNED if self.use_vae_prior else K.PRIOR_FIXED if self.use_vae_fixed_prior else K.PRIOR_NONE
+        self.prior_mode = prior_mode_of(d)
         self.vae_prior_fixed_logvar = float(d.get("vae_prior_fixed_logvar", 0))
         # use_vae_sphere_prior acts inside the fixed-prior branch only (:237-239); with a learned prior or none it has no effect
         self.use_vae_sphere_prior = bool(d.get("use_vae_sphere_prior", False))

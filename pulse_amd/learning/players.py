@@ -11,14 +11,38 @@ from .common_agent import CommonAgent
 from .amp_agent import AMPAgent
 
 
+def check_z_source_options(config, detail=None):
+    """config['player']['z_source'] / ['prior_logvar'] -> (z_source, prior_logvar), validated without a device.  ``detail``: the env's
+    task_obs_size_detail (the prior switches); default: read off config['vec_env'] when the env is already there, otherwise only what needs no
+    env is checked here and the model's own setter checks the rest once it exists."""
+    from .network_z import check_z_source, prior_mode_of
+    p = config.get("player", {}) or {}
+    z_source, prior_logvar = p.get("z_source", "posterior"), p.get("prior_logvar", None)
+    check_z_source(z_source, prior_logvar, None)
+    if z_source == "posterior":
+        return z_source, prior_logvar
+    name = config["network"].get("name", "amp")
+    if name != "amp_z":
+        raise ValueError(f"player z_source {z_source!r} on network {name!r}: only amp_z has a latent with a prior to draw from "
+                         "(amp_network_z_builder.py:101-116)")
+    if detail is None and "vec_env" in config:
+        detail = config["vec_env"].env.task.get_task_obs_size_detail()
+    if detail is not None:
+        check_z_source(z_source, prior_logvar, prior_mode_of(detail))
+    return z_source, prior_logvar
+
+
 class CommonPlayer:
     AGENT = CommonAgent
 
     def __init__(self, config):
         self.config = config
+        self.z_source, self.prior_logvar = check_z_source_options(config)      # before any device work
         # a player is an agent that never trains: construction builds the networks, normalisers and env plumbing once
         self._agent = self.AGENT("player", config)
         a = self._agent
+        if self.z_source != "posterior":
+            a.model.set_z_source(self.z_source, self.prior_logvar)
         self.env, self.device = a.vec_env, a.ppo_device
         self.model, self.running_mean_std = a.model, a.running_mean_std
         self.actions_num, self.clip_actions = a.actions_num, a.clip_actions
@@ -67,6 +91,40 @@ class CommonPlayer:
             if games >= self.games_num:
                 break
         return {"games": games, "av_reward": sum_rewards / max(1, games)}
+
+    def generate(self, n_steps, record=False):
+        """The run loop as a motion generator: ``n_steps`` steps of every env, finished envs reset as in ``run``.  With z_source 'prior' (&c)
+        the humanoid moves from the prior's samples alone.  -> {'steps', 'resets'}; ``record``: also 'rb' (T, N, J, 13), the simulator's
+        rigid-body state after each step, and -- for a network with a latent -- 'z' (T, N, E), the latent of each step; both stay on the device."""
+        env, n, T = self.env, self.env.num_envs, int(n_steps)
+        obs = env.reset()
+        has_z = record and hasattr(self.model, "z_source")          # amp_z: the policy has a latent to record
+        ws = self.model.workspace(n, train=False) if has_z else None
+        out = {}
+        if record:
+            out["rb"] = torch.empty((T,) + tuple(env.task.sim.rigid_body_state.shape), device=self.device)
+            if has_z:
+                out["z"] = torch.empty(T, n, ws["z"].shape[1], device=self.device)
+        resets = torch.zeros((), dtype=torch.int64, device=self.device)
+        try:
+            for t in range(T):
+                if has_z:
+                    ws["z_record"] = out["z"][t]                    # the prior launch writes the step's z there itself
+                action = self.get_action(obs, self.is_determenistic)
+                if has_z and self.model.z_source == "posterior":    # (the posterior launch has no recorder output)
+                    out["z"][t].copy_(ws["z"])
+                obs, _, done, info = env.step(action)
+                self._post_step(info)
+                if record:
+                    out["rb"][t].copy_(env.task.sim.rigid_body_state)
+                d = done > 0
+                resets += d.sum()
+                obs = env.reset_masked(d)                           # (a mask, no read-back: one host sync at the end of the loop)
+        finally:
+            if has_z:
+                ws["z_record"] = None
+        out.update(steps=T, resets=int(resets))
+        return out
 
 
 class AMPPlayerContinuous(CommonPlayer):
