@@ -16,6 +16,7 @@
 // HBM/launch bound: 52 B root record + 2 x 276 B dofs + 48 B key bodies read, 4 W bytes written per env.
 // Compiled with -ffp-contract=off (reference operation order).
 #include "common.h"
+#include "env_select.h"
 #include "rot_math.h"
 #include "motion_math.h"
 
@@ -41,11 +42,6 @@ __host__ __device__ inline AmpLayout amp_layout(int Jd, int Kb, int root_height_
     return L;
 }
 
-// remove_base_rot (humanoid.py:1617-1620): quat_mul(q, conj(0.5, 0.5, 0.5, 0.5)), the expression of the fused env step
-__device__ __forceinline__ Q4 amp_root_rot(Q4 q, int upright_start) {
-    return upright_start ? q : qmul(q, Q4{-0.5f, -0.5f, -0.5f, 0.5f});
-}
-
 // the shape / limb rows behind everything else (copied, never computed)
 __device__ __forceinline__ void amp_copy_rows(float* o, const AmpLayout& L, int lane, const float* shape, int num_shape, const float* limb, int num_limb) {
     for (int c = lane; c < num_shape; c += kAmpLanes) o[L.off_shape + c] = shape[c];
@@ -67,14 +63,8 @@ __global__ void __launch_bounds__(kAmpEnvs * kAmpLanes) amp_obs_kernel(const pul
     __shared__ __align__(16) float s_out[kAmpEnvs][kAmpMaxW];
     __shared__ __align__(16) float s_hist[HIST ? kAmpEnvs : 1][HIST ? kAmpMaxHist * kAmpMaxW : 1];
     const int slot = threadIdx.x / kAmpLanes, lane = threadIdx.x % kAmpLanes;
-    const int idx = blockIdx.x * kAmpEnvs + slot;
-    const int count = a.env_ids ? a.num_ids : a.num_envs;
-    bool valid = idx < count;
-    long long e = 0;
-    if (valid) {
-        e = a.env_ids ? a.env_ids[idx] : (long long)idx;
-        if (a.env_mask && a.env_mask[e] == 0) valid = false;
-    }
+    int64_t e = 0;
+    const bool valid = select_env(a, blockIdx.x * kAmpEnvs + slot, e);      // (carried past the barrier: nobody returns early)
     const int Jd = a.num_joints, Kb = a.num_key_bodies;
     const AmpLayout L = amp_layout(Jd, Kb, a.root_height_obs, version, num_shape, num_limb);   // counts are 0 without a pointer (launcher)
     const int h0 = L.h0, off_vel = L.off_vel, off_ang = L.off_ang, off_dof = L.off_dof, off_dvel = L.off_dvel, off_key = L.off_key, W = L.W;
@@ -94,7 +84,7 @@ __global__ void __launch_bounds__(kAmpEnvs * kAmpLanes) amp_obs_kernel(const pul
     if (valid) {
         const float* rb = a.rb + e * a.rb_env_stride;
         const V3 root_p{rb[0], rb[1], rb[2]};
-        const Q4 root_q = amp_root_rot(Q4{rb[3], rb[4], rb[5], rb[6]}, upright_start);
+        const Q4 root_q = remove_base_rot(Q4{rb[3], rb[4], rb[5], rb[6]}, upright_start);
         const Q4 hinv = heading_quat(root_q, true);
         if (lane == 0) {
             if (a.root_height_obs) o[0] = root_p.z;
@@ -173,7 +163,7 @@ __global__ void __launch_bounds__(kAmpEnvs * kAmpLanes) amp_hist_init_kernel(con
     bool valid = idx < (long long)a.num_envs * Hs;
     const long long e = valid ? idx / Hs : 0;
     const int k = valid ? (int)(idx - e * Hs) : 0;
-    if (valid && a.env_mask && a.env_mask[e] == 0) valid = false;
+    valid = valid && env_enabled(a, e);
     const int Jd = a.num_joints, Kb = a.num_key_bodies;
     const AmpLayout L = amp_layout(Jd, Kb, a.root_height_obs, a.version, a.num_shape, a.num_limb);   // counts are 0 without a pointer (launcher)
     const int h0 = L.h0, off_vel = L.off_vel, off_ang = L.off_ang, off_dof = L.off_dof, off_dvel = L.off_dvel, off_key = L.off_key, W = L.W;
@@ -184,7 +174,7 @@ __global__ void __launch_bounds__(kAmpEnvs * kAmpLanes) amp_hist_init_kernel(con
         const float t = a.start_times[e] + (float)(k + 1) * (-a.dt);
         const FramePair fp = frame_pair(T, a.motion_ids[e], t);
         BodyState root = blend_body(T, fp.r0, fp.r1, fp.blend, 0, nullptr);
-        root.q = amp_root_rot(root.q, a.upright_start);
+        root.q = remove_base_rot(root.q, a.upright_start);
         const Q4 hinv = heading_quat(root.q, true);
         if (lane == 0) {
             if (a.root_height_obs) o[0] = root.p.z;
@@ -256,7 +246,7 @@ int pulse_amp_obs_width_v(int num_joints, int num_key_bodies, int root_height_ob
 int pulse_amp_obs(const pulse_amp_obs_args* args, pulse_stream_t s) {
     PULSE_REQUIRE(args != nullptr, "pulse_amp_obs: null args");
     const pulse_amp_obs_args& a = *args;
-    const int count = a.env_ids ? a.num_ids : a.num_envs;
+    const int count = env_count(a);
     PULSE_REQUIRE(count >= 0, "pulse_amp_obs: negative count");
     if (count == 0) return PULSE_OK;
     PULSE_REQUIRE(a.rb && a.dof_pos && a.dof_vel && a.out && a.key_body_ids, "pulse_amp_obs: null pointer");

@@ -173,8 +173,7 @@ __global__ void __launch_bounds__(256) disc_penalty_kernel(const float* __restri
         if (out32) *reinterpret_cast<float4*>(out32 + (long long)r * ld32 + c) = make_float4(a, b, cc, d);
         if (out16) *reinterpret_cast<uint2*>(out16 + (long long)r * ld16 + c) = make_uint2(split_pack_rn(a, b), split_pack_rn(cc, d));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = lane_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -214,8 +213,7 @@ __global__ void __launch_bounds__(256) disc_reg_kernel(const float* __restrict__
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc[r] += __shfl_xor(acc[r], o, 64);
+        acc[r] = lane_sum(acc[r]);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][r] = acc[r];
     }
     __syncthreads();
@@ -314,9 +312,7 @@ __global__ void __launch_bounds__(256) reduce_grads_kernel(const float* __restri
     float vals[9] = {sq, w2[0], w2[1], w2[2], w2[3], w2[4], w2[5], w2[6], w2[7]};
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
-        float v = vals[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        const float v = lane_sum(vals[k]);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
     }
     __syncthreads();

@@ -42,6 +42,21 @@ hipError_t launch_dyn_lds(dim3 grid, dim3 block, size_t lds, hipStream_t stream,
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+// Lane-group reductions: the xor butterfly over W adjacent lanes (offsets W/2 .. 1); every lane of the group ends with the result.  The one
+// definition of the summation order that the bit-exact tests pin.
+template <int W = kWave, typename T>
+__device__ __forceinline__ T lane_sum(T v) {
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, W);
+    return v;
+}
+template <int W = kWave>
+__device__ __forceinline__ int lane_or(int v) {
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) v |= __shfl_xor(v, o, W);
+    return v;
+}
+
 // ---- the exact three-way bf16 split of fp32 values (gemm_x3 / gemm_x3p arithmetic): x = p0 + p1 + p2, p0 = bf16(x), p1 = bf16(x - p0),
 // p2 = bf16(x - p0 - p1), round to nearest even, the remainders exact.  Pairs of elements, packed {hi, lo} per dword.
 typedef float pulse_f32x2 __attribute__((ext_vector_type(2)));

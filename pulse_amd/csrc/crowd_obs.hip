@@ -12,37 +12,21 @@
 // a wave arg-min (cross-lane shuffles, no LDS) pick the six nearest in order; the 165 output floats are then written as a coalesced row.
 // The stamp is one thread per (person, root point) with an atomicMax into a per-group int32 OWNER grid (0 = empty, else env index + 1):
 // the height field is never replicated per group, and the cells a stamp touched are listed so the next stamp clears exactly those.
-// The height block is one 256-thread workgroup per env, as in traj_step.hip, reading the shared int16 field plus the group's owner grid.
+// The height block is one 256-thread workgroup per env, as in traj_step.hip, reading the shared int16 field plus the group's owner grid;
+// cell lookup and centre height are terrain_math.h's, the ones traj_step.hip uses.
 // -ffp-contract=off: the expressions follow the reference's operation order.
 #include "common.h"
-#include "rot_math.h"
+#include "env_select.h"
+#include "terrain_math.h"
 
 namespace pulse {
-
-// isaacgym.torch_utils.quat_apply (3P): b + w t + xyz x t, t = 2 xyz x b
-__device__ __forceinline__ V3 crowd_q_apply(const Q4 a, const V3 b) {
-    const V3 t{(a.y * b.z - a.z * b.y) * 2.0f, (a.z * b.x - a.x * b.z) * 2.0f, (a.x * b.y - a.y * b.x) * 2.0f};
-    return V3{b.x + a.w * t.x + (a.y * t.z - a.z * t.y), b.y + a.w * t.y + (a.z * t.x - a.x * t.z), b.z + a.w * t.z + (a.x * t.y - a.y * t.x)};
-}
-
-// world_points_to_map: (p / horizontal_scale).long() truncates toward zero, then clip to [0, size - 2]
-__device__ __forceinline__ void crowd_cell(float wx, float wy, float hscale, int rows, int cols, int& px, int& py) {
-    long long x = (long long)(wx / hscale), y = (long long)(wy / hscale);
-    x = x < 0 ? 0 : (x > rows - 2 ? rows - 2 : x);
-    y = y < 0 ? 0 : (y > cols - 2 ? cols - 2 : y);
-    px = (int)x; py = (int)y;
-}
 
 __device__ const int kCrowdJoints[PULSE_CROWD_JOINTS] = {0, 1, 5, 9, 3, 7, 16, 21, 18, 23};
 
 // ---- compute_group_observation: one wave per env, four envs per workgroup ---------------------------------------------------------------
 __global__ void __launch_bounds__(256) crowd_group_obs_kernel(const pulse_crowd_group_obs_args a) {
-    const int count = a.env_ids ? a.num_ids : a.num_envs;
-    const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (idx >= count) return;                                                            // (whole waves leave: no barrier below)
-    const int64_t e = a.env_ids ? a.env_ids[idx] : (int64_t)idx;
-    if (e < 0 || e >= a.num_envs) return;
-    if (a.env_mask && a.env_mask[e] == 0) return;
+    int64_t e;
+    if (!select_env(a, blockIdx.x * 4 + (threadIdx.x >> 6), e)) return;                  // (whole waves leave: no barrier below)
     const int lane = threadIdx.x & 63;
     const int G = a.group_size;
     const int64_t g0 = (e / G) * G;                                                      // first env of the group: neighbours never leave [g0, g0 + G)
@@ -72,9 +56,7 @@ __global__ void __launch_bounds__(256) crowd_group_obs_kernel(const pulse_crowd_
         if (r >= 1 && lane == r - 1) { sel_d = best_d; sel_m = best_m; }
     }
 
-    Q4 root_q{rb[3], rb[4], rb[5], rb[6]};
-    if (!a.upright_start) root_q = qmul(root_q, Q4{-0.5f, -0.5f, -0.5f, 0.5f});          // remove_base_rot
-    const Q4 hinv = heading_quat(root_q, true);
+    const Q4 hinv = heading_quat(remove_base_rot(Q4{rb[3], rb[4], rb[5], rb[6]}, a.upright_start), true);
     float* out = a.obs + e * a.obs_stride + a.obs_offset;
     for (int o = lane; o < PULSE_CROWD_GROUP_OBS; o += 64) {
         const bool is_vel = o >= PULSE_CROWD_TOPK * PULSE_CROWD_JOINTS * 3;
@@ -118,10 +100,10 @@ __global__ void __launch_bounds__(256) crowd_stamp_kernel(const pulse_crowd_stam
     const float ly = iy == 19 ? 0.5f : (float)((double)iy * (1.0 / 19.0) + -0.5);
     const float* rb = a.rb + e * a.rb_env_stride;
     const Q4 hq = heading_quat(Q4{rb[3], rb[4], rb[5], rb[6]}, false);                    // the RAW root rotation (get_heights :750)
-    const V3 w = crowd_q_apply(hq, V3{lx, ly, 0.0f});
-    int px, py;
-    crowd_cell(w.x + rb[0], w.y + rb[1], a.horizontal_scale, a.map_rows, a.map_cols, px, py);
-    const int cell = px * a.map_cols + py;
+    const V3 w = q_apply(hq, V3{lx, ly, 0.0f});
+    long long c1, c2;
+    height_cells(HeightField{nullptr, a.map_rows, a.map_cols, a.horizontal_scale, 0.0f}, w.x + rb[0], w.y + rb[1], c1, c2);   // (cells only: no samples read)
+    const int cell = (int)c1;
     const int64_t plane = (int64_t)a.map_rows * a.map_cols;
     atomicMax(a.owner + (e / a.group_size) * plane + cell, (int)e + 1);
     a.cells[t] = cell;
@@ -129,58 +111,30 @@ __global__ void __launch_bounds__(256) crowd_stamp_kernel(const pulse_crowd_stam
 
 // ---- the height block: one workgroup per env -------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) crowd_height_kernel(const pulse_crowd_heights_args a) {
-    __shared__ float s_center;
-    __shared__ float s_cpt[256];
-    const int count = a.env_ids ? a.num_ids : a.num_envs;
-    const int idx = blockIdx.x;
-    if (idx >= count) return;
-    const int64_t e = a.env_ids ? a.env_ids[idx] : (int64_t)idx;
-    if (e < 0 || e >= a.num_envs) return;
-    if (a.env_mask && a.env_mask[e] == 0) return;
+    int64_t e;
+    if (!select_env(a, blockIdx.x, e)) return;                                           // (the whole workgroup leaves)
     const int tid = threadIdx.x;
     const float* rb = a.rb + e * a.rb_env_stride;
     const V3 root_p{rb[0], rb[1], rb[2]};
     const Q4 raw_q{rb[3], rb[4], rb[5], rb[6]};
-    Q4 root_q = raw_q;
-    if (!a.upright_start) root_q = qmul(root_q, Q4{-0.5f, -0.5f, -0.5f, 0.5f});          // remove_base_rot
+    const HeightField hf = height_field_of(a);
     const int64_t plane = (int64_t)a.map_rows * a.map_cols;
     const int32_t* ow = a.owner ? a.owner + (e / a.group_size) * plane : nullptr;
-
-    if (a.use_center_height) {
-        // get_center_heights (:690-716): the plain field, never the stamped one (sample_height_points without root_points)
-        if (tid < a.num_center_points) {
-            const float n = fmaxf(sqrtf(root_q.z * root_q.z + root_q.w * root_q.w), 1e-9f);
-            const Q4 qy{0.0f / n, 0.0f / n, root_q.z / n, root_q.w / n};
-            const V3 w = crowd_q_apply(qy, V3{a.center_points[2 * tid], a.center_points[2 * tid + 1], 0.0f});
-            int px, py;
-            crowd_cell(w.x + root_p.x, w.y + root_p.y, a.horizontal_scale, a.map_rows, a.map_cols, px, py);
-            const short h1 = a.heightsamples[(int64_t)px * a.map_cols + py], h2 = a.heightsamples[(int64_t)(px + 1) * a.map_cols + py + 1];
-            s_cpt[tid] = (float)(h1 < h2 ? h1 : h2) * a.vertical_scale;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            float sum = 0.0f;
-            for (int c = 0; c < a.num_center_points; ++c) sum += s_cpt[c];
-            s_center = sum / (float)a.num_center_points;
-        }
-    }
-    __syncthreads();
+    const float ref = height_reference(hf, a.use_center_height, a.center_points, a.num_center_points, remove_base_rot(raw_q, a.upright_start), root_p);
 
     const float* sb = rb + 13 * a.sensor_body;
-    Q4 sq{sb[3], sb[4], sb[5], sb[6]};
-    if (!a.upright_start) sq = qmul(sq, Q4{-0.5f, -0.5f, -0.5f, 0.5f});
-    const Q4 hq = heading_quat(sq, false);
-    const float ref = a.use_center_height ? s_center : root_p.z;
+    const Q4 hq = heading_quat(remove_base_rot(Q4{sb[3], sb[4], sb[5], sb[6]}, a.upright_start), false);
     // velocities: the env's own root velocity and calc_heading_quat_inv of its RAW root rotation (sample_height_points :1219-1221, 1270-1272)
     const V3 own_v{rb[7], rb[8], rb[9]};
     const Q4 vinv = a.velocity_map ? heading_quat(raw_q, true) : Q4{0.f, 0.f, 0.f, 1.f};
     const int ch = a.velocity_map ? 3 : 1;
     float* ho = a.obs + e * a.obs_stride + a.obs_offset;
+    // One point per thread and pass, with the owner grid read beside the field.  traj_step.hip's loop over the same points takes four per
+    // thread with their gathers batched and knows no owners: two kernels on purpose, one set of cells (height_cells).
     for (int p = tid; p < a.num_height_points; p += 256) {
-        const V3 w = crowd_q_apply(hq, V3{a.height_points[2 * p], a.height_points[2 * p + 1], 0.0f});
-        int px, py;
-        crowd_cell(w.x + sb[0], w.y + sb[1], a.horizontal_scale, a.map_rows, a.map_cols, px, py);
-        const int64_t c1 = (int64_t)px * a.map_cols + py, c2 = (int64_t)(px + 1) * a.map_cols + py + 1;
+        const V3 w = q_apply(hq, V3{a.height_points[2 * p], a.height_points[2 * p + 1], 0.0f});
+        long long c1, c2;
+        height_cells(hf, w.x + sb[0], w.y + sb[1], c1, c2);
         int h1 = a.heightsamples[c1], h2 = a.heightsamples[c2];
         int o1 = 0;
         if (ow) {
@@ -225,7 +179,7 @@ int pulse_crowd_group_obs(const pulse_crowd_group_obs_args* args, pulse_stream_t
     PULSE_REQUIRE(a.group_size >= PULSE_CROWD_TOPK + 1, "pulse_crowd_group_obs: group_size %d < 6 (the reference's topk of 6 distances, "
                   "humanoid_pedestrian_terrain.py:1724)", a.group_size);
     PULSE_REQUIRE(a.num_envs % a.group_size == 0, "pulse_crowd_group_obs: num_envs %d is not a multiple of group_size %d", a.num_envs, a.group_size);
-    const int count = a.env_ids ? a.num_ids : a.num_envs;
+    const int count = env_count(a);
     PULSE_REQUIRE(count >= 0, "pulse_crowd_group_obs: negative num_ids");
     if (count == 0) return PULSE_OK;
     PULSE_REQUIRE(a.rb && a.num_bodies >= 24 && a.rb_env_stride >= 13LL * a.num_bodies,
@@ -261,7 +215,7 @@ int pulse_crowd_heights(const pulse_crowd_heights_args* args, pulse_stream_t s) 
         PULSE_REQUIRE(a.group_size >= 1, "pulse_crowd_heights: group_size %d < 1", a.group_size);
         PULSE_REQUIRE(a.num_envs % a.group_size == 0, "pulse_crowd_heights: num_envs %d is not a multiple of group_size %d", a.num_envs, a.group_size);
     }
-    const int count = a.env_ids ? a.num_ids : a.num_envs;
+    const int count = env_count(a);
     PULSE_REQUIRE(count >= 0, "pulse_crowd_heights: negative num_ids");
     if (count == 0) return PULSE_OK;
     PULSE_REQUIRE(a.rb && a.num_bodies >= 1 && a.rb_env_stride >= 13LL * a.num_bodies, "pulse_crowd_heights: bad rigid-body state");

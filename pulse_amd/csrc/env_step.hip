@@ -14,7 +14,7 @@
 //   * the env's 13-float AoS rigid-body records and both reference frames (t and t+1) are
 //     staged into LDS with coalesced 16-byte loads, then read back at a 13-float lane stride
 //     (odd stride -> conflict-free ds_read_b32);
-//   * per-env reductions (4 reward errors, power, any-body-fell) are LB-lane butterfly shuffles;
+//   * per-env reductions (4 reward errors, power, any-body-fell) are LB-lane butterfly shuffles (lane_sum / lane_or, common.h);
 //   * the 934-float observation row is assembled in LDS and written with full-line 16-byte
 //     stores straight into the caller's row pitch (e.g. a 960-float GEMM-ready pitch, pad zeroed).
 // Compiled with -ffp-contract=off so products/sums round exactly like the eager reference.
@@ -71,19 +71,6 @@ __device__ __forceinline__ int task_off(int v, int blk, int Jt, int T, int t, in
     const int base[8] = {0, 3, 9, 12, -1, -1, -1, -1};
     if (base[blk] < 0 || (v == 3 && blk > 1)) return -1;
     return base[blk] * Jt * T + w * (t * Jt + j);
-}
-
-template <int LB>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int o = LB / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, LB);
-    return v;
-}
-template <int LB>
-__device__ __forceinline__ int group_or(int v) {
-#pragma unroll
-    for (int o = LB / 2; o > 0; o >>= 1) v |= __shfl_xor(v, o, LB);
-    return v;
 }
 
 // cooperative copy of n floats global -> LDS by the nl lanes of one env group (lane = 0 .. nl - 1)
@@ -304,8 +291,7 @@ __global__ void __launch_bounds__(E * R * LB) im_step_kernel(const pulse_im_step
             if (a.pass_time_out) a.pass_time_out[e] = pass_time ? 1 : 0;
         }
         const V3 root_p{rb_e[0], rb_e[1], rb_e[2]};
-        Q4 root_q{rb_e[3], rb_e[4], rb_e[5], rb_e[6]};
-        if (!a.upright_start) root_q = qmul(root_q, Q4{-0.5f, -0.5f, -0.5f, 0.5f});   // remove_base_rot, humanoid.py:1616-1620
+        const Q4 root_q = remove_base_rot(Q4{rb_e[3], rb_e[4], rb_e[5], rb_e[6]}, a.upright_start);
         const Q4 hinv = heading_quat(root_q, true);   // calc_heading_quat_inv
         // calc_heading_quat is its exact conjugate: quat_from_angle_axis(+-h, z^) differ in the sign of sin(h / 2) only (sin is odd in fp32 too,
         // the normalisation is the same) -- one heading evaluation (atan2 + sin + cos + two normalisations) per lane instead of two [r6]
@@ -450,13 +436,13 @@ __global__ void __launch_bounds__(E * R * LB) im_step_kernel(const pulse_im_step
                 dx = x[J * 10 + 3 * b] - r[10]; dy = x[J * 10 + 3 * b + 1] - r[11]; dz = x[J * 10 + 3 * b + 2] - r[12];
                 e_ang = (dx * dx + dy * dy + dz * dz) / 3.0f;
             }
-            e_pos = group_sum<LB>(e_pos); e_rot = group_sum<LB>(e_rot);
-            e_vel = group_sum<LB>(e_vel); e_ang = group_sum<LB>(e_ang);
+            e_pos = lane_sum<LB>(e_pos); e_rot = lane_sum<LB>(e_rot);
+            e_vel = lane_sum<LB>(e_vel); e_ang = lane_sum<LB>(e_ang);
             float pw = 0.f;
             if (a.specs.power_reward) {
                 if (lane < kPowerLanes)
                     for (int d = lane; d < nd; d += kPowerLanes) pw += fabsf(df_e[d] * dv_e[d]);
-                pw = group_sum<LB>(pw);
+                pw = lane_sum<LB>(pw);
             }
             if (lane == 0) {
                 const float fn = (float)nb;
@@ -507,10 +493,10 @@ __global__ void __launch_bounds__(E * R * LB) im_step_kernel(const pulse_im_step
             }
             int fallen;
             if (a.reset_use_mean) {
-                const float m = group_sum<LB>(dist) / (float)a.num_reset;
+                const float m = lane_sum<LB>(dist) / (float)a.num_reset;
                 fallen = m > a.term_dist[a.reset_ids[0]];
             } else {
-                fallen = group_or<LB>(fell);
+                fallen = lane_or<LB>(fell);
             }
             if (lane == 0) {
                 const bool pt = pass_time;

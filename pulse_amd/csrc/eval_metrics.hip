@@ -4,22 +4,16 @@
 // summed per env on the device, in fp64, and only the (N, 8) accumulator rows are read back, once per batch.
 //
 // Same idiom as env_step.hip: one lane group per env, lane = body; LB = 32 lanes up to 32 bodies (4 envs per workgroup), LB = 64 for
-// 33 .. 64 (2 envs per workgroup).  Every per-env reduction is a butterfly shuffle, so all lanes of a group hold every sum (the 3 x 3 SVD
+// 33 .. 64 (2 envs per workgroup).  Every per-env reduction is a butterfly shuffle (lane_sum, common.h), so all lanes of a group hold every sum (the 3 x 3 SVD
 // runs redundantly on all of them) and lanes J .. LB - 1 feed exact zeros.  No atomics, no LDS.
 #include <cstdint>
 #include "common.h"
+#include "env_select.h"
 
 namespace pulse {
 namespace {
 
 constexpr int kEvalThreads = 128;
-
-template <int LB>
-__device__ __forceinline__ double group_sum_f64(double v) {
-#pragma unroll
-    for (int o = LB / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, LB);
-    return v;
-}
 
 __device__ __forceinline__ double norm3(double x, double y, double z) { return sqrt(x * x + y * y + z * z); }
 
@@ -62,8 +56,7 @@ __global__ void __launch_bounds__(kEvalThreads) im_eval_accum_kernel(const pulse
     const int J = a.num_bodies;
     const int lane = threadIdx.x % LB;
     const int e = blockIdx.x * E + threadIdx.x / LB;
-    if (e >= a.num_envs) return;                              // whole groups leave together: the shuffles below stay inside a group
-    if (a.env_mask && !a.env_mask[e]) return;
+    if (!env_enabled(a, e)) return;                           // whole groups leave together: the shuffles below stay inside a group
     const int s = a.step;
     const bool body = lane < J;
 
@@ -97,23 +90,23 @@ __global__ void __launch_bounds__(kEvalThreads) im_eval_accum_kernel(const pulse
 
     const double invJ = 1.0 / (double)J;
     // ---- mpjpe_g, mpjpe_l
-    const double t_g = group_sum_f64<LB>(body ? norm3(P[0] - G[0], P[1] - G[1], P[2] - G[2]) : 0.0) * invJ;
+    const double t_g = lane_sum<LB>(body ? norm3(P[0] - G[0], P[1] - G[1], P[2] - G[2]) : 0.0) * invJ;
     double P0[3], G0[3];                                      // body 0 of the env, from the group's first lane
 #pragma unroll
     for (int k = 0; k < 3; ++k) { P0[k] = __shfl(P[k], 0, LB); G0[k] = __shfl(G[k], 0, LB); }
     double Pt[3], Gt[3];                                      // root-relative
 #pragma unroll
     for (int k = 0; k < 3; ++k) { Pt[k] = body ? P[k] - P0[k] : 0.0; Gt[k] = body ? G[k] - G0[k] : 0.0; }
-    const double t_l = group_sum_f64<LB>(norm3(Pt[0] - Gt[0], Pt[1] - Gt[1], Pt[2] - Gt[2])) * invJ;
+    const double t_l = lane_sum<LB>(norm3(Pt[0] - Gt[0], Pt[1] - Gt[1], Pt[2] - Gt[2])) * invJ;
 
     // ---- mpjpe_pa: the similarity Procrustes fit of the common p_mpjpe, X = target (gt), Y = predicted, both root-relative
     double muX[3], muY[3], X0[3], Y0[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { muX[k] = group_sum_f64<LB>(Gt[k]) * invJ; muY[k] = group_sum_f64<LB>(Pt[k]) * invJ; }
+    for (int k = 0; k < 3; ++k) { muX[k] = lane_sum<LB>(Gt[k]) * invJ; muY[k] = lane_sum<LB>(Pt[k]) * invJ; }
 #pragma unroll
     for (int k = 0; k < 3; ++k) { X0[k] = body ? Gt[k] - muX[k] : 0.0; Y0[k] = body ? Pt[k] - muY[k] : 0.0; }
-    const double normX = sqrt(group_sum_f64<LB>(X0[0] * X0[0] + X0[1] * X0[1] + X0[2] * X0[2]));
-    const double normY = sqrt(group_sum_f64<LB>(Y0[0] * Y0[0] + Y0[1] * Y0[1] + Y0[2] * Y0[2]));
+    const double normX = sqrt(lane_sum<LB>(X0[0] * X0[0] + X0[1] * X0[1] + X0[2] * X0[2]));
+    const double normY = sqrt(lane_sum<LB>(Y0[0] * Y0[0] + Y0[1] * Y0[1] + Y0[2] * Y0[2]));
     const double invX = normX > 0.0 ? 1.0 / normX : 0.0, invY = normY > 0.0 ? 1.0 / normY : 0.0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) { X0[k] *= invX; Y0[k] *= invY; }
@@ -121,7 +114,7 @@ __global__ void __launch_bounds__(kEvalThreads) im_eval_accum_kernel(const pulse
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int k = 0; k < 3; ++k) H[i][k] = group_sum_f64<LB>(X0[i] * Y0[k]);
+        for (int k = 0; k < 3; ++k) H[i][k] = lane_sum<LB>(X0[i] * Y0[k]);
     const double detH = H[0][0] * (H[1][1] * H[2][2] - H[1][2] * H[2][1]) - H[0][1] * (H[1][0] * H[2][2] - H[1][2] * H[2][0]) +
                         H[0][2] * (H[1][0] * H[2][1] - H[1][1] * H[2][0]);
     jacobi_svd3(H, V);                                        // H now holds U Sigma, column by column
@@ -149,7 +142,7 @@ __global__ void __launch_bounds__(kEvalThreads) im_eval_accum_kernel(const pulse
     for (int c = 0; c < 3; ++c) tvec[c] = muX[c] - scale * (muY[0] * R[0][c] + muY[1] * R[1][c] + muY[2] * R[2][c]);
 #pragma unroll
     for (int c = 0; c < 3; ++c) al[c] = scale * (Pt[0] * R[0][c] + Pt[1] * R[1][c] + Pt[2] * R[2][c]) + tvec[c];
-    const double t_pa = group_sum_f64<LB>(body ? norm3(al[0] - Gt[0], al[1] - Gt[1], al[2] - Gt[2]) : 0.0) * invJ;
+    const double t_pa = lane_sum<LB>(body ? norm3(al[0] - Gt[0], al[1] - Gt[1], al[2] - Gt[2]) : 0.0) * invJ;
 
     // ---- vel_dist, accel_dist (finite differences over recorded steps)
     double dv[3], da[3];
@@ -158,8 +151,8 @@ __global__ void __launch_bounds__(kEvalThreads) im_eval_accum_kernel(const pulse
         dv[k] = (P[k] - P1[k]) - (G[k] - G1[k]);
         da[k] = (P[k] - 2.0 * P1[k] + P2[k]) - (G[k] - 2.0 * G1[k] + G2[k]);
     }
-    const double t_v = group_sum_f64<LB>(body ? norm3(dv[0], dv[1], dv[2]) : 0.0) * invJ;
-    const double t_a = group_sum_f64<LB>(body ? norm3(da[0], da[1], da[2]) : 0.0) * invJ;
+    const double t_v = lane_sum<LB>(body ? norm3(dv[0], dv[1], dv[2]) : 0.0) * invJ;
+    const double t_a = lane_sum<LB>(body ? norm3(da[0], da[1], da[2]) : 0.0) * invJ;
 
     if (lane == 0) {
         double* acc = a.accum + (int64_t)e * a.accum_stride;

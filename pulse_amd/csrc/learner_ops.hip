@@ -17,17 +17,6 @@ namespace pulse {
 
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_sumf(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------------
 // RunningMeanStd: wide matrices (cols >= 64): threads own columns, blocks own row chunks.
 // ------------------------------------------------------------------------------------------------
@@ -232,7 +221,7 @@ __global__ void __launch_bounds__(256) rms_normalize_narrow_kernel(const float* 
             y[(long long)r * y_stride + c] = o;
         }
         if (partials) {
-            s1 = wave_sum(s1); s2 = wave_sum(s2);
+            s1 = lane_sum(s1); s2 = lane_sum(s2);
             if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s1; red[1][threadIdx.x >> 6] = s2; }
             __syncthreads();
             if (threadIdx.x == 0) {
@@ -289,12 +278,6 @@ __global__ void __launch_bounds__(1024) rms_update_kernel(double* __restrict__ m
 constexpr int kLanesPerSample = 16;
 constexpr float kHalfLog2Pi = 0.91893853320467274178f;  // 0.5 * ln(2 pi)
 
-__device__ __forceinline__ float group16_sum(float v) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, kLanesPerSample);
-    return v;
-}
-
 __global__ void __launch_bounds__(256) policy_sample_kernel(const float* __restrict__ mu, long long mu_stride, const float* __restrict__ logstd,
                                                            const float* __restrict__ noise, long long noise_stride,
                                                            const float* __restrict__ value_raw, long long value_stride,
@@ -319,8 +302,8 @@ __global__ void __launch_bounds__(256) policy_sample_kernel(const float* __restr
         if (mus_out) mus_out[(long long)g * mus_out_stride + j] = m;
         if (sigmas) sigmas[(long long)g * sigmas_stride + j] = m * 0.0f + sg;   // amp_network_builder.py:142-148
     }
-    quad = group16_sum(quad);
-    lsum = group16_sum(lsum);
+    quad = lane_sum<kLanesPerSample>(quad);
+    lsum = lane_sum<kLanesPerSample>(lsum);
     if (l == 0) {
         neglogp[(long long)g * neglogp_stride] = 0.5f * quad + kHalfLog2Pi * (float)A + lsum;
         if (values) {
@@ -365,7 +348,7 @@ __global__ void __launch_bounds__(256) ppo_loss_kernel(const pulse_ppo_loss_args
                 c_lsum += ls;
             }
         }
-        c_lsum = group16_sum(c_lsum);
+        c_lsum = lane_sum<kLanesPerSample>(c_lsum);
     }
     for (int base = blockIdx.x * samples_per_block; base < a.rows; base += gridDim.x * samples_per_block) {
         const int i = base + slot;
@@ -401,7 +384,7 @@ __global__ void __launch_bounds__(256) ppo_loss_kernel(const pulse_ppo_loss_args
                 }
             }
             lsum = c_lsum;
-            quad = group16_sum(quad); bl = group16_sum(bl); kl = group16_sum(kl);
+            quad = lane_sum<kLanesPerSample>(quad); bl = lane_sum<kLanesPerSample>(bl); kl = lane_sum<kLanesPerSample>(kl);
         } else {
             for (int j = l; j < A; j += kLanesPerSample) {
                 const float ls = a.logstd[j], sg = expf(ls);
@@ -418,7 +401,7 @@ __global__ void __launch_bounds__(256) ppo_loss_kernel(const pulse_ppo_loss_args
                 const float dm = omu[j] - m;
                 kl += logf(s1 / sg + 1e-5f) + (sg * sg + dm * dm) / (2.0f * (s1 * s1 + 1e-5f)) + (-0.5f);
             }
-            quad = group16_sum(quad); lsum = group16_sum(lsum); bl = group16_sum(bl); kl = group16_sum(kl);
+            quad = lane_sum<kLanesPerSample>(quad); lsum = lane_sum<kLanesPerSample>(lsum); bl = lane_sum<kLanesPerSample>(bl); kl = lane_sum<kLanesPerSample>(kl);
         }
         const float nlp = 0.5f * quad + kHalfLog2Pi * (float)A + lsum;
         const float adv = a.advantages[d];
@@ -499,7 +482,7 @@ __global__ void __launch_bounds__(256) adv_moments_kernel(const float* __restric
         adv[i] = a;
         s1 += (double)a; s2 += (double)a * (double)a;
     }
-    s1 = wave_sum(s1); s2 = wave_sum(s2);
+    s1 = lane_sum(s1); s2 = lane_sum(s2);
     if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s1; red[1][threadIdx.x >> 6] = s2; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -560,7 +543,7 @@ __global__ void __launch_bounds__(1024) disc_head_kernel(const float* __restrict
         }
     }
 #pragma unroll
-    for (int k = 0; k < 7; ++k) acc[k] = wave_sum(acc[k]);
+    for (int k = 0; k < 7; ++k) acc[k] = lane_sum(acc[k]);
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int k = 0; k < 7; ++k) red[threadIdx.x >> 6][k] = acc[k];
@@ -586,7 +569,7 @@ __global__ void __launch_bounds__(256) sqnorm_partial_kernel(const float* __rest
         s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
     }
     if (blockIdx.x == 0) for (long long i = (n4 << 2) + threadIdx.x; i < count; i += 256) s += x[i] * x[i];
-    s = wave_sumf(s);
+    s = lane_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
@@ -601,7 +584,7 @@ __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __
     if (sq_partials) {
         double s = 0.0;
         for (int i = threadIdx.x; i < npart; i += 256) s += (double)sq_partials[i];
-        s = wave_sum(s);
+        s = lane_sum(s);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = (float)s;
         __syncthreads();
         if (threadIdx.x == 0) {

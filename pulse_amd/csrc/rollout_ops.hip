@@ -13,12 +13,6 @@
 
 namespace pulse {
 
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // rl_games AverageMeter.update (torch_ext.py): windowed running mean over finished episodes
 __device__ __forceinline__ void meter_update(float* st, float sum, float count, float max_size) {
     if (count <= 0.f) return;
@@ -64,7 +58,7 @@ __global__ void __launch_bounds__(1024) rollout_record_kernel(const pulse_rollou
         a.current_lengths[e] = cl * keep;
         a.done_mask[e] = done ? 1 : 0;
     }
-    cnt = wave_sum_f(cnt); sr = wave_sum_f(sr); sl = wave_sum_f(sl);
+    cnt = lane_sum(cnt); sr = lane_sum(sr); sl = lane_sum(sl);
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { red[0][w] = cnt; red[1][w] = sr; red[2][w] = sl; }
     __syncthreads();

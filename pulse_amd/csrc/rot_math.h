@@ -30,6 +30,11 @@ __device__ __forceinline__ Q4 qmul(const Q4 a, const Q4 b) {
 
 __device__ __forceinline__ Q4 qconj(const Q4 a) { return Q4{-a.x, -a.y, -a.z, a.w}; }
 
+// remove_base_rot (phc/env/tasks/humanoid.py:1617-1620): quat_mul(q, conj(0.5, 0.5, 0.5, 0.5)) unless the humanoid starts upright
+__device__ __forceinline__ Q4 remove_base_rot(const Q4 q, int upright_start) {
+    return upright_start ? q : qmul(q, Q4{-0.5f, -0.5f, -0.5f, 0.5f});
+}
+
 // my_quat_rotate, phc/utils/torch_utils.py:45-55:  v(2w^2-1) + 2w(u x v) + 2u(u.v)
 __device__ __forceinline__ V3 qrot(const Q4 q, const V3 v) {
     const float s = 2.0f * (q.w * q.w) - 1.0f;

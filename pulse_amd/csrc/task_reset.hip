@@ -77,8 +77,7 @@ __global__ void __launch_bounds__(kTrThreads) task_reset_kernel(const pulse_task
         if (a.heightsamples && lane < a.num_center_points) {
             // get_center_heights (:690-716) of the MOVED root: the grid turned by the root's yaw only
             const HeightField hf = height_field_of(a);
-            const Q4 bq = a.upright_start ? rq : qmul(rq, Q4{-0.5f, -0.5f, -0.5f, 0.5f});          // remove_base_rot
-            const V3 w = q_apply(yaw_quat(bq), V3{a.center_points[2 * lane], a.center_points[2 * lane + 1], 0.0f});
+            const V3 w = q_apply(yaw_quat(remove_base_rot(rq, a.upright_start)), V3{a.center_points[2 * lane], a.center_points[2 * lane + 1], 0.0f});
             s_cpt[slot][lane] = sample_height(hf, w.x + nx, w.y + ny);
         }
     }
@@ -89,7 +88,7 @@ __global__ void __launch_bounds__(kTrThreads) task_reset_kernel(const pulse_task
             s.p.x = lane == 0 ? 0.0f : s.p.x - rp.x;
             s.p.y = lane == 0 ? 0.0f : s.p.y - rp.y;
         } else if (a.transform == PULSE_TASK_RESET_REMOVE_HEADING) {
-            const Q4 hinv = heading_quat(a.upright_start ? rq : qmul(rq, Q4{-0.5f, -0.5f, -0.5f, 0.5f}), true);
+            const Q4 hinv = heading_quat(remove_base_rot(rq, a.upright_start), true);
             const V3 d = q_apply(hinv, V3{s.p.x - rp.x, s.p.y - rp.y, s.p.z - rp.z});               // quat_apply(h, rb_pos - root_pos) + root_pos
             s.p = V3{d.x + rp.x, d.y + rp.y, d.z + rp.z};
             s.q = qmul(hinv, s.q);

@@ -9,8 +9,10 @@
 // One thread per environment: the per-env state of these tasks is a root record, a target and a handful of scalars
 // (< 500 B with the 24 x 3 contact forces), so the work is launch-latency bound; what matters is that one launch replaces
 // the ~40 elementwise launches of the eager form and that every output goes straight into the caller's buffers (the task
-// observation lands at its column offset of the GEMM-ready observation row).  -ffp-contract=off, reference op order.
+// observation lands at its column offset of the GEMM-ready observation row).  Env selection and the fall test of compute_humanoid_reset
+// are env_select.h's, shared with traj_step.hip.  -ffp-contract=off, reference op order.
 #include "common.h"
+#include "env_select.h"
 #include "rot_math.h"
 
 namespace pulse {
@@ -19,30 +21,9 @@ __device__ __forceinline__ int task_obs_width(int task) {
     return task == PULSE_TASK_SPEED ? 3 : task == PULSE_TASK_REACH ? 3 : 15;
 }
 
-// compute_humanoid_reset's fall test: contact on a non-foot body AND some non-foot body below its termination height
-__device__ __forceinline__ bool has_fallen(const pulse_task_step_args& a, const float* rb, const float* cf, bool* nonstrike_contact) {
-    bool fall_contact = false, fall_height = false, nonstrike = false;
-    for (int b = 0; b < a.num_bodies; ++b) {
-        bool is_contact_body = false, is_strike_body = false;
-        for (int k = 0; k < a.num_contact_ids; ++k) is_contact_body |= a.contact_body_ids[k] == b;
-        for (int k = 0; k < a.num_strike; ++k) is_strike_body |= a.strike_body_ids[k] == b;
-        if (is_contact_body) continue;                           // masked_contact_buf[:, contact_body_ids, :] = 0
-        const float* f = cf + 3 * b;
-        const float ax = fabsf(f[0]), ay = fabsf(f[1]), az = fabsf(f[2]);
-        fall_contact |= (ax > 0.1f) || (ay > 0.1f) || (az > 0.1f);
-        fall_height |= rb[13 * b + 2] < a.termination_heights[b];
-        if (!is_strike_body) nonstrike |= (ax > 50.0f) || (ay > 50.0f) || (az > 50.0f);
-    }
-    *nonstrike_contact = nonstrike;
-    return fall_contact && fall_height;
-}
-
 __global__ void __launch_bounds__(256) task_step_kernel(const pulse_task_step_args a) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int count = a.env_ids ? a.num_ids : a.num_envs;
-    if (i >= count) return;
-    const int64_t e = a.env_ids ? a.env_ids[i] : (int64_t)i;
-    if (a.env_mask && a.env_mask[e] == 0) return;
+    int64_t e;
+    if (!select_env(a, blockIdx.x * blockDim.x + threadIdx.x, e)) return;
     const float* rb = a.rb + e * a.rb_env_stride;
     const V3 root_p{rb[0], rb[1], rb[2]};
     const Q4 root_q{rb[3], rb[4], rb[5], rb[6]};
@@ -126,8 +107,12 @@ __global__ void __launch_bounds__(256) task_step_kernel(const pulse_task_step_ar
         const long long prog = a.progress[e];
         int64_t term = 0;
         if (a.enable_early_termination) {
-            bool nonstrike = false;
-            bool failed = has_fallen(a, rb, a.contact_forces + e * (3 * a.num_bodies), &nonstrike);
+            bool nonstrike = false;                              // strike: a body outside the strike set with a force component above 50 N
+            bool failed = has_fallen(a, rb, a.contact_forces + e * (3 * a.num_bodies), [&](int b, float ax, float ay, float az) {
+                bool is_strike_body = false;
+                for (int k = 0; k < a.num_strike; ++k) is_strike_body |= a.strike_body_ids[k] == b;
+                if (!is_strike_body) nonstrike |= (ax > 50.0f) || (ay > 50.0f) || (az > 50.0f);
+            });
             if (a.task == PULSE_TASK_STRIKE) {
                 const float* tf = a.tar_contact_forces + 3 * e;
                 const bool tar_contact = (fabsf(tf[0]) > 50.0f) || (fabsf(tf[1]) > 50.0f);
@@ -154,7 +139,7 @@ int pulse_task_step(const pulse_task_step_args* args, pulse_stream_t s) {
     const pulse_task_step_args& a = *args;
     PULSE_REQUIRE(a.task == PULSE_TASK_SPEED || a.task == PULSE_TASK_REACH || a.task == PULSE_TASK_STRIKE, "pulse_task_step: unknown task %d", a.task);
     PULSE_REQUIRE(a.num_envs >= 0, "pulse_task_step: negative num_envs");
-    const int count = a.env_ids ? a.num_ids : a.num_envs;
+    const int count = env_count(a);
     if (count == 0 || a.what == 0) return PULSE_OK;
     PULSE_REQUIRE(a.rb != nullptr && a.num_bodies >= 1 && a.rb_env_stride >= 13LL * a.num_bodies, "pulse_task_step: bad rigid-body state");
     if (a.what & PULSE_TASK_OBS) {

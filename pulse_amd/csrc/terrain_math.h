@@ -1,6 +1,7 @@
-// Height-field lookup shared by the kernels that stand on the terrain (traj_step.hip, task_reset.hip):
-// Terrain.world_points_to_map / sample_height_points (phc/env/tasks/humanoid_pedestrian_terrain.py:1191-1270) and the yaw-only
-// rotation of get_center_heights (:690-716, quat_apply_yaw).  Compile with -ffp-contract=off.
+// The only height-field lookup, shared by the kernels that stand on the terrain (traj_step.hip, crowd_obs.hip, task_reset.hip):
+// Terrain.world_points_to_map / sample_height_points (phc/env/tasks/humanoid_pedestrian_terrain.py:1191-1270) and get_center_heights
+// (:690-716, quat_apply_yaw): its yaw-only rotation for all three, its workgroup-wide mean for the two height-block kernels.
+// Compile with -ffp-contract=off.
 #pragma once
 #include <cstdint>
 #include "rot_math.h"
@@ -40,6 +41,31 @@ __device__ __forceinline__ float sample_height(const HeightField& f, float wx, f
 __device__ __forceinline__ Q4 yaw_quat(const Q4 q) {
     const float n = fmaxf(sqrtf(q.z * q.z + q.w * q.w), 1e-9f);
     return Q4{0.0f / n, 0.0f / n, q.z / n, q.w / n};
+}
+
+// The height a height block is measured from, for one env by its WHOLE workgroup (barriers inside: every thread calls it, at most 256 centre
+// points).  use_center: get_center_heights -- the centre grid under the root, turned by the root's yaw only, one thread per point (their
+// dependent gathers overlap), summed by thread 0 in the reference's order, mean; always the plain field, never a stamped one.  Otherwise
+// the root's own height, and the second barrier is still crossed.
+__device__ __forceinline__ float height_reference(const HeightField& f, bool use_center, const float* center_points, int num_center_points,
+                                                  const Q4 root_q, const V3 root_p) {
+    __shared__ float s_center;
+    __shared__ float s_cpt[256];
+    const int tid = threadIdx.x;
+    if (use_center) {
+        if (tid < num_center_points) {
+            const V3 w = q_apply(yaw_quat(root_q), V3{center_points[2 * tid], center_points[2 * tid + 1], 0.0f});
+            s_cpt[tid] = sample_height(f, w.x + root_p.x, w.y + root_p.y);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            float sum = 0.0f;
+            for (int c = 0; c < num_center_points; ++c) sum += s_cpt[c];
+            s_center = sum / (float)num_center_points;
+        }
+    }
+    __syncthreads();
+    return use_center ? s_center : root_p.z;
 }
 
 }  // namespace pulse

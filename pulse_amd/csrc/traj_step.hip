@@ -16,7 +16,7 @@
 // Reward and reset are a handful of scalars per env and ride in the same launch (thread 0 / one wave reduction).
 // -ffp-contract=off: the expressions follow the reference's operation order.
 #include "common.h"
-#include "rot_math.h"
+#include "env_select.h"
 #include "terrain_math.h"
 
 namespace pulse {
@@ -36,19 +36,13 @@ __device__ __forceinline__ V3 traj_pos(const float* verts, int num_verts, float 
 }
 
 __global__ void __launch_bounds__(256) traj_step_kernel(const pulse_traj_step_args a) {
-    __shared__ float s_center;
-    __shared__ float s_cpt[256];
     __shared__ float s_red[4][4];
-    const int count = a.env_ids ? a.num_ids : a.num_envs;
-    const int idx = blockIdx.x;
-    if (idx >= count) return;
-    const int64_t e = a.env_ids ? a.env_ids[idx] : (int64_t)idx;
-    if (a.env_mask && a.env_mask[e] == 0) return;
+    int64_t e;
+    if (!select_env(a, blockIdx.x, e)) return;                                            // (the whole workgroup leaves)
     const int tid = threadIdx.x;
     const float* rb = a.rb + e * a.rb_env_stride;
     const V3 root_p{rb[0], rb[1], rb[2]};
-    Q4 root_q{rb[3], rb[4], rb[5], rb[6]};
-    if (!a.upright_start) root_q = qmul(root_q, Q4{-0.5f, -0.5f, -0.5f, 0.5f});          // remove_base_rot
+    const Q4 root_q = remove_base_rot(Q4{rb[3], rb[4], rb[5], rb[6]}, a.upright_start);
     const float* verts = a.verts + e * (int64_t)a.num_verts * 3;
     const float time = (float)a.progress[e] * a.dt;                                       // progress_buf * self.dt
     const HeightField hf = height_field_of(a);
@@ -70,29 +64,13 @@ __global__ void __launch_bounds__(256) traj_step_kernel(const pulse_traj_step_ar
                     ho[p] = fminf(fmaxf(ref - 0.0f, -3.0f), 3.0f) * a.height_meas_scale;
                 }
             } else {
-                if (a.use_center_height) {
-                    // get_center_heights: 3 x 3 grid under the root, rotated by the root's yaw-only quaternion (quat_apply_yaw).  One thread per
-                    // point (their dependent gathers overlap), summed by thread 0 in the reference's order
-                    if (tid < a.num_center_points) {
-                        const Q4 qy = yaw_quat(root_q);
-                        const V3 w = q_apply(qy, V3{a.center_points[2 * tid], a.center_points[2 * tid + 1], 0.0f});
-                        s_cpt[tid] = sample_height(hf, w.x + root_p.x, w.y + root_p.y);
-                    }
-                    __syncthreads();
-                    if (tid == 0) {
-                        float sum = 0.0f;
-                        for (int c = 0; c < a.num_center_points; ++c) sum += s_cpt[c];
-                        s_center = sum / (float)a.num_center_points;
-                    }
-                }
-                __syncthreads();
+                // get_center_heights (3 x 3 grid under the root), or the root's height
+                const float ref = height_reference(hf, a.use_center_height, a.center_points, a.num_center_points, root_q, root_p);
                 // get_heights: the sensor grid rotated by the HEADING of the sensor body (terrain_obs_root: head) and moved to it
                 const float* sb = rb + 13 * a.sensor_body;
-                Q4 sq{sb[3], sb[4], sb[5], sb[6]};
-                if (!a.upright_start) sq = qmul(sq, Q4{-0.5f, -0.5f, -0.5f, 0.5f});
-                const Q4 hq = heading_quat(sq, false);
-                const float ref = a.use_center_height ? s_center : root_p.z;
+                const Q4 hq = heading_quat(remove_base_rot(Q4{sb[3], sb[4], sb[5], sb[6]}, a.upright_start), false);
                 // four points per thread and pass, their cell indices first and their eight gathers together: the gathers' latencies overlap
+                // (crowd_obs.hip's loop over the same points takes one per thread and reads the owner grid: two kernels on purpose)
                 for (int p0 = tid; p0 < a.num_height_points; p0 += 1024) {
                     long long i1[4], i2[4];
 #pragma unroll
@@ -129,8 +107,7 @@ __global__ void __launch_bounds__(256) traj_step_kernel(const pulse_traj_step_ar
             const float* v = a.dof_vel + e * a.num_dof;
             for (int d = tid; d < a.num_dof; d += 256) pw += fabsf(f[d] * v[d]);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) pw += __shfl_xor(pw, o, 64);
+        pw = lane_sum(pw);
         if ((tid & 63) == 0) s_red[0][tid >> 6] = pw;
         __syncthreads();
         if (tid == 0) {
@@ -162,15 +139,7 @@ __global__ void __launch_bounds__(256) traj_step_kernel(const pulse_traj_step_ar
                 }
                 fallen = sqrtf(fabsf(sx) * fabsf(sx) + fabsf(sy) * fabsf(sy) + fabsf(sz) * fabsf(sz)) > 50.0f;
             } else {
-                bool fall_contact = false, fall_height = false;
-                for (int b = 0; b < a.num_bodies; ++b) {
-                    bool foot = false;
-                    for (int k = 0; k < a.num_contact_ids; ++k) foot |= a.contact_body_ids[k] == b;
-                    if (foot) continue;
-                    fall_contact |= fabsf(cf[3 * b]) > 0.1f || fabsf(cf[3 * b + 1]) > 0.1f || fabsf(cf[3 * b + 2]) > 0.1f;
-                    fall_height |= rb[13 * b + 2] < a.termination_heights[b];
-                }
-                fallen = fall_contact && fall_height;
+                fallen = has_fallen(a, rb, cf, [](int, float, float, float) {});
             }
             fallen = fallen && prog > 1;
             const float dx = tar.x - rb[0], dy = tar.y - rb[1];                           // (the un-rotated root position)
@@ -189,8 +158,7 @@ __global__ void __launch_bounds__(256) traj_step_kernel(const pulse_traj_step_ar
 // reference's order: u_dtheta, u_sharp, sharp_mask (Bernoulli), u_heading, u_dspeed, u_speed0.
 __global__ void __launch_bounds__(64) traj_generate_kernel(const pulse_traj_gen_args a) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= a.num_envs) return;
-    if (a.env_mask && a.env_mask[e] == 0) return;
+    if (!env_enabled(a, e)) return;
     const int segs = a.num_verts - 1;
     const float* rb = a.rb + (int64_t)e * a.rb_env_stride;
     float* v = a.verts + (int64_t)e * a.num_verts * 3;
@@ -229,7 +197,7 @@ int pulse_traj_step(const pulse_traj_step_args* args, pulse_stream_t s) {
     PULSE_REQUIRE(args != nullptr, "pulse_traj_step: null args");
     const pulse_traj_step_args& a = *args;
     PULSE_REQUIRE(a.num_envs >= 0, "pulse_traj_step: negative num_envs");
-    const int count = a.env_ids ? a.num_ids : a.num_envs;
+    const int count = env_count(a);
     if (count == 0 || a.what == 0) return PULSE_OK;
     PULSE_REQUIRE(a.rb && a.num_bodies >= 1 && a.rb_env_stride >= 13LL * a.num_bodies, "pulse_traj_step: bad rigid-body state");
     PULSE_REQUIRE(a.verts && a.num_verts >= 2 && a.traj_dur > 0.f && a.progress && a.dt > 0.f, "pulse_traj_step: trajectory table / clock missing");

@@ -21,22 +21,17 @@ namespace pulse {
 
 constexpr int kVL = 32;   // lanes per row
 
-__device__ __forceinline__ float vsum(float v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, kVL);
-    return v;
-}
 __device__ __forceinline__ float vclamp(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 
 constexpr int kLearned = PULSE_VAE_PRIOR_LEARNED, kFixed = PULSE_VAE_PRIOR_FIXED, kNone = PULSE_VAE_PRIOR_NONE;
 
 // project_to_norm(x, norm, "sphere") = x / (||x|| / norm + 1e-8) over one row (torch_utils.py:38-43).  Every lane of the half-wave calls
 // these; an idle lane (lane >= embedding_size) passes zeros.
-__device__ __forceinline__ float sphere_project(float v, float norm) { return v / (sqrtf(vsum(v * v)) / norm + 1e-8f); }
+__device__ __forceinline__ float sphere_project(float v, float norm) { return v / (sqrtf(lane_sum<kVL>(v * v)) / norm + 1e-8f); }
 // g = d loss / d project(v) -> d loss / d v = g / s - v (g . v) / (s^2 norm ||v||), s = ||v|| / norm + 1e-8; the second term is absent
 // at ||v|| = 0 (torch.norm's sub-gradient)
 __device__ __forceinline__ float sphere_backward(float g, float v, float norm) {
-    const float n = sqrtf(vsum(v * v)), s = n / norm + 1e-8f, gv = vsum(g * v);
+    const float n = sqrtf(lane_sum<kVL>(v * v)), s = n / norm + 1e-8f, gv = lane_sum<kVL>(g * v);
     float o = g / s;
     if (n > 0.f) o -= v * gv / (s * s * norm * n);
     return o;
@@ -182,7 +177,7 @@ __global__ void __launch_bounds__(256) vae_kin_loss_kernel(const pulse_vae_kin_a
         const float* gt = a.gt + i * a.gt_stride;
         float sq = 0.f;
         for (int j = l; j < A; j += kVL) { const float d = pr[j] - gt[j]; sq += d * d; }
-        const float nrm = sqrtf(vsum(sq));
+        const float nrm = sqrtf(lane_sum<kVL>(sq));
         float* dmu = a.dmu + i * a.dmu_stride;
         for (int j = l; j < A; j += kVL) dmu[j] = nrm > 0.f ? ((pr[j] - gt[j]) / nrm) * inv_rows : 0.f;
         // KL(q || prior), loss_functions.py:3-10; against N(0, I) without a prior
@@ -209,9 +204,9 @@ __global__ void __launch_bounds__(256) vae_kin_loss_kernel(const pulse_vae_kin_a
                 err2 = er * er;
             }
         }
-        kl = vsum(kl);
-        const float ar = a.use_ar1 ? sqrtf(vsum(err2)) : 0.f;
-        if (a.use_regu) { e_pm = vsum(e_pm); e_qm = vsum(e_qm); e_pv = vsum(e_pv); e_qv = vsum(e_qv); }
+        kl = lane_sum<kVL>(kl);
+        const float ar = a.use_ar1 ? sqrtf(lane_sum<kVL>(err2)) : 0.f;
+        if (a.use_regu) { e_pm = lane_sum<kVL>(e_pm); e_qm = lane_sum<kVL>(e_qm); e_pv = lane_sum<kVL>(e_pv); e_qv = lane_sum<kVL>(e_qv); }
         acc[0] += nrm; acc[1] += kl; acc[2] += ar; acc[3] += e_pm; acc[4] += e_qm; acc[5] += e_pv; acc[6] += e_qv;
     }
     if (l == 0) {
@@ -315,7 +310,7 @@ __global__ void __launch_bounds__(256) vae_head_backward_kernel(const pulse_vae_
             const bool has_prev = ti > 0 && ar1_keep(a.progress, i - 1), has_next = ti < T - 1 && ar1_keep(a.progress, i);
             if (on && has_prev) e_prev = qm - zh[l - a.zheads_stride] * 0.99f;
             if (on && has_next) e_next = zh[a.zheads_stride + l] - qm * 0.99f;
-            const float n_prev = sqrtf(vsum(e_prev * e_prev)), n_next = sqrtf(vsum(e_next * e_next));
+            const float n_prev = sqrtf(lane_sum<kVL>(e_prev * e_prev)), n_next = sqrtf(lane_sum<kVL>(e_next * e_next));
             if (on) {
                 if (n_prev > 0.f) g_qm += a.c_ar1 * (e_prev / n_prev);
                 if (n_next > 0.f) g_qm += a.c_ar1 * (-0.99f * (e_next / n_next));

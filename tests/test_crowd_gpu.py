@@ -185,6 +185,43 @@ def test_crowd_config_trains_two_epochs(dev, kind):
     assert blk.abs().max().item() <= 20.0 and blk.std().item() > 0.1
 
 
+def test_plain_height_block_is_traj_steps_bit_for_bit(dev):
+    """pulse_crowd_heights without owner grid and velocity channels and the height block of pulse_traj_step share terrain_math.h's cell
+    lookup and centre height, so on the same inputs they are the same bits.  Five envs on the synthetic field; a 7-point grid (traj_step
+    takes four points per thread: 7 is no multiple of 4) and the 32 x 32 one (four passes of the one-point-per-thread loop); centre height
+    and upright start on and off; env 3 stands on the field's corner, so points leave it on both axes and are clipped to [0, size - 2];
+    a mask leaves rows 1 and 4 as they were.  Every combination goes through ops.traj_step: none is left out."""
+    from pulse_amd._lib import TASK_OBS
+    n, off, head = 5, 6, M.HEAD
+    rb = torch.from_numpy(Z["n24g6/rb"])[:n].clone()
+    # the corner: the field is 26 m x 30 m (260 x 300 cells of 0.1 m).  Both grids reach 1.41 m or more from the sensor in every direction
+    # whatever its heading, so with the head within 1 m of the root on either axis (25.6 - 1 + 1.41 > 25.9, -0.4 + 1 - 1.41 < 0) some
+    # point has x past the last cell pair and some point y < 0
+    rb[3, :, 0:2] += torch.tensor([25.6, -0.4]) - rb[3, 0, 0:2]
+    assert (rb[3, head, 0:2] - rb[3, 0, 0:2]).abs().max() < 1.0
+    rb = rb.to(dev)
+    seven = torch.tensor([[2.0, 0.0], [-2.0, 0.0], [0.0, 2.0], [0.0, -2.0], [1.5, 1.5], [-1.5, -1.5], [0.3, -0.1]])
+    verts = torch.zeros(n, 2, 3, device=dev)
+    verts[:, 1, 0] = 1.0
+    prog = torch.zeros(n, dtype=torch.int64, device=dev)
+    mask = torch.tensor([1, 0, 1, 1, 0], dtype=torch.bool)
+    for hp in (seven.to(dev), syn.square_height_points(2.0, 32).to(dev)):
+        nh = hp.shape[0]
+        for center in (True, False):
+            for upright in (True, False):
+                kw = dict(upright=upright, sensor_body=head, center_points=CP.to(dev), use_center_height=center)
+                crowd = torch.full((n, off + nh + 5), float("nan"), device=dev)
+                ops.crowd_heights(rb, HS.to(dev), hp, obs=crowd, obs_offset=off, env_mask=mask.to(dev), **kw)
+                traj = torch.full((n, off + 20 + nh + 5), float("nan"), device=dev)
+                ops.traj_step(rb, verts, prog, what=TASK_OBS, dt=1.0 / 30.0, episode_dur=10.0, heightsamples=HS.to(dev), height_points=hp,
+                              obs=traj, obs_offset=off, env_mask=mask.to(dev), **kw)
+                crowd, traj, tag = crowd.cpu(), traj.cpu(), (nh, center, upright)
+                assert torch.isnan(crowd[~mask]).all() and torch.isnan(traj[~mask]).all(), tag          # masked rows: poison untouched
+                assert torch.isnan(crowd[:, :off]).all() and torch.isnan(crowd[:, off + nh:]).all(), tag
+                got, want = crowd[mask, off:off + nh], traj[mask, off + 20:off + 20 + nh]
+                assert torch.isfinite(got).all() and torch.equal(got, want), tag
+
+
 def test_error_statuses_and_wrapper_checks(dev):
     lib = _lib.load()
     rb = torch.from_numpy(Z["n24g6/rb"]).to(dev)
