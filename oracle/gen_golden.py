@@ -14,6 +14,7 @@ Fixtures (all small, < 1 MB each):
   env_amp.npz     AMP per-frame observation (full 23 joints, 19-joint dof subset, global root)
   agent_math.npz  GAE discount_values, PPO actor/critic/bound losses, _calc_advs
   rms.npz         RunningMeanStd forward sequences (fp64 state), kl_multi
+  motion_degenerate.npz  the motion query on still / frozen / identity / slow / sign-flipped joints (oracle/degenerate_clips.py)
 """
 import os
 import sys
@@ -355,6 +356,41 @@ def gen_motion_lib(num_motions=9, n=203):
     np.savez_compressed(os.path.join(GOLDEN_DIR, "motion_lib.npz"), **_np(out))
 
 
+def motion_degenerate(seed=20261):
+    """The arrays of motion_degenerate.npz: MotionLibBase.get_motion_state / get_root_pos_smpl / _calc_frame_blend run from the reference's own
+    source on the degenerate library of oracle/degenerate_clips.py (still, frozen, identity, slow and sign-flipped joints; clips of 2 and 3
+    frames) at its queries, with the branch label of every consecutive pair stored alongside."""
+    from oracle import degenerate_clips as D
+    cls = refload.motion_lib_class()
+    tabs, info = D.build(seed, "smpl")
+    num_motions = tabs["motion_lengths"].shape[0]
+    ref = cls()
+    for k in ("gts", "grs", "lrs", "gvs", "gavs", "dvs", "length_starts"):
+        setattr(ref, k, tabs[k])
+    ref._motion_lengths, ref._motion_fps, ref._motion_dt = tabs["motion_lengths"], tabs["motion_fps"], tabs["motion_dt"]
+    ref._motion_num_frames, ref.num_bodies, ref._device = tabs["motion_num_frames"], syn.NUM_BODIES, "cpu"
+    ref._motion_aa = torch.zeros(tabs["gts"].shape[0], 72)
+    ref._motion_bodies = torch.zeros(num_motions, 17)
+    ref._motion_limb_weights = torch.zeros(num_motions, 10)
+    ids, times, offset = D.queries(tabs, seed)
+    bad = D.query_conditions(tabs, ids, times)
+    assert not bad, f"queries on a cliff of quat_to_angle_axis (query, joint, w): {bad[:8]}"
+    res = ref.get_motion_state(ids, times, offset)
+    res_no = ref.get_motion_state(ids, times)
+    f0, f1, blend = ref._calc_frame_blend(times, tabs["motion_lengths"][ids], tabs["motion_num_frames"][ids], tabs["motion_dt"][ids])
+    out = {"tab_" + k: v for k, v in tabs.items()}
+    out.update({"motion_ids": ids, "motion_times": times, "offset": offset, "frame_idx0": f0, "frame_idx1": f1, "blend": blend,
+                "root_pos_smpl": ref.get_root_pos_smpl(ids, times)["root_pos"], "rg_pos_no_offset": res_no["rg_pos"], "seed": np.int64(seed),
+                "kinds": info["kinds"], "pair_rows": info["pair_rows"], "lrs_labels": info["lrs_labels"], "grs_labels": info["grs_labels"]})
+    for key in ("root_pos", "root_rot", "dof_pos", "root_vel", "root_ang_vel", "dof_vel", "rg_pos", "rb_rot", "body_vel", "body_ang_vel"):
+        out[key] = res[key]
+    return _np(out)
+
+
+def gen_motion_degenerate():
+    np.savez_compressed(os.path.join(GOLDEN_DIR, "motion_degenerate.npz"), **motion_degenerate())
+
+
 def gen_tasks(n=61):
     """Downstream-task functions (speed / reach / strike + the base reset) from the reference's own TorchScript sources."""
     fn = refload.task_functions()
@@ -565,6 +601,7 @@ def main():
     gen_agent_math()
     gen_rms()
     gen_motion_lib()
+    gen_motion_degenerate()
     gen_tasks()
     for f in sorted(os.listdir(GOLDEN_DIR)):
         print(f, os.path.getsize(os.path.join(GOLDEN_DIR, f)), "bytes")
