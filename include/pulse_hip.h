@@ -712,6 +712,64 @@ int pulse_sizeof_crowd_heights_args(void);
 int pulse_crowd_heights(const pulse_crowd_heights_args* args, pulse_stream_t s);
 
 /* ------------------------------------------------------------------------- *
+ * 2a''''. The walkable map of the terrain task (Terrain, humanoid_pedestrian_terrain.py:1114-1189): where a humanoid may be put at a
+ *     reset.  Two construction-time entries (the obstacle field and the table of valid start cells) and the per-reset draw from the table.
+ * ------------------------------------------------------------------------- */
+#define PULSE_TERRAIN_MAX_DILATION 16
+
+/* The flagging of the 'poles' tiles and its dilation (randomized_terrain :1362-1364, 1380; curiculum :1443-1445, 1471):
+ *     walkable[r, c] = 1  iff  some cell within L1 distance ``iterations`` of (r, c), inside the array, is an obstacle
+ * -- ndimage.binary_dilation(walkable_field_raw, iterations = k) with its default cross and zero border is this diamond.  A cell is an
+ * obstacle when its tile is flagged and its height is not 0 (tile (i, j) covers rows border + i length_px .., columns border + j width_px ..;
+ * cells of the border belong to no tile), or when ``obstacle_mask`` (rows, cols), a caller's own field, is set there.  Either source may
+ * be NULL; heights is needed with tile_flags.  One thread per cell, one pass; 0 <= iterations <= PULSE_TERRAIN_MAX_DILATION. */
+typedef struct pulse_terrain_walkable_args {
+    int32_t rows, cols;
+    const int16_t* heights;                                  /* (rows, cols) height_field_raw */
+    const uint8_t* tile_flags; int32_t tile_rows, tile_cols; /* (tile_rows, tile_cols): 1 = a poles tile */
+    int32_t border, length_px, width_px;
+    const uint8_t* obstacle_mask;                            /* (rows, cols) or NULL */
+    int32_t iterations;
+    uint8_t* walkable;                                       /* (rows, cols) out: 0 / 1 */
+} pulse_terrain_walkable_args;
+int pulse_sizeof_terrain_walkable_args(void);
+int pulse_terrain_walkable(const pulse_terrain_walkable_args* args, pulse_stream_t s);
+
+/* The table of valid start cells (Terrain.__init__ :1160-1172): the candidates are the cells with walkable == 0; xmin, xmax, ymin, ymax are
+ * taken over the candidates' rows (x) and columns (y); a candidate is kept iff
+ *     x_s < xmax_s - b  &&  y_s < ymax_s - b  &&  x_s > xmin_s + b  &&  y_s > ymin_s + b,     x_s = (float)x * horizontal_scale,
+ * all in float32 in that order, b = border_scaled (the host's border * horizontal_scale rounded once to float32).  coord_x / coord_y
+ * receive x_s / y_s of the kept cells in row-major order (torch.where's), at most ``capacity`` of them (entries past it are dropped, never
+ * written); *count receives how many there are.  Entries past the count are not touched.  Five launches on the stream: per-row candidate
+ * extents, their reduction, per-row counts, an exclusive scan (one workgroup), one workgroup per row writing its cells in column order.
+ * Scratch: row_extents int32 (2 rows + 4), row_offsets int64 (rows + 1). */
+typedef struct pulse_terrain_valid_args {
+    int32_t rows, cols;
+    const uint8_t* walkable;                                 /* (rows, cols) */
+    float horizontal_scale, border_scaled;
+    int32_t* row_extents; int64_t* row_offsets;              /* scratch */
+    float* coord_x; float* coord_y; int64_t capacity;        /* out: (capacity,) each */
+    int64_t* count;                                          /* out: one int64 */
+} pulse_terrain_valid_args;
+int pulse_sizeof_terrain_valid_args(void);
+int pulse_terrain_valid_cells(const pulse_terrain_valid_args* args, pulse_stream_t s);
+
+/* Terrain.sample_valid_locations (:1175-1189) for the envs of the mask (all when NULL); the rows of the other envs are not touched.
+ * group_num_people 0:  out[e] = (coord_x[idx[e]], coord_y[idx[e]]),  idx (num_envs,) int64 draws in [0, num_samples) -- an index outside
+ * the table writes nothing.  group_num_people P > 0 (:1176-1183; num_envs a multiple of P): env e is member e % P of group g = e / P,
+ *     out[e] = (extent_x * u_center[g] + (16 u_dx[e] - 8),  extent_y * u_center[G + g] + (-16 u_dy[e] + 8)),
+ * u_center (2, G), u_dx / u_dy (G, P) uniform draws in the reference's order, torch_rand_float's (hi - lo) * u + lo. */
+typedef struct pulse_terrain_sample_args {
+    int32_t num_envs; const uint8_t* env_mask;
+    const float* coord_x; const float* coord_y; int64_t num_samples; const int64_t* idx;
+    int32_t group_num_people; float extent_x, extent_y;
+    const float* u_center; const float* u_dx; const float* u_dy;
+    float* out;                                              /* (num_envs, 2) */
+} pulse_terrain_sample_args;
+int pulse_sizeof_terrain_sample_args(void);
+int pulse_terrain_sample(const pulse_terrain_sample_args* args, pulse_stream_t s);
+
+/* ------------------------------------------------------------------------- *
  * 3. GAE: CommonAgent.discount_values + returns, phc/learning/common_agent.py:493-505,
  *    :346-347.  Element (t, n) of every array lives at t*stride_t + n*stride_n.
  *    gamma_tau is the host-side double product gamma*tau rounded to float (as

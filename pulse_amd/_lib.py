@@ -224,6 +224,25 @@ class CrowdHeightsArgs(Structure):
                 ("obs", c_void_p), ("obs_stride", c_int64), ("obs_offset", c_int32)]
 
 
+class TerrainWalkableArgs(Structure):
+    _fields_ = [("rows", c_int32), ("cols", c_int32), ("heights", c_void_p), ("tile_flags", c_void_p), ("tile_rows", c_int32),
+                ("tile_cols", c_int32), ("border", c_int32), ("length_px", c_int32), ("width_px", c_int32), ("obstacle_mask", c_void_p),
+                ("iterations", c_int32), ("walkable", c_void_p)]
+
+
+class TerrainValidArgs(Structure):
+    _fields_ = [("rows", c_int32), ("cols", c_int32), ("walkable", c_void_p), ("horizontal_scale", c_float), ("border_scaled", c_float),
+                ("row_extents", c_void_p), ("row_offsets", c_void_p), ("coord_x", c_void_p), ("coord_y", c_void_p), ("capacity", c_int64),
+                ("count", c_void_p)]
+
+
+class TerrainSampleArgs(Structure):
+    _fields_ = [("num_envs", c_int32), ("env_mask", c_void_p), ("coord_x", c_void_p), ("coord_y", c_void_p), ("num_samples", c_int64),
+                ("idx", c_void_p), ("group_num_people", c_int32), ("extent_x", c_float), ("extent_y", c_float),
+                ("u_center", c_void_p), ("u_dx", c_void_p), ("u_dy", c_void_p), ("out", c_void_p)]
+
+
+TERRAIN_MAX_DILATION = 16                            # PULSE_TERRAIN_MAX_DILATION
 CROWD_GROUP_OBS, CROWD_ROOT_POINTS = 165, 200        # PULSE_CROWD_GROUP_OBS, PULSE_CROWD_ROOT_POINTS
 
 
@@ -375,6 +394,12 @@ SIGNATURES = {
     "pulse_crowd_stamp": (c_int, [POINTER(CrowdStampArgs), P]),
     "pulse_sizeof_crowd_heights_args": (c_int, []),
     "pulse_crowd_heights": (c_int, [POINTER(CrowdHeightsArgs), P]),
+    "pulse_sizeof_terrain_walkable_args": (c_int, []),
+    "pulse_terrain_walkable": (c_int, [POINTER(TerrainWalkableArgs), P]),
+    "pulse_sizeof_terrain_valid_args": (c_int, []),
+    "pulse_terrain_valid_cells": (c_int, [POINTER(TerrainValidArgs), P]),
+    "pulse_sizeof_terrain_sample_args": (c_int, []),
+    "pulse_terrain_sample": (c_int, [POINTER(TerrainSampleArgs), P]),
     "pulse_vae_embed": (c_int, [POINTER(VaeEmbedArgs), P]),
     "pulse_vae_embed_prior": (c_int, [POINTER(VaeEmbedPriorArgs), P]),
     "pulse_sizeof_vae_embed_prior_args": (c_int, []),

@@ -78,6 +78,30 @@ def crowd_env(kind, **extra):
     return dict(CROWD_ENVS[kind], **extra)
 
 
+# Maps for the terrain task (env/terrain.py:Terrain; the ``terrain`` block of env_pulse_terrain.yaml:75-90), small enough for tests: the
+# curriculum layout over the tile kinds that need no isaacgym.terrain_utils generator -- 'poles' (synthetic.synthetic_poles stands in for
+# poles_terrain) and flat.  make_agent("terrain_z_amp_small", terrain="poles_small") resets its humanoids onto the valid start cells.
+TERRAINS = {
+    # 2 levels x 4 terrains of 8 m (small_terrain, humanoid_pedestrian_terrain.py:817-819): terrains 0, 1 poles, 2, 3 flat
+    "poles_small": {"terrainType": "trimesh", "curriculum": True, "mapLength": 8., "mapWidth": 8., "numLevels": 2, "numTerrains": 4,
+                    "terrainProportions": [0., 0., 0., 0., 0., 0., 0.5, 0.5], "slopeTreshold": 0.9},
+}
+
+
+def terrain_env(kind, **extra):
+    """The env-dict overrides of a TERRAINS entry (its ``terrain`` block, a copy), for make_agent / make_env's ``env_overrides``."""
+    return {"terrain": dict(TERRAINS[kind], **extra)}
+
+
+def make_terrain(kind, num_robots, device, seed=1234, **extra):
+    """The Terrain of a TERRAINS entry on ``device``; its poles are drawn from a generator seeded with ``seed``."""
+    from . import synthetic as syn
+    from .env.terrain import Terrain
+    g = syn.make_generator(seed + 83)
+    return Terrain.from_config(dict(TERRAINS[kind], **extra), num_robots, {"poles": lambda terrain, difficulty: syn.synthetic_poles(terrain, difficulty, g)},
+                               device)
+
+
 NETWORK_Z_READER = {      # phc/data/cfg/learning/pulse_z_task.yaml:10-44 (network: amp_z_reader)
     "name": "amp_z_reader", "separate": True,
     "space": {"continuous": {"mu_activation": "None", "sigma_activation": "None", "mu_init": {"name": "default"},
@@ -247,7 +271,7 @@ def agent_config(name, **overrides):
 
 
 def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kind="im", reference="recorded", env_overrides=None, humanoid="smpl",
-             num_clips=None, robot_overrides=None, dof_limits=None):
+             num_clips=None, robot_overrides=None, dof_limits=None, terrain=None):
     """``humanoid``: 'smpl' (24 bodies) | 'smplx' / 'smplh' (52 bodies) -- the robot config handed to the task as cfg.robot.
     ``reference``: 'recorded' = pre-recorded rigid-body / reference frames (RecordedRollout, what the CPU oracle agent replays);
     'motion_lib' = reference motion queried from the HBM-resident MotionLib every step, physics stand-in tracking it;
@@ -255,9 +279,13 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
     env out of ``num_clips`` unique ones -- min(num_envs, 1024) / 2 + 1 unless given -- re-drawn by resample_motions).
     ``robot_overrides``: cfg.robot keys on top of the humanoid's (bias_offset, has_smpl_pd_offset, freeze_toe, freeze_hand, ...).
     ``dof_limits``: the joint limits the stand-in simulator publishes -- None (none: the PD-target table stays offset 0 / scale 1), True
-    (synthetic.synthetic_dof_limits of the humanoid) or a (lower, upper) pair."""
+    (synthetic.synthetic_dof_limits of the humanoid) or a (lower, upper) pair.
+    ``terrain`` (env_kind 'terrain_z'): a TERRAINS name or an env/terrain.py:Terrain the simulator publishes as ``sim.terrain`` -- the task
+    then walks on its height field and resets onto its valid start cells."""
     from .env.humanoid_im import HumanoidIm, VecTaskPythonWrapper, check_humanoid_options
     robot = robot_config(humanoid, **(robot_overrides or {}))
+    if terrain is not None and env_kind != "terrain_z":
+        raise ValueError(f"make_env: terrain= belongs to env_kind 'terrain_z', not {env_kind!r}")
     if dof_limits is True:
         from . import synthetic as _syn
         dof_limits = _syn.synthetic_dof_limits(humanoid)
@@ -268,10 +296,13 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
         from .learning.network_z import AMPZNetwork
         env_cfg = dict(ENV_TERRAIN_Z if env_kind == "terrain_z" else ENV_SPEED_Z)
         env_cfg.update(env_overrides or {})
+        if isinstance(terrain, str):
+            env_cfg.update(terrain_env(terrain))
+            terrain = make_terrain(terrain, num_envs, device, seed=seed)
         # the terrain task's humanoids walk inside the synthetic height field (cells of 0.1 m): start them near its middle
         amp = bool(env_cfg.get("enable_amp_obs", False))
         sim = HT.SyntheticTaskSim(num_envs, horizon + 1, device, seed=seed, rank=rank, xy_offset=(13.0, 15.0) if env_kind == "terrain_z" else (0.0, 0.0),
-                                  dof_pos_bank=amp, dof_limits=dof_limits)
+                                  dof_pos_bank=amp, dof_limits=dof_limits, terrain=terrain)
         motion = None
         if amp:                                          # the HumanoidAMP layer resets from, looks back into and demonstrates with a motion library
             from . import synthetic as syn
@@ -344,7 +375,8 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
     return VecTaskPythonWrapper(task, rl_device=device), rollout
 
 
-def make_agent(name="cfg2", device="cuda:0", seed=1234, rank=0, rollout=None, reference="recorded", env_overrides=None, humanoid=None, **overrides):
+def make_agent(name="cfg2", device="cuda:0", seed=1234, rank=0, rollout=None, reference="recorded", env_overrides=None, humanoid=None, terrain=None,
+               **overrides):
     from .learning.amp_agent import AMPAgent
     from .learning.common_agent import CommonAgent
     num_envs_override = overrides.pop("num_envs_override", None)
@@ -352,7 +384,8 @@ def make_agent(name="cfg2", device="cuda:0", seed=1234, rank=0, rollout=None, re
     if num_envs_override is not None:
         num_envs = int(num_envs_override)
     vec_env, rollout = make_env(num_envs, cfg["horizon_length"], device, seed=seed, rank=rank, rollout=rollout, env_kind=cfg["_env_kind"],
-                                reference=reference, env_overrides=dict(cfg["_env_overrides"], **(env_overrides or {})) or None, humanoid=humanoid if humanoid is not None else cfg["_humanoid"])
+                                reference=reference, env_overrides=dict(cfg["_env_overrides"], **(env_overrides or {})) or None, humanoid=humanoid if humanoid is not None else cfg["_humanoid"],
+                                terrain=terrain)
     cfg.update({"vec_env": vec_env, "device": device, "seed": seed})
     cls = AMPAgent if cfg["_agent_kind"] == "amp" else CommonAgent
     return cls("pulse_amd", cfg), rollout

@@ -38,6 +38,7 @@ SOURCES = [
     ("task_step.hip", NO_CONTRACT),
     ("traj_step.hip", NO_CONTRACT),
     ("crowd_obs.hip", NO_CONTRACT),
+    ("terrain_map.hip", NO_CONTRACT),
     ("motion_state.hip", NO_CONTRACT),
     ("task_reset.hip", NO_CONTRACT),
     ("motion_build.hip", NO_CONTRACT),

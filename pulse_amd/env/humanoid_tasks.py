@@ -158,8 +158,9 @@ class HumanoidTask:
         self._last_demo = (ids, t0)
         return out
 
-    def _ref_state_kwargs(self):
-        """The transform arguments of ops.task_ref_state_init beside ``transform`` (the terrain task adds its location and height field)."""
+    def _ref_state_kwargs(self, mask=None):
+        """The transform arguments of ops.task_ref_state_init beside ``transform`` (the terrain task adds its location and height field);
+        ``mask``: the envs being reset."""
         return {}
 
     def _reset_ref_state_init(self, mask):
@@ -172,7 +173,7 @@ class HumanoidTask:
         sim = self.sim
         ops.task_ref_state_init(lib, ids, times, mask, sim.rigid_body_state, sim.dof_pos, sim.dof_vel, self._motion_start_times, self._sampled_motion_ids,
                                 clears=(self.progress_buf, self.reset_buf, self._terminate_buf), transform=self.REF_STATE_TRANSFORM,
-                                upright=self._has_upright_start, **self._ref_state_kwargs())
+                                upright=self._has_upright_start, **self._ref_state_kwargs(mask))
         if hasattr(sim, "on_reset"):
             sim.on_reset(mask)
 
@@ -420,6 +421,7 @@ class HumanoidTraj(HumanoidTask):
         self._traj_sample_timestep = float(env.get("trajSampleTimestep", 0.5))
         self.terrain_obs = bool(env.get("terrain_obs", self.TERRAIN_OBS))
         self._height_points = self._center_points = self._heightsamples = None
+        self._terrain = self._sim_terrain(env, sim)                                          # before anything goes to the device
         if self.terrain_obs:
             if env.get("terrain_obs_type", "square") != "square":
                 raise NotImplementedError("terrain_obs_type 'square' (env_pulse_terrain.yaml) is built; 'fov' / 'square_fov' are viewer-era variants")
@@ -443,10 +445,29 @@ class HumanoidTraj(HumanoidTask):
             if terrain_type == "none":
                 raise NameError("Can't measure height with terrain type 'none'")            # get_heights (:744-745)
             if terrain_type != "plane":
-                hs = getattr(sim, "heightsamples", None)
+                hs = getattr(sim, "heightsamples", None) if self._terrain is None else self._terrain.heightsamples
                 self._heightsamples = (hs if hs is not None else syn.synthetic_height_field()).to(dev).contiguous()
             self._horizontal_scale, self._vertical_scale, self.height_meas_scale = 0.1, 0.005, 5.0    # Terrain.__init__ (:1121-1122), :69
         self._init_crowd(dev)
+
+    def _sim_terrain(self, env, sim):
+        """``sim.terrain`` (env/terrain.py: the map and its walkable field) when the simulator publishes one and the task can walk on it; a
+        terrain the task would have to ignore raises instead of falling back to the uniform draw without a word."""
+        terrain = getattr(sim, "terrain", None)
+        if terrain is None:
+            return None
+        name, terrain_type = type(self).__name__, env.get("terrain", {}).get("terrainType", "trimesh")
+        if not self.terrain_obs:
+            raise ValueError(f"{name}: the simulator publishes a terrain, but terrain_obs is off: this task never looks at a map "
+                             "(HumanoidTraj has none, phc/env/tasks/humanoid_traj.py)")
+        if terrain_type == "plane":
+            raise ValueError(f"{name}: the simulator publishes a terrain, but terrainType is 'plane': the reference builds no map there "
+                             "(Terrain.__init__ returns first, phc/env/tasks/humanoid_pedestrian_terrain.py:1119-1120)")
+        hs = getattr(sim, "heightsamples", None)
+        if hs is not None and tuple(hs.shape) != tuple(terrain.heightsamples.shape):
+            raise ValueError(f"{name}: the simulator publishes a terrain of {tuple(terrain.heightsamples.shape)} cells and heightsamples of "
+                             f"{tuple(hs.shape)}: which map the humanoids walk on is ambiguous")
+        return terrain
 
     # ---- crowd variant (humanoid.py:256-261; humanoid_pedestrian_terrain.py:253-293, 385-439, 718-772, 1200-1276, 1700-1753)
     def _read_crowd_options(self, env, num_envs):
@@ -571,8 +592,14 @@ class HumanoidTraj(HumanoidTask):
 class HumanoidPedestrianTerrain(HumanoidTraj):
     """HumanoidPedestrianTerrain (phc/env/tasks/humanoid_pedestrian_terrain.py:31-890; env_pulse_terrain.yaml): the trajectory task over a height
     field -- the task observation gains the 32 x 32 height map under the head (:384-440), a fall is a summed non-foot contact force above
-    50 N (:1476-1531), the reward keeps a power term (:871-890).  The terrain itself (isaacgym.terrain_utils, PhysX tri-mesh) is a synthetic
-    height field here.
+    50 N (:1476-1531), the reward keeps a power term (:871-890).
+
+    The map: when the simulator publishes ``sim.terrain`` (env/terrain.py:Terrain -- the reference's geometry, tile layout, obstacle field
+    of the 'poles' tiles with its 3-step dilation, table of valid start cells), its height field is the task's and every reset location is
+    drawn from the valid cells (Terrain.sample_valid_locations, :531, 1175-1189).  Without one the map is ``sim.heightsamples`` or a
+    synthetic height field, and reset locations are uniform over its interior.  Not built: the sub-terrain generators
+    (isaacgym.terrain_utils; Terrain takes them as plug-ins), convert_heightfield_to_trimesh and anything PhysX, MeshTerrain (:975-1112),
+    the flags.fixed / flags.server_mode placements (:535-549).
 
     Crowd variant (no shipped config enables it; configs.crowd_env): ``divide_group`` partitions the envs into contiguous groups of
     min(num_env_group, num_envs) (humanoid.py:256-261).  With ``group_obs`` the task observation gains the 165-float 'people' block,
@@ -588,11 +615,18 @@ class HumanoidPedestrianTerrain(HumanoidTraj):
     CROWD = True
     REF_STATE_TRANSFORM = "terrain"                 # humanoid_pedestrian_terrain.py:527-589
 
-    def _ref_state_kwargs(self):
-        """The new location of every env (:531) and the height field the root is lifted over (:553-563).  Terrain.sample_valid_locations
-        draws from the walkable map of the Isaac scene; here: uniform over the interior of the height field, a sensor reach from its
-        edges, from the generator the motions are drawn with."""
+    def _ref_state_kwargs(self, mask=None):
+        """The new location of every env (:531) and the height field the root is lifted over (:553-563).  With a Terrain: a draw from its
+        valid start cells for the envs of ``mask`` (Terrain.sample_into; the rows of the other envs keep what they held).  Without: uniform
+        over the interior of the height field, a sensor reach from its edges.  Both from the generator the motions are drawn with."""
         hs = self._heightsamples
+        if self._terrain is not None:
+            xy = getattr(self, "_new_root_xy", None)
+            if xy is None:
+                xy = self._new_root_xy = torch.zeros(self.num_envs, 2, device=self.device)
+            self._terrain.sample_into(xy, mask, self._amp_gen)
+            return dict(new_root_xy=xy, heightsamples=hs, horizontal_scale=self._horizontal_scale, vertical_scale=self._vertical_scale,
+                        center_points=self._center_points)
         rows, cols = hs.shape if hs is not None else (260, 300)                   # terrainType 'plane': the extent of the synthetic field
         scale = getattr(self, "_horizontal_scale", 0.1)
         extent = torch.tensor([rows * scale, cols * scale], device=self.device)
@@ -652,7 +686,8 @@ class SyntheticTaskSim:
     """Physics stand-in for the downstream tasks: a bank of recorded frames (rigid bodies with a drifting root, sparse contact
     forces, a target object) replayed one per control step.  Actions are accepted and ignored, exactly like RecordedSim."""
 
-    def __init__(self, num_envs, frames, device, seed=1234, rank=0, fall_rate=0.01, xy_offset=(0.0, 0.0), dof_pos_bank=False, dof_limits=None):
+    def __init__(self, num_envs, frames, device, seed=1234, rank=0, fall_rate=0.01, xy_offset=(0.0, 0.0), dof_pos_bank=False, dof_limits=None,
+                 terrain=None):
         g = syn.make_generator(seed + 31, rank)
         n, j, f = num_envs, syn.NUM_BODIES, frames
         self.num_envs, self.frames, self.frame = n, f, 0
@@ -682,6 +717,8 @@ class SyntheticTaskSim:
         self.target_states[:, 6] = 1.0
         self.target_contact_forces = self.bank["tar_contact"][0].clone()
         self.pd_targets = None
+        if terrain is not None:
+            self.terrain = terrain                                                         # env/terrain.py:Terrain, read by the terrain task
         from .sim import publish_dof_limits
         publish_dof_limits(self, dof_limits, syn.NUM_DOF, device)
 

@@ -990,6 +990,109 @@ def crowd_heights(rb, heightsamples, height_points, *, group_size=0, owner=None,
 
 
 # --------------------------------------------------------------------------- #
+# the walkable map of the terrain task (include/pulse_hip.h section 2a'''')
+# --------------------------------------------------------------------------- #
+def _terrain_grid(t, name, dtype, shape=None):
+    _dev(t, name, dtype)
+    if t.dim() != 2 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        want = "(rows, cols)" if shape is None else str(tuple(shape))
+        raise ValueError(f"{name}: contiguous {want} {dtype} expected, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
+    return t
+
+
+def terrain_walkable(heights=None, *, tile_flags=None, border=0, length_px=0, width_px=0, obstacle_mask=None, iterations=3, out=None):
+    """The obstacle field of Terrain (humanoid_pedestrian_terrain.py:1362-1364, 1380, 1443-1445, 1471) in one launch of pulse_terrain_walkable:
+    (rows, cols) uint8, 1 where a cell of a flagged tile with a non-zero height -- or a set cell of ``obstacle_mask`` -- lies within L1
+    distance ``iterations`` (ndimage.binary_dilation's default cross, zero border).  ``heights`` (rows, cols) int16 with ``tile_flags``
+    (tile_rows, tile_cols) uint8 / bool; tile (i, j) starts at row border + i * length_px, column border + j * width_px."""
+    from ._lib import TerrainWalkableArgs
+    if tile_flags is None and obstacle_mask is None:
+        raise TypeError("terrain_walkable: tile_flags (with heights) or obstacle_mask is required")
+    a, P = TerrainWalkableArgs(), Filler()
+    shape = None
+    if tile_flags is not None:
+        if heights is None:
+            raise TypeError("terrain_walkable: tile_flags need heights")
+        shape = tuple(_terrain_grid(heights, "heights", torch.int16).shape)
+        flags = _terrain_grid(mask_u8(tile_flags), "tile_flags", torch.uint8)
+        a.heights, a.tile_flags, a.tile_rows, a.tile_cols = heights.data_ptr(), P(flags, "tile_flags", torch.uint8), flags.shape[0], flags.shape[1]
+        a.border, a.length_px, a.width_px = int(border), int(length_px), int(width_px)
+    if obstacle_mask is not None:
+        mask = _terrain_grid(mask_u8(obstacle_mask), "obstacle_mask", torch.uint8, shape)
+        shape = tuple(mask.shape)
+        a.obstacle_mask = P(mask, "obstacle_mask", torch.uint8)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=(heights if heights is not None else obstacle_mask).device)
+    _terrain_grid(out, "out", torch.uint8, shape)
+    a.rows, a.cols, a.iterations, a.walkable = shape[0], shape[1], int(iterations), out.data_ptr()
+    _launch("pulse_terrain_walkable", ctypes.byref(a))
+    return out
+
+
+def terrain_valid_cells(walkable, *, border_scaled, horizontal_scale=0.1, coord_x=None, coord_y=None):
+    """The table of valid start cells (Terrain.__init__ :1160-1172) from a (rows, cols) uint8 walkable field: the cells with value 0 that lie
+    more than ``border_scaled`` (the host's float32 border * horizontal_scale) inside the candidates' own extent, scaled to metres, in
+    torch.where's order.  ``coord_x`` / ``coord_y``: equally long float32 buffers to fill -- entries past the count are not touched, cells past
+    the buffers' end are dropped; None: count only (size the table from it and call again).  Returns (coord_x, coord_y, count) with ``count``
+    a device int64 of one element: nothing is read back here."""
+    from ._lib import TerrainValidArgs
+    w = _terrain_grid(mask_u8(walkable), "walkable", torch.uint8)
+    rows, cols = w.shape
+    dev = w.device
+    if (coord_x is None) != (coord_y is None):
+        raise TypeError("terrain_valid_cells: coord_x and coord_y come together")
+    if coord_x is not None:
+        _dev(coord_x, "coord_x"), _dev(coord_y, "coord_y")
+        if coord_x.dim() != 1 or coord_x.shape != coord_y.shape or not (coord_x.is_contiguous() and coord_y.is_contiguous()):
+            raise ValueError(f"coord_x / coord_y: equally long contiguous 1-D buffers expected, got {tuple(coord_x.shape)} and {tuple(coord_y.shape)}")
+    extents = torch.empty(2 * rows + 4, dtype=torch.int32, device=dev)
+    offsets = torch.empty(rows + 1, dtype=torch.int64, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    a = TerrainValidArgs()
+    a.rows, a.cols, a.walkable = rows, cols, w.data_ptr()
+    a.horizontal_scale, a.border_scaled = float(horizontal_scale), float(border_scaled)
+    a.row_extents, a.row_offsets = extents.data_ptr(), offsets.data_ptr()
+    a.count = count.data_ptr()
+    if coord_x is not None and coord_x.numel() > 0:
+        a.coord_x, a.coord_y, a.capacity = coord_x.data_ptr(), coord_y.data_ptr(), coord_x.numel()
+    _launch("pulse_terrain_valid_cells", ctypes.byref(a))
+    return coord_x, coord_y, count
+
+
+def terrain_sample(out, *, coord_x=None, coord_y=None, idx=None, env_mask=None, group_num_people=0, extent_x=0.0, extent_y=0.0, u_center=None,
+                   u_dx=None, u_dy=None):
+    """Terrain.sample_valid_locations (:1175-1189) from injected draws, one launch of pulse_terrain_sample: the rows of ``out`` (N, 2) that
+    ``env_mask`` selects (all when None) receive (coord_x[idx[e]], coord_y[idx[e]]) -- ``idx`` (N,) int64 in [0, len(coord_x)) -- or, with
+    ``group_num_people`` P > 0, centre of group e // P plus member e % P's offset from the uniforms ``u_center`` (2, N / P), ``u_dx`` and
+    ``u_dy`` (N / P, P).  The other rows are not touched."""
+    from ._lib import TerrainSampleArgs
+    _dev(out, "out")
+    if out.dim() != 2 or out.shape[1] != 2 or not out.is_contiguous():
+        raise ValueError(f"out: contiguous (N, 2) expected, got shape {tuple(out.shape)} strides {tuple(out.stride())}")
+    n, p = out.shape[0], int(group_num_people)
+    a, P = TerrainSampleArgs(), Filler()
+    a.num_envs, a.out, a.group_num_people = n, out.data_ptr(), p
+    if env_mask is not None:
+        a.env_mask = P(mask_u8(env_mask), "env_mask", torch.uint8, (n,))
+    if p > 0:
+        if n % p != 0:
+            raise ValueError(f"terrain_sample: {n} envs are not a multiple of group_num_people {p}")
+        if u_center is None or u_dx is None or u_dy is None:
+            raise TypeError("terrain_sample: group mode needs u_center, u_dx and u_dy")
+        g = n // p
+        a.u_center, a.u_dx, a.u_dy = P(u_center, "u_center", shape=(2, g)), P(u_dx, "u_dx", shape=(g, p)), P(u_dy, "u_dy", shape=(g, p))
+        a.extent_x, a.extent_y = float(extent_x), float(extent_y)
+    else:
+        if coord_x is None or coord_y is None or idx is None:
+            raise TypeError("terrain_sample: coord_x, coord_y and idx are required")
+        m = coord_x.shape[0]
+        a.coord_x, a.coord_y, a.num_samples = P(coord_x, "coord_x", shape=(m,)), P(coord_y, "coord_y", shape=(m,)), m
+        a.idx = P(idx, "idx", torch.int64, (n,))
+    _launch("pulse_terrain_sample", ctypes.byref(a))
+    return out
+
+
+# --------------------------------------------------------------------------- #
 # MCP composer stage (include/pulse_hip.h section 4e)
 # --------------------------------------------------------------------------- #
 def mcp_compose(weights, x, out=None, *, num_actions=None, discrete=False):

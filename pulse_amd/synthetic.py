@@ -361,6 +361,26 @@ def synthetic_height_field(rows=260, cols=300, seed=5):
     return torch.round(h / 0.005).to(torch.int16)
 
 
+def synthetic_poles(sub, difficulty, generator):
+    """A deterministic stand-in for isaacgym.terrain_utils.poles_terrain (a closed third-party package; the reference calls it at
+    phc/env/tasks/humanoid_pedestrian_terrain.py:1363, 1444) so that a terrain with obstacles can be built from nothing but a seed:
+    2 + 10 * difficulty discs of radius 0.2 .. 0.5 m and height 1 .. 2.5 m on the flat sub-terrain ``sub`` (``height_field_raw`` (width,
+    length) int16, written in place), none within 1.5 m of its centre, where the env origin is.  Draws come from ``generator``."""
+    import numpy as np
+    w, l = sub.height_field_raw.shape
+    hs, vs = float(sub.horizontal_scale), float(sub.vertical_scale)
+    num = 2 + int(10 * float(difficulty))
+    u = _rand(generator, num, 4).double().numpy()
+    rows, cols = np.meshgrid(np.arange(w), np.arange(l), indexing="ij")
+    for ux, uy, ur, uh in u:
+        cx, cy = ux * (w - 1), uy * (l - 1)
+        if np.hypot(cx - (w - 1) / 2, cy - (l - 1) / 2) * hs < 1.5:
+            continue
+        disc = np.hypot(rows - cx, cols - cy) * hs <= 0.2 + 0.3 * ur
+        sub.height_field_raw[disc] = np.int16(round((1.0 + 1.5 * uh) / vs))
+    return sub
+
+
 def square_height_points(extent=2.0, res=32):
     """init_square_height_points (humanoid_pedestrian_terrain.py:608-625): res x res grid over [-extent, extent]^2, x-major -> (res^2, 2)."""
     import numpy as np
