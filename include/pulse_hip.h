@@ -490,6 +490,61 @@ int pulse_sizeof_motion_build_args(void);
 int pulse_motion_build(const pulse_motion_build_args* args, pulse_stream_t s);
 
 /* ------------------------------------------------------------------------- *
+ * 2b'.1. Raw SMPL pose sequences -> the converted motion data section 2b' starts from (pose_quat_global, root_trans_offset):
+ *      what scripts/data_process/convert_amass_isaac.py:85-137 and convert_amass_data.py:88-141 compute per clip with scipy and
+ *      poselib on the CPU, for every output frame of every clip in one launch (a 32-lane half-wave per frame, lane = body).
+ *        decimation  output frame t of clip m reads staged frame clip_src_start[m] + t * clip_skip[m]; skip = int(framerate / 30)
+ *                    (convert_amass_data.py:88-99).  The result is LABELLED 30 fps whatever framerate / skip is: the reference does that
+ *                    to 100 Hz data (skip 3 -> 33.3 fps, stored as fps 30), and so does the host side here.
+ *        pose_aa     [poses[:, :66], 0]: the hand columns 66 .. 71 read as zero (:90 / isaac :87);
+ *        pose        body b takes source joint joint_map[b] (smpl_2_mujoco, :104-105), scipy Rotation.from_rotvec in fp32: xyzw,
+ *                    scale = 1/2 - a^2/48 + a^4/3840 at angle a <= 1e-3, sin(a/2)/a above; w = cos(a/2) is NOT made positive;
+ *        global      SkeletonState.global_rotation (skeleton3d.py:390-419): the root as from_rotvec gave it, every other body
+ *                    quat_mul_norm(global[parent], local[b]) (rotation3d.py:93-98, 197-202: w made >= 0, then normalised);
+ *        upright     upright_start != 0: normalise, compose with (0.5, 0.5, 0.5, 0.5)^-1 on the right, normalise (scipy's from_quat,
+ *                    __mul__; the sign is kept) (:122-123).  upright_start == 0 leaves the factor out and hands back the local
+ *                    rotations unchanged; the reference has no runnable counterpart of that branch (both scripts hard-code True);
+ *        pose_quat   SkeletonState.local_rotation of the new globals (skeleton3d.py:444-460): root = global, body b =
+ *                    quat_mul_norm(quat_inverse(G[parent]), G[b]) (:125-126);
+ *        trans       root_trans_offset = trans + root_offset (:114);
+ *        mirror      clip_mirror[m] != 0 (convert_amass_isaac.py:120-126, ``double``): out_rot = G[:, mirror_map] with x and z negated,
+ *                    out_trans y negated; pose_quat, pose_aa and trans_orig stay those of the unmirrored clip, as the reference leaves them.
+ *      fp32 throughout, in the reference's operation order (precise sinf / cosf / sqrtf).  Nothing is launched unless every argument passes.
+ * ------------------------------------------------------------------------- */
+#define PULSE_INGEST_MAX_BODIES 32
+#define PULSE_INGEST_SMPL_JOINTS 24  /* joints of a raw SMPL pose row (72 floats) */
+#define PULSE_INGEST_SMPL_HAND_COL 66 /* first of the hand columns */
+typedef struct pulse_motion_ingest_args {
+    /* staged raw data, device */
+    const float* src_pose;              /* (src_frames, 72) axis-angle rows, SMPL joint order */
+    const float* src_trans;             /* (src_frames, 3) */
+    int64_t src_frames;
+    int32_t num_clips;                  /* M output clips (a mirrored copy is a clip of its own) */
+    int32_t num_bodies;                 /* J in [1, 32] */
+    const int64_t* clip_src_start;      /* (M) device: staged frame of the clip's output frame 0 */
+    const int64_t* clip_skip;           /* (M) device: decimation step */
+    const uint8_t* clip_mirror;         /* (M) device, optional: non-zero = the mirrored copy */
+    const int64_t* clip_out_start;      /* (M + 1) device: first output frame of clip m; [M] = total_frames */
+    const int64_t* clip_src_start_host; /* (M) HOST copies: validated before anything is launched (frames >= 1, skip >= 1, */
+    const int64_t* clip_skip_host;      /*     every read inside [0, src_frames), sum of frames = total_frames) */
+    const int64_t* clip_frames_host;
+    const int32_t* parent_indices_host; /* (J) HOST: -1 for body 0, parent < child; handed to the kernel by value with every body's depth */
+    int32_t joint_map[PULSE_INGEST_MAX_BODIES];   /* body -> SMPL joint, first J used */
+    int32_t mirror_map[PULSE_INGEST_MAX_BODIES];  /* body -> body whose rotation the mirrored copy takes (left_to_right_index), first J used */
+    int32_t upright_start;
+    float root_offset[3];               /* added to trans (the skeleton's local_translation[0]) */
+    /* outputs, device */
+    float* out_rot;                     /* (total_frames, J, 4) pose_quat_global, 16-byte aligned */
+    float* out_trans;                   /* (total_frames, 3) root_trans_offset */
+    float* out_pose_quat;               /* (total_frames, J, 4) optional, 16-byte aligned */
+    float* out_pose_aa;                 /* (total_frames, 72) optional: the zero-handed pose in SMPL joint order */
+    float* out_trans_orig;              /* (total_frames, 3) optional: the decimated trans */
+    int64_t total_frames;
+} pulse_motion_ingest_args;
+int pulse_sizeof_motion_ingest_args(void);
+int pulse_motion_ingest(const pulse_motion_ingest_args* args, pulse_stream_t s);
+
+/* ------------------------------------------------------------------------- *
  * 2b''. Evaluation metrics, accumulated per control step of an evaluation batch (IMAmpAgent.eval,
  *      phc/learning/im_amp.py:136-363).  The reference copies every env's body positions to the host on every step
  *      (HumanoidIm.post_physics_step under flags.im_eval, phc/env/tasks/humanoid_im.py:667-673), slices them per motion to

@@ -49,6 +49,15 @@ class MotionBuildArgs(Structure):
                 ("filter_w", c_float * 9)]
 
 
+class MotionIngestArgs(Structure):
+    _fields_ = [("src_pose", c_void_p), ("src_trans", c_void_p), ("src_frames", c_int64), ("num_clips", c_int32), ("num_bodies", c_int32),
+                ("clip_src_start", c_void_p), ("clip_skip", c_void_p), ("clip_mirror", c_void_p), ("clip_out_start", c_void_p),
+                ("clip_src_start_host", c_void_p), ("clip_skip_host", c_void_p), ("clip_frames_host", c_void_p), ("parent_indices_host", c_void_p),
+                ("joint_map", c_int32 * 32), ("mirror_map", c_int32 * 32), ("upright_start", c_int32), ("root_offset", c_float * 3),
+                ("out_rot", c_void_p), ("out_trans", c_void_p), ("out_pose_quat", c_void_p), ("out_pose_aa", c_void_p), ("out_trans_orig", c_void_p),
+                ("total_frames", c_int64)]
+
+
 class ImEvalArgs(Structure):
     _fields_ = [("rb", c_void_p), ("rb_env_stride", c_int64), ("ref_pos", c_void_p), ("ref_env_stride", c_int64), ("num_envs", c_int32),
                 ("num_bodies", c_int32), ("num_steps", c_void_p), ("step", c_int32), ("env_mask", c_void_p), ("ring", c_void_p),
@@ -378,6 +387,8 @@ SIGNATURES = {
     "pulse_motion_state": (c_int, [POINTER(MotionStateArgs), P]),
     "pulse_sizeof_motion_build_args": (c_int, []),
     "pulse_motion_build": (c_int, [POINTER(MotionBuildArgs), P]),
+    "pulse_sizeof_motion_ingest_args": (c_int, []),
+    "pulse_motion_ingest": (c_int, [POINTER(MotionIngestArgs), P]),
     "pulse_sizeof_im_eval_args": (c_int, []),
     "pulse_im_eval_accum": (c_int, [POINTER(ImEvalArgs), P]),
     "pulse_gae": (c_int, [P, P, P, P, c_int32, c_int32, c_int64, c_int64, c_float, c_float, P, P, P]),

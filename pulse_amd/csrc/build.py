@@ -42,6 +42,7 @@ SOURCES = [
     ("motion_state.hip", NO_CONTRACT),
     ("task_reset.hip", NO_CONTRACT),
     ("motion_build.hip", NO_CONTRACT),
+    ("motion_ingest.hip", NO_CONTRACT),
     ("eval_metrics.hip", NO_CONTRACT),
     ("rollout_ops.hip", NO_CONTRACT),
     ("gae.hip", NO_CONTRACT),

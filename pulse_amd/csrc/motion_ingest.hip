@@ -1,0 +1,168 @@
+// Raw SMPL pose sequences -> the converted motion data MotionLib stages (include/pulse_hip.h section 2b'.1), on gfx950: what
+// scripts/data_process/convert_amass_isaac.py:85-137 and convert_amass_data.py:88-141 compute clip by clip with scipy and poselib on the
+// CPU -- here one launch over every output frame of every clip.
+//
+// A 32-lane half-wave per output frame, eight frames per 256-thread workgroup.  Nothing goes through LDS and there is no barrier:
+//   lane s <-> SMPL joint s (24 of the 32 lanes): loads its three axis-angle floats (a coalesced row read), zeroes the hand columns, writes pose_aa;
+//   lane b <-> BODY b: fetches the axis-angle of SMPL joint joint_map[b] from that lane (ds_bpermute), scipy's from_rotvec in fp32,
+//     then the forward pass down the tree one level per round, each lane reading its parent's global rotation from the parent's lane;
+//     the upright factor; the local rotations back from the new globals (one more parent read); the mirrored copy reads lane
+//     mirror_map[b].  Each lane stores its own float4, so a frame's (J, 4) row is one contiguous run of 16-byte stores.
+// The lanes of a half-wave whose frame lies past the end, and lanes >= J, run along with identity rotations and store nothing: every
+// lane of the wave executes every cross-lane read.  Memory bound: 300 bytes read and 16 J + 12 (+ 16 J + 300 with the optional
+// outputs) written per frame.  Measured: profiles/motion_ingest.txt.
+// Compiled with -ffp-contract=off: fp32 in the operation order of scipy / poselib.
+#include "poselib_math.h"
+
+namespace pulse {
+
+constexpr int kMiThreads = 256;
+constexpr int kMiLanes = 32;                     // lanes per frame = PULSE_INGEST_MAX_BODIES
+constexpr int kMiSlots = kMiThreads / kMiLanes;  // frames per workgroup
+constexpr int kMiJoints = PULSE_INGEST_SMPL_JOINTS, kMiHandCol = PULSE_INGEST_SMPL_HAND_COL;
+
+// the tree, by value in the kernel arguments (from the launcher's validated host copy)
+struct MiTree { signed char parent[kMiLanes]; unsigned char depth[kMiLanes]; int max_depth; };
+
+// scipy Rotation.from_rotvec (_rotation.pyx): xyzw, Taylor series of sin(angle / 2) / angle at angle <= 1e-3, w = cos(angle / 2) as it comes
+__device__ __forceinline__ Q4 rotvec_to_quat(const float x, const float y, const float z) {
+    const float angle = sqrtf(x * x + y * y + z * z);
+    float scale;
+    if ((double)angle <= 1e-3) {
+        const float a2 = angle * angle;
+        scale = 0.5f - a2 / 48.0f + a2 * a2 / 3840.0f;
+    } else {
+        scale = sinf(angle / 2.0f) / angle;
+    }
+    return Q4{scale * x, scale * y, scale * z, cosf(angle / 2.0f)};
+}
+
+// scipy's Rotation(q): q / sqrt(q . q)
+__device__ __forceinline__ Q4 qunit_scipy(const Q4 q) {
+    const float n = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
+    return Q4{q.x / n, q.y / n, q.z / n, q.w / n};
+}
+// scipy _compose_quat: p * q, the sign kept
+__device__ __forceinline__ Q4 qcompose_scipy(const Q4 p, const Q4 q) {
+    const float cx = p.y * q.z - p.z * q.y, cy = p.z * q.x - p.x * q.z, cz = p.x * q.y - p.y * q.x;
+    Q4 r;
+    r.x = p.w * q.x + q.w * p.x + cx;
+    r.y = p.w * q.y + q.w * p.y + cy;
+    r.z = p.w * q.z + q.w * p.z + cz;
+    r.w = p.w * q.w - p.x * q.x - p.y * q.y - p.z * q.z;
+    return r;
+}
+
+__device__ __forceinline__ Q4 lane_read(const Q4 q, const int lane) {
+    return Q4{__shfl(q.x, lane, kMiLanes), __shfl(q.y, lane, kMiLanes), __shfl(q.z, lane, kMiLanes), __shfl(q.w, lane, kMiLanes)};
+}
+
+__global__ void __launch_bounds__(kMiThreads) motion_ingest_kernel(const pulse_motion_ingest_args a, const MiTree tree) {
+    const int slot = threadIdx.x / kMiLanes, b = threadIdx.x % kMiLanes;
+    const long long g = (long long)blockIdx.x * kMiSlots + slot;
+    const int J = a.num_bodies;
+    const bool frame = g < a.total_frames;                 // no early return: every lane reaches every cross-lane read
+    const bool body = frame && b < J;
+    long long src = 0;
+    int mirror = 0;
+    if (frame) {
+        const int m = clip_of(a.clip_out_start, a.num_clips, g);
+        src = a.clip_src_start[m] + (g - a.clip_out_start[m]) * a.clip_skip[m];
+        src = src < 0 ? 0 : (src > a.src_frames - 1 ? a.src_frames - 1 : src);          // a bad clip table reads a wrong frame, never out of bounds
+        mirror = a.clip_mirror ? (int)a.clip_mirror[m] : 0;
+    }
+    // lane <-> SMPL joint: pose_aa = [poses[:, :66], 0]
+    float ax = 0.0f, ay = 0.0f, az = 0.0f;
+    if (frame && b < kMiJoints) {
+        if (3 * b < kMiHandCol) {
+            const float* p = a.src_pose + src * (3 * kMiJoints) + 3 * b;
+            ax = p[0]; ay = p[1]; az = p[2];
+        }
+        if (a.out_pose_aa) { float* o = a.out_pose_aa + g * (3 * kMiJoints) + 3 * b; o[0] = ax; o[1] = ay; o[2] = az; }
+    }
+    // lane <-> body: pose_aa.reshape(-1, 24, 3)[:, smpl_2_mujoco] -> from_rotvec
+    const int jm = b < J ? a.joint_map[b] : 0;
+    const Q4 q = rotvec_to_quat(__shfl(ax, jm, kMiLanes), __shfl(ay, jm, kMiLanes), __shfl(az, jm, kMiLanes));
+    // SkeletonState.global_rotation of local rotations: transform_mul's quat_mul_norm down the tree, the root as scipy gave it
+    const int p = b < J ? tree.parent[b] : -1, ps = p < 0 ? 0 : p;
+    const int depth = b < J ? tree.depth[b] : 0;
+    Q4 G = q;
+    for (int lvl = 1; lvl <= tree.max_depth; ++lvl) {
+        const Q4 Gp = lane_read(G, ps);
+        if (depth == lvl) G = qmul_norm(Gp, q);
+    }
+    Q4 l = q;
+    if (a.upright_start) {
+        // (sRot.from_quat(g) * sRot.from_quat([0.5, 0.5, 0.5, 0.5]).inv()).as_quat(): normalise, compose, normalise
+        G = qunit_scipy(qcompose_scipy(qunit_scipy(G), Q4{-0.5f, -0.5f, -0.5f, 0.5f}));
+        // SkeletonState.local_rotation of the new globals (skeleton3d.py:444-460)
+        const Q4 Gp = lane_read(G, ps);
+        l = p < 0 ? G : qmul_norm(qconj(Gp), G);
+    }
+    if (body && a.out_pose_quat) *reinterpret_cast<float4*>(a.out_pose_quat + (g * J + b) * 4) = make_float4(l.x, l.y, l.z, l.w);
+    // the mirrored copy: pose_quat_global[:, left_to_right_index], x and z negated
+    const Q4 Gm = lane_read(G, b < J ? a.mirror_map[b] : 0);
+    if (mirror) G = Q4{-Gm.x, Gm.y, -Gm.z, Gm.w};
+    if (body) *reinterpret_cast<float4*>(a.out_rot + (g * J + b) * 4) = make_float4(G.x, G.y, G.z, G.w);
+    if (frame && b < 3) {
+        const float t = a.src_trans[3 * src + b];
+        const float o = t + a.root_offset[b];
+        a.out_trans[3 * g + b] = (mirror && b == 1) ? -o : o;
+        if (a.out_trans_orig) a.out_trans_orig[3 * g + b] = t;
+    }
+}
+
+}  // namespace pulse
+
+extern "C" int pulse_sizeof_motion_ingest_args(void) { return (int)sizeof(pulse_motion_ingest_args); }
+
+extern "C" int pulse_motion_ingest(const pulse_motion_ingest_args* args, pulse_stream_t s) {
+    using namespace pulse;
+    static_assert(PULSE_INGEST_MAX_BODIES == kMiLanes, "one lane per body");
+    PULSE_REQUIRE(args != nullptr, "pulse_motion_ingest: null args");
+    const pulse_motion_ingest_args& a = *args;
+    PULSE_REQUIRE(a.num_clips >= 0 && a.total_frames >= 0, "pulse_motion_ingest: negative clip / frame count");
+    if (a.num_clips == 0 && a.total_frames == 0) return PULSE_OK;
+    const int J = a.num_bodies;
+    static_assert(kMiJoints <= kMiLanes && kMiHandCol % 3 == 0, "one lane per SMPL joint; the hand columns start at a joint");
+    PULSE_REQUIRE(J >= 1 && J <= kMiLanes, "pulse_motion_ingest: num_bodies %d not in [1,32] (one lane of a half-wave per body)", J);
+    PULSE_REQUIRE(a.src_pose && a.src_trans, "pulse_motion_ingest: null staging pointer (src_pose / src_trans)");
+    PULSE_REQUIRE(a.src_frames >= 1, "pulse_motion_ingest: src_frames %lld: the staging buffers are empty", (long long)a.src_frames);
+    PULSE_REQUIRE(a.clip_src_start && a.clip_skip && a.clip_out_start, "pulse_motion_ingest: null per-clip table (clip_src_start / clip_skip / clip_out_start)");
+    PULSE_REQUIRE(a.clip_src_start_host && a.clip_skip_host && a.clip_frames_host,
+                  "pulse_motion_ingest: null host table (clip_src_start_host / clip_skip_host / clip_frames_host)");
+    PULSE_REQUIRE(a.parent_indices_host != nullptr, "pulse_motion_ingest: null parent_indices_host");
+    PULSE_REQUIRE(a.out_rot && a.out_trans, "pulse_motion_ingest: null output (out_rot / out_trans)");
+    MiTree tree;
+    tree.max_depth = 0;
+    for (int b = 0; b < kMiLanes; ++b) { tree.parent[b] = -1; tree.depth[b] = 0; }
+    PULSE_REQUIRE(a.parent_indices_host[0] == -1, "pulse_motion_ingest: body 0 must be the root (parent -1), got parent %d", a.parent_indices_host[0]);
+    for (int b = 1; b < J; ++b) {
+        const int p = a.parent_indices_host[b];
+        PULSE_REQUIRE(p >= 0 && p < b, "pulse_motion_ingest: parent_indices[%d] = %d: every parent must precede its child (0 <= parent < child)", b, p);
+        tree.parent[b] = (signed char)p;
+        tree.depth[b] = (unsigned char)(tree.depth[p] + 1);
+        if (tree.depth[b] > tree.max_depth) tree.max_depth = tree.depth[b];
+    }
+    for (int b = 0; b < J; ++b) {
+        PULSE_REQUIRE(a.joint_map[b] >= 0 && a.joint_map[b] < kMiJoints, "pulse_motion_ingest: joint_map[%d] = %d is no SMPL joint (0 .. %d)", b, a.joint_map[b], kMiJoints - 1);
+        PULSE_REQUIRE(a.mirror_map[b] >= 0 && a.mirror_map[b] < J, "pulse_motion_ingest: mirror_map[%d] = %d is no body (0 .. %d)", b, a.mirror_map[b], J - 1);
+    }
+    long long sum = 0;
+    for (int m = 0; m < a.num_clips; ++m) {
+        const long long f = a.clip_frames_host[m], k = a.clip_skip_host[m], s0 = a.clip_src_start_host[m];
+        PULSE_REQUIRE(f >= 1, "pulse_motion_ingest: clip %d has %lld frames: at least 1 is needed", m, f);
+        PULSE_REQUIRE(k >= 1, "pulse_motion_ingest: clip %d has skip %lld: the decimation step int(framerate / 30) must be >= 1", m, k);
+        // (f - 1) * k is not formed before it is known to fit: the last frame read is s0 + (f - 1) * k <= src_frames - 1
+        PULSE_REQUIRE(s0 >= 0 && s0 < a.src_frames && f - 1 <= (a.src_frames - 1 - s0) / k,
+                      "pulse_motion_ingest: clip %d reads %lld staged frames from %lld in steps of %lld, outside [0,%lld)", m, f, s0, k, (long long)a.src_frames);
+        sum += f;
+    }
+    PULSE_REQUIRE(sum == a.total_frames, "pulse_motion_ingest: the clips hold %lld frames but total_frames is %lld", sum, (long long)a.total_frames);
+    PULSE_REQUIRE(reinterpret_cast<uintptr_t>(a.out_rot) % 16 == 0, "pulse_motion_ingest: out_rot must be 16-byte aligned");
+    PULSE_REQUIRE(reinterpret_cast<uintptr_t>(a.out_pose_quat) % 16 == 0, "pulse_motion_ingest: out_pose_quat must be 16-byte aligned");
+    const long long blocks = (a.total_frames + kMiSlots - 1) / kMiSlots;
+    PULSE_REQUIRE(blocks <= 0x7fffffffLL, "pulse_motion_ingest: %lld frames exceed the grid", (long long)a.total_frames);
+    hipLaunchKernelGGL(motion_ingest_kernel, dim3((unsigned)blocks), dim3(kMiThreads), 0, as_stream(s), a, tree);
+    return check_launch("pulse_motion_ingest");
+}

@@ -18,6 +18,11 @@ MotionLibSMPL.load_motion_with_skeleton (motion_lib_smpl.py:101-174) does clip b
 scope: ``fix_trans_height`` (needs SMPL model files; the reference itself adds 0 when data/smpl is absent), reading pickles or
 directories of pickles from disk, ``real_traj`` quest data and the multi-process loader.
 
+A third way in, one step earlier: ``from_smpl_data`` takes raw SMPL pose sequences (axis-angle ``poses`` / ``pose_aa``, ``trans``, ``betas``,
+``gender``, ``mocap_framerate``) and converts them on the device in one launch of ``pulse_motion_ingest`` (csrc/motion_ingest.hip) -- what the
+reference's scripts/data_process/convert_amass_data.py and convert_amass_isaac.py do with smpl_sim, scipy and poselib -- into the staging
+buffers ``load_motions`` reads; ``motion_data()`` hands the converted dict back.
+
 Same names and return keys as MotionLibBase: ``get_motion_state``, ``get_root_pos_smpl``, ``get_motion_length``,
 ``get_motion_num_steps``, ``sample_motions``, ``sample_time``, ``sample_time_interval``, ``num_motions``,
 ``get_total_length``; attributes ``_motion_lengths``, ``_motion_fps``, ``_motion_dt``, ``_motion_num_frames``,
@@ -93,6 +98,50 @@ def _parse_skeleton_trees(skeleton_trees):
     return parents, lt.contiguous()
 
 
+SMPL_MIN_FRAMES = 10                     # convert_amass_data.py:101: shorter clips are skipped
+
+
+def _smpl_field(entry, *names):
+    """The first of ``names`` the raw SMPL entry carries (both spellings occur: pose_aa / poses, beta / betas), as a tensor."""
+    for n in names:
+        if n in entry:
+            return torch.as_tensor(entry[n])
+    raise KeyError(f"a raw SMPL clip needs one of {names}, got {sorted(entry)}")
+
+
+def plan_smpl_clips(data, bounds=None, mirror=False, min_length=-1, im_eval=False):
+    """What ``from_smpl_data`` will build, decided on the host: (clips, dropped keys).  Every clip: key, source (the key of its raw data), raw_frames,
+    skip = int(mocap_framerate / 30), frames = len(range(0, raw, skip))[:bound], mirror.  Clips left with fewer than SMPL_MIN_FRAMES frames are
+    dropped (convert_amass_data.py:88-102); a mirrored copy follows its original under key + "_1"; then ``filter_motion_data``'s selection
+    and order (min_length, im_eval) over the converted lengths."""
+    clips, dropped = [], []
+    for key, entry in data.items():
+        pose, trans = _smpl_field(entry, "pose_aa", "poses"), torch.as_tensor(entry["trans"])
+        if pose.dim() != 2 or pose.shape[1] < 72 or tuple(trans.shape) != (pose.shape[0], 3):
+            raise ValueError(f"clip {key!r}: pose_aa / poses (F, >= 72) and trans (F, 3) expected, got {tuple(pose.shape)} and {tuple(trans.shape)}")
+        _smpl_field(entry, "beta", "betas")
+        rate = float(torch.as_tensor(entry["mocap_framerate"]).item()) if "mocap_framerate" in entry else 30.0
+        if not math.isfinite(rate) or rate < 30:
+            raise ValueError(f"clip {key!r}: mocap_framerate {rate} is not a finite rate of at least 30 (the decimation step int(framerate / 30) would be 0)")
+        skip = int(rate / 30)
+        n = -(-pose.shape[0] // skip)
+        bound = int((bounds or {}).get(key, 0))
+        if bound < 0:
+            raise ValueError(f"clip {key!r}: bound {bound} is negative")
+        n = min(n, bound) if bound else n
+        if n < SMPL_MIN_FRAMES:
+            dropped.append(key)
+            continue
+        for m in range(2 if mirror else 1):
+            clips.append({"key": f"{key}_1" if m else key, "source": key, "raw_frames": int(pose.shape[0]), "skip": skip, "frames": n, "mirror": bool(m)})
+    keys = [c["key"] for c in clips]
+    if len(set(keys)) != len(keys):
+        raise ValueError("from_smpl_data: a mirrored copy's key (key + '_1') collides with another clip's key")
+    order = filter_motion_data({c["key"]: {"pose_quat_global": range(c["frames"])} for c in clips}, min_length, im_eval)
+    by_key = {c["key"]: c for c in clips}
+    return [by_key[k] for k in order], dropped
+
+
 class MotionLib:
     FIELDS = ("gts", "grs", "lrs", "gvs", "gavs", "dvs")
 
@@ -149,6 +198,7 @@ class MotionLib:
         self.motion_bodies = self._shape_rows(tables, "motion_bodies", 17)
         self.motion_limb_weights = self._shape_rows(tables, "motion_limb_weights", 10)
         self._src = None                                   # staged raw clips: only a library built by from_motion_data reloads
+        self._smpl = None
         self._generation = 0
 
     def _shape_rows(self, tables, key, width):
@@ -188,13 +238,19 @@ class MotionLib:
             if r.shape[0] < 2:
                 raise ValueError(f"clip {k!r} has {r.shape[0]} frame(s): at least 2 are needed (np.gradient raises below 2)")
         frames = torch.tensor([r.shape[0] for r in rot], dtype=torch.int64)
-        self._src = {
+        src = {
             "rot": torch.cat([r.to(torch.float32) for r in rot]).contiguous().to(dev),
             "trans": torch.cat([torch.as_tensor(data[k]["root_trans_offset"]).to(torch.float32) for k in keys]).contiguous().to(dev),
             "start": torch.cumsum(frames, 0) - frames, "frames": frames,
             "fps": torch.tensor([float(data[k].get("fps", 30)) for k in keys], dtype=torch.float64),             # curr_file.get("fps", 30), motion_lib_smpl.py:150
             "has_beta": torch.tensor(["beta" in data[k] for k in keys]),
         }
+        return self._finish_staged(src, j, im_eval, generator, skeleton_trees, gender_betas, limb_weights)
+
+    def _finish_staged(self, src, j, im_eval, generator, skeleton_trees, gender_betas, limb_weights):
+        """The rest of a library over staged clips (``_src``), however they were staged: layout, sampling weights, a first ``load_motions``."""
+        dev = self._device
+        self._src = src
         self.num_bodies, self.num_dof = j, (j - 1) * 3
         self.offsets, self.frame_stride, _ = self.record_layout(j)
         self._im_eval, self._generator = bool(im_eval), generator
@@ -205,6 +261,89 @@ class MotionLib:
         self._last_load = {"skeleton_trees": None, "gender_betas": None, "limb_weights": None}
         self.load_motions(skeleton_trees, gender_betas, limb_weights)
         return self
+
+    @classmethod
+    def from_smpl_data(cls, data, skeleton_trees, *, upright_start=True, mirror=False, bounds=None, root_offset=None, gender_betas=None,
+                       limb_weights=None, device="cuda:0", min_length=-1, im_eval=False, generator=None):
+        """A library over RAW SMPL pose sequences, as motion data sets ship them: ``data`` maps key -> {pose_aa | poses (F, >= 72) axis-angle in SMPL
+        joint order, trans (F, 3), beta | betas, gender, [mocap_framerate]}, numpy or torch, fp32 or fp64.  What the reference's
+        scripts/data_process/convert_amass_data.py:88-141 and convert_amass_isaac.py:85-137 do on the CPU first happens here in ONE launch of
+        ``pulse_motion_ingest`` (csrc/motion_ingest.hip) over every frame of every clip, straight into the staging buffers ``load_motions`` reads;
+        everything after that is ``from_motion_data``'s (the remaining arguments are the same).
+
+          * a clip is decimated by skip = int(mocap_framerate / 30) and then labelled 30 fps WHATEVER framerate / skip is -- 100 Hz data becomes
+            33.3 fps data called 30, as in the reference;
+          * a clip WITHOUT mocap_framerate is taken as 30 Hz data and kept whole, as convert_amass_isaac.py takes its input; convert_amass_data.py:81-82
+            skips such a clip instead;
+          * ``bounds``: key -> number of decimated frames to keep (the occlusion file's ``idxes[0]``); a clip left with fewer than 10 frames is
+            dropped (convert_amass_data.py:101) with a warning that names it;
+          * ``mirror``: every clip is followed by its left-right mirrored copy under ``key + "_1"`` -- the spelling convert_amass_isaac.py:118 has
+            commented out; its live line (:119) reuses the key, so that the copy overwrites the original;
+          * ``root_offset``: three floats added to ``trans`` (default: local_translation[0] of skeleton slot 0, :114);
+          * ``upright_start=False`` leaves the (0.5, 0.5, 0.5, 0.5)^-1 factor out; the reference has no runnable counterpart (both scripts
+            hard-code True).
+        The humanoid is SMPL (24 bodies): SMPL-X / SMPL-H sources, reading .npz trees from disk and fix_trans_height are out of scope."""
+        import warnings
+        from .. import kernels, synthetic
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("MotionLib lives in HBM (pulse_amd has no CPU path)")
+        parents, lt = _parse_skeleton_trees(skeleton_trees)
+        clips, dropped = plan_smpl_clips(data, bounds, mirror, min_length, im_eval)
+        if dropped:
+            warnings.warn(f"from_smpl_data: dropped {len(dropped)} clip(s) left with fewer than {SMPL_MIN_FRAMES} frames: {', '.join(map(str, dropped))}")
+        if not clips:
+            raise ValueError("from_smpl_data: no clip left" + (f" with at least {min_length} frames" if min_length != -1 else ""))
+        joint_map = synthetic.smpl_joint_map()
+        if len(parents) != len(joint_map):
+            raise ValueError(f"from_smpl_data: the skeleton trees have {len(parents)} bodies, the SMPL humanoid {len(joint_map)}")
+        self = cls.__new__(cls)
+        self._device = dev
+        self._motion_data_keys = [c["key"] for c in clips]
+        self._num_unique_motions = len(clips)
+        # the raw arrays, staged once as fp32: one copy per source clip (a mirrored copy reads its original's rows)
+        sources, src_start, at = {}, [], 0
+        for c in clips:
+            if c["source"] not in sources:
+                sources[c["source"]] = at
+                at += c["raw_frames"]
+            src_start.append(sources[c["source"]])
+        pose = torch.cat([_smpl_field(data[k], "pose_aa", "poses")[:, :72].to(torch.float32) for k in sources]).contiguous().to(dev)
+        trans = torch.cat([torch.as_tensor(data[k]["trans"]).to(torch.float32) for k in sources]).contiguous().to(dev)
+        frames = torch.tensor([c["frames"] for c in clips], dtype=torch.int64)
+        total, j = int(frames.sum()), len(parents)
+        src = {"rot": torch.empty(total, j, 4, dtype=torch.float32, device=dev), "trans": torch.empty(total, 3, dtype=torch.float32, device=dev),
+               "start": torch.cumsum(frames, 0) - frames, "frames": frames, "fps": torch.full((len(clips),), 30.0, dtype=torch.float64),
+               "has_beta": torch.ones(len(clips), dtype=torch.bool)}              # the converted file always carries a (zeroed) beta
+        self._smpl = {"pose_quat": torch.empty(total, j, 4, dtype=torch.float32, device=dev), "pose_aa": torch.empty(total, 72, dtype=torch.float32, device=dev),
+                      "trans_orig": torch.empty(total, 3, dtype=torch.float32, device=dev),
+                      # beta: zeros of the input's length (a (1, n) row counts as n, convert_amass_isaac.py:62-64, 96)
+                      "beta_len": [int(_smpl_field(data[c["source"]], "beta", "betas").shape[-1]) for c in clips]}
+        off = lt[0, 0].tolist() if root_offset is None else [float(v) for v in root_offset]
+        kernels.motion_ingest(src["rot"], src["trans"], src_pose=pose, src_trans=trans, clip_src_start=torch.tensor(src_start, dtype=torch.int64),
+                              clip_skip=torch.tensor([c["skip"] for c in clips], dtype=torch.int64), clip_frames=frames, parents=parents,
+                              joint_map=joint_map, mirror_map=synthetic.mirror_body_map(), clip_mirror=torch.tensor([c["mirror"] for c in clips]),
+                              upright_start=upright_start, root_offset=off, out_pose_quat=self._smpl["pose_quat"], out_pose_aa=self._smpl["pose_aa"],
+                              out_trans_orig=self._smpl["trans_orig"])
+        return self._finish_staged(src, j, im_eval, generator, skeleton_trees, gender_betas, limb_weights)
+
+    def motion_data(self):
+        """The converted motion data of a library built by ``from_smpl_data``, in the layout the reference's scripts dump (convert_amass_isaac.py:129-138)
+        as CPU numpy arrays: key -> {pose_quat_global, pose_quat, trans_orig, root_trans_offset, beta (zeros of the input's length), gender "neutral",
+        pose_aa, fps}.  A mirrored clip carries the unmirrored pose_quat / pose_aa / trans_orig, as the reference leaves them.
+        ``from_motion_data(lib.motion_data(), ...)`` stages the same bits."""
+        import numpy as np
+        if self._src is None or getattr(self, "_smpl", None) is None:
+            raise ValueError("motion_data: only a library built by from_smpl_data holds converted motion data")
+        host = {k: v.cpu().numpy() for k, v in (("rot", self._src["rot"]), ("trans", self._src["trans"]), ("pose_quat", self._smpl["pose_quat"]),
+                                                 ("pose_aa", self._smpl["pose_aa"]), ("trans_orig", self._smpl["trans_orig"]))}
+        out = {}
+        for i, key in enumerate(self._motion_data_keys):
+            s = slice(int(self._src["start"][i]), int(self._src["start"][i]) + int(self._src["frames"][i]))
+            out[key] = {"pose_quat_global": host["rot"][s].copy(), "pose_quat": host["pose_quat"][s].copy(), "trans_orig": host["trans_orig"][s].copy(),
+                        "root_trans_offset": host["trans"][s].copy(), "beta": np.zeros(self._smpl["beta_len"][i]), "gender": "neutral",
+                        "pose_aa": host["pose_aa"][s].copy(), "fps": 30}
+        return out
 
     def eval_twin(self):
         """The evaluation library of this one (humanoid_im.py:336-339: the same motion file under ``im_eval``): the same clips numbered longest

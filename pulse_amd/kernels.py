@@ -457,6 +457,60 @@ def motion_build(frames, offsets, *, src_rot, src_trans, clip_src_start, clip_ou
     return frames
 
 
+INGEST_MAX_BODIES = 32
+
+
+def motion_ingest(out_rot, out_trans, *, src_pose, src_trans, clip_src_start, clip_skip, clip_frames, parents, joint_map, mirror_map=None,
+                  clip_mirror=None, upright_start=True, root_offset=(0.0, 0.0, 0.0), out_pose_quat=None, out_pose_aa=None,
+                  out_trans_orig=None):
+    """pulse_motion_ingest: raw SMPL pose rows -> ``out_rot`` (T, J, 4) pose_quat_global and ``out_trans`` (T, 3) root_trans_offset, one launch
+    (include/pulse_hip.h section 2b'.1).  Device tensors: ``src_pose`` (S, 72) / ``src_trans`` (S, 3) fp32 and the outputs.  Host: the
+    per-clip tables ``clip_src_start`` / ``clip_skip`` / ``clip_frames`` (M) int64 CPU tensors and ``clip_mirror`` (M) bool / uint8, optional (the
+    launcher validates them; their device copies are made here), ``parents`` / ``joint_map`` / ``mirror_map`` sequences of J ints."""
+    a = _lib.MotionIngestArgs()
+    for name, t in (("src_pose", src_pose), ("src_trans", src_trans), ("out_rot", out_rot), ("out_trans", out_trans), ("out_pose_quat", out_pose_quat),
+                    ("out_pose_aa", out_pose_aa), ("out_trans_orig", out_trans_orig)):
+        ptr = _p(t, name, torch.float32)
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name}: contiguous tensor expected, got strides {tuple(t.stride())}")
+        setattr(a, name, ptr)
+    for name, t in (("clip_src_start", clip_src_start), ("clip_skip", clip_skip), ("clip_frames", clip_frames)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cpu" or t.dtype != torch.int64 or not t.is_contiguous() or t.dim() != 1:
+            raise TypeError(f"{name}: contiguous (M) int64 CPU tensor expected (the launcher validates the clip tables on the host)")
+    m, j = clip_frames.numel(), len(parents)
+    if j > INGEST_MAX_BODIES:
+        raise ValueError(f"motion_ingest: num_bodies {j} > {INGEST_MAX_BODIES} (one lane of a half-wave per body)")
+    if clip_src_start.numel() != m or clip_skip.numel() != m:
+        raise ValueError(f"clip_src_start / clip_skip: expected shape ({m},)")
+    if src_pose.dim() != 2 or src_pose.shape[1] != 72 or tuple(src_trans.shape) != (src_pose.shape[0], 3):
+        raise ValueError(f"src_pose / src_trans: expected (S, 72) and (S, 3), got {tuple(src_pose.shape)} and {tuple(src_trans.shape)}")
+    total, dev = int(clip_frames.sum()), out_rot.device
+    for name, t, shape in (("out_rot", out_rot, (total, j, 4)), ("out_trans", out_trans, (total, 3)), ("out_pose_quat", out_pose_quat, (total, j, 4)),
+                           ("out_pose_aa", out_pose_aa, (total, 72)), ("out_trans_orig", out_trans_orig, (total, 3))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+    if len(joint_map) != j or (mirror_map is not None and len(mirror_map) != j):
+        raise ValueError(f"joint_map / mirror_map: {j} entries expected, one per body")
+    out_start = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(clip_frames, 0)])
+    keep = [clip_src_start.to(dev), clip_skip.to(dev), out_start.to(dev)]
+    a.clip_src_start, a.clip_skip, a.clip_out_start = (t.data_ptr() for t in keep)
+    if clip_mirror is not None:
+        if clip_mirror.numel() != m:
+            raise ValueError(f"clip_mirror: expected shape ({m},)")
+        keep.append(clip_mirror.to(torch.uint8).contiguous().to(dev))
+        a.clip_mirror = keep[-1].data_ptr()
+    par = (ctypes.c_int32 * j)(*[int(p) for p in parents])
+    a.clip_src_start_host, a.clip_skip_host, a.clip_frames_host = clip_src_start.data_ptr(), clip_skip.data_ptr(), clip_frames.data_ptr()
+    a.parent_indices_host = ctypes.cast(par, ctypes.c_void_p)
+    a.src_frames, a.num_clips, a.num_bodies = src_pose.shape[0], m, j
+    a.joint_map[:j] = [int(v) for v in joint_map]
+    a.mirror_map[:j] = [int(v) for v in mirror_map] if mirror_map is not None else list(range(j))
+    a.upright_start, a.total_frames = int(bool(upright_start)), total
+    a.root_offset[:] = [float(v) for v in root_offset]
+    _launch("pulse_motion_ingest", ctypes.byref(a))
+    return out_rot, out_trans
+
+
 # --------------------------------------------------------------------------- #
 # planar ("x3p") fp32-grade GEMM: operands kept pre-split in HBM as three bf16 planes (include/pulse_hip.h section 4b)
 # --------------------------------------------------------------------------- #

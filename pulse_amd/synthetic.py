@@ -184,6 +184,25 @@ SKELETONS = {"smpl": _skeleton(SMPL_BODY_NAMES, SMPL_PARENTS, ("L_Hand", "R_Hand
              "smplx": _skeleton(SMPLX_BODY_NAMES, SMPLX_PARENTS, ("L_Toe", "R_Toe"), _ANKLES_TOES)}       # humanoid.py:404-405
 SKELETONS["smplh"] = SKELETONS["smplx"]                                                                  # humanoid.py:376: the same 52 bodies
 
+# SMPL's own joint order under the humanoid's body names: the order of a raw SMPL pose row (F, 72).  The reference takes the list from
+# smpl_sim (SMPL_BONE_ORDER_NAMES, convert_amass_data.py:16, 104); it is the public SMPL kinematic tree.
+SMPL_BONE_ORDER_NAMES = ['Pelvis', 'L_Hip', 'R_Hip', 'Torso', 'L_Knee', 'R_Knee', 'Spine', 'L_Ankle', 'R_Ankle', 'Chest', 'L_Toe', 'R_Toe',
+                         'Neck', 'L_Thorax', 'R_Thorax', 'Head', 'L_Shoulder', 'R_Shoulder', 'L_Elbow', 'R_Elbow', 'L_Wrist', 'R_Wrist',
+                         'L_Hand', 'R_Hand']
+
+
+def smpl_joint_map(body_names=None):
+    """smpl_2_mujoco (convert_amass_data.py:104): for every body of the humanoid, in body order, the SMPL joint it takes its rotation from."""
+    names = SMPL_BODY_NAMES if body_names is None else body_names
+    return [SMPL_BONE_ORDER_NAMES.index(q) for q in names if q in SMPL_BONE_ORDER_NAMES]
+
+
+def mirror_body_map(body_names=None):
+    """left_to_right_index (convert_amass_isaac.py:121): every L_ body takes its R_ twin's place and the other way round."""
+    names = list(SMPL_BODY_NAMES if body_names is None else body_names)
+    swap = {"L_": "R_", "R_": "L_"}
+    return [names.index(swap[n[:2]] + n[2:]) if n[:2] in swap else i for i, n in enumerate(names)]
+
 
 def _exp_map_to_quat_xyzw(e):
     ang = e.norm(dim=-1, keepdim=True)
@@ -319,6 +338,38 @@ def synthetic_motion_data(g, num_clips, humanoid="smpl", frames=None, min_frames
     lt = offsets[None] * (1.0 + 0.1 * _randn(g, slots, 1, 1))
     lt[:, 0] = 0.0
     return data, (list(parents), lt.contiguous())
+
+
+def synthetic_smpl_data(g, num_clips, frames=None, min_frames=45, max_frames=180, framerate=30, num_slots=None):
+    """Raw SMPL motion as data sets ship it, and skeleton trees to load it with: ``(data, (parents, local_translation (num_slots, 24, 3)))``.
+    ``data``: key -> {poses (F, 72) float32 numpy axis-angle in SMPL joint order (hands included), trans (F, 3) float32 numpy, betas (16),
+    gender, mocap_framerate}: two sinusoids per joint axis, a drifting and swaying root.  ``frames``: the RAW lengths (default: drawn in
+    [min_frames, max_frames] x int(framerate / 30)); ``framerate``: one value or one per clip.  For ``MotionLib.from_smpl_data``."""
+    import numpy as np
+    m = num_clips
+    rates = [framerate] * m if not isinstance(framerate, (list, tuple)) else list(framerate)
+    if frames is None:
+        frames = (torch.randint(min_frames, max_frames + 1, (m,), generator=g, dtype=torch.int64) * torch.tensor([max(1, int(r / 30)) for r in rates])).tolist()
+    if len(frames) != m or len(rates) != m:
+        raise ValueError(f"synthetic_smpl_data: {m} clips need {m} lengths and framerates")
+    data = {}
+    for c in range(m):
+        f = int(frames[c])
+        t = (torch.arange(f, dtype=torch.float32) / float(rates[c]))[:, None, None]
+        amp = 0.35 * _rand(g, 24, 3, 2)
+        amp[0] *= 0.3
+        frq = 0.3 + 1.7 * _rand(g, 24, 3, 2)
+        pha = 6.2831853 * _rand(g, 24, 3, 2)
+        e = (amp * torch.sin(6.2831853 * frq * t[..., None] + pha)).sum(-1)                     # (F, 24, 3) joint axis-angles
+        e[:, 0, 2] += 6.2831853 * _rand(g, 1) + 0.8 * _randn(g, 1) * t[:, 0, 0]
+        root = (0.6 * _randn(g, 3) * torch.tensor([1.0, 1.0, 0.0])) * t[:, 0] + 0.05 * _randn(g, 3) * torch.sin(3.0 * t[:, 0]) + torch.tensor([0.0, 0.0, 0.9])
+        data[f"clip_{c:04d}"] = {"poses": e.reshape(f, 72).contiguous().numpy(), "trans": root.contiguous().numpy(), "betas": _randn(g, 16).numpy(),
+                                 "gender": np.array("neutral"), "mocap_framerate": np.array(float(rates[c]))}
+    slots = m if num_slots is None else num_slots
+    offsets = 0.08 + 0.3 * _rand(g, 24, 3) * torch.tensor([0.4, 0.4, 1.0])
+    lt = offsets[None] * (1.0 + 0.1 * _randn(g, slots, 1, 1))
+    lt[:, 0] = 0.0
+    return data, (list(SMPL_PARENTS), lt.contiguous())
 
 
 # --------------------------------------------------------------------------- #
