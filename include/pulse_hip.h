@@ -545,6 +545,65 @@ int pulse_sizeof_motion_ingest_args(void);
 int pulse_motion_ingest(const pulse_motion_ingest_args* args, pulse_stream_t s);
 
 /* ------------------------------------------------------------------------- *
+ * 2b'.2. A recorded rollout -> motion clips and SMPL pose sequences: the way back out of section 2b'.1.  What the reference does frame by
+ *      frame on the CPU -- HumanoidIm.render's conversion of the simulator's body rotations into SMPL pose_aa / trans
+ *      (phc/env/tasks/humanoid_im.py:217-257) and Humanoid._write_states_to_file's per-episode dump (phc/env/tasks/humanoid.py:439-491) --
+ *      for every output frame of every segment of a recording in one launch (a 32-lane half-wave per frame, lane = body).
+ *      Output frame g of segment m is read IN PLACE from rb[seg_t0[m] + (g - seg_out_start[m]), seg_env[m]] (no staging copy).
+ *        out_rot        the simulator's global body rotations, copied bit for bit: pose_quat_global of the converted data (the inverse of
+ *                       convert_amass_isaac.py:107-112 is the identity on them);
+ *        out_trans      the root position, copied bit for bit: root_trans_offset (humanoid_im.py:221);
+ *        out_pose_quat  upright_start != 0: local rotations in the SMPL frame (:234-236): every global rotation normalised, composed with
+ *                       (0.5, 0.5, 0.5, 0.5) on the right, normalised (scipy's from_quat, __mul__; the sign is kept), then
+ *                       SkeletonState.local_rotation (skeleton3d.py:444-460): root = global, body b = quat_mul_norm(quat_inverse(G[parent]), G[b]).
+ *                       upright_start == 0: the reference forms no such field; WRITTEN HERE: [root quat, exp_map_to_quat(dof_pos)], the
+ *                       rotations its pose_aa of that branch stands for (needs dof_pos);
+ *        out_pose_aa    (F, 3 J) in SMPL joint order: joint s takes body b with joint_map[b] == s (mujoco_2_smpl, :164, 238).
+ *                       upright_start != 0: scipy's Rotation.from_quat(pose_quat).as_rotvec() (:237): normalise; negate the quaternion when
+ *                       w < 0; angle = 2 atan2(|xyz|, w); xyz * (2 + angle^2 / 12 + 7 angle^4 / 2880) at angle <= 1e-3, xyz * angle / sin(angle / 2)
+ *                       above.  upright_start == 0: [quat_to_exp_map(root_rot), dof_pos] (:240-257; torch_utils.py:57-97), needs dof_pos;
+ *        out_trans_orig root position - root_offset (:231-232, 255-256);
+ *        out_body_quat  the dump's body_quat = [root quat, exp_map_to_quat(dof_pos)] (humanoid.py:472-476; torch_utils.py:148-172), and
+ *        out_dof_pos    the dump's dof_pos copy; both need dof_pos.
+ *      fp32 throughout, in the operation order of scipy / poselib / torch_utils (precise sinf / cosf / atan2f / acosf / sqrtf).
+ *      Nothing is launched unless every argument passes.
+ * ------------------------------------------------------------------------- */
+#define PULSE_EXPORT_MAX_BODIES 32
+typedef struct pulse_motion_export_args {
+    /* the recording, device, read in place */
+    const float* rb;                    /* (T, N, J, 13) rigid-body states: position 0:3, rotation xyzw 3:7; element strides below, inner stride 1 */
+    int64_t rb_stride_t, rb_stride_n, rb_stride_b;
+    const float* dof_pos;               /* (T, N, 3 (J - 1)) optional; inner stride 1 */
+    int64_t dof_stride_t, dof_stride_n;
+    int64_t num_steps;                  /* T */
+    int32_t num_envs;                   /* N */
+    int32_t num_bodies;                 /* J in [1, 32] */
+    int32_t num_segments;               /* M */
+    int32_t upright_start;
+    const int64_t* seg_env;             /* (M) device: env of the segment */
+    const int64_t* seg_t0;              /* (M) device: its first step */
+    const int64_t* seg_out_start;       /* (M + 1) device: its first output frame; [M] = total_frames */
+    const int64_t* seg_env_host;        /* (M) HOST copies: validated before anything is launched (frames >= 1, every segment inside */
+    const int64_t* seg_t0_host;         /*     [0, T) x [0, N), sum of frames = total_frames) */
+    const int64_t* seg_frames_host;
+    const int32_t* parent_indices_host; /* (J) HOST: -1 for body 0, parent < child */
+    int32_t joint_map[PULSE_EXPORT_MAX_BODIES];   /* body -> SMPL joint: a permutation of 0 .. J-1, first J used */
+    float root_offset[3];               /* subtracted from the root position (the skeleton's local_translation[0]) */
+    int32_t reserved;
+    /* outputs, device */
+    float* out_rot;                     /* (total_frames, J, 4), 16-byte aligned */
+    float* out_trans;                   /* (total_frames, 3) */
+    float* out_pose_quat;               /* (total_frames, J, 4) optional, 16-byte aligned */
+    float* out_pose_aa;                 /* (total_frames, 3 J) optional */
+    float* out_trans_orig;              /* (total_frames, 3) optional */
+    float* out_body_quat;               /* (total_frames, J, 4) optional, 16-byte aligned */
+    float* out_dof_pos;                 /* (total_frames, 3 (J - 1)) optional */
+    int64_t total_frames;
+} pulse_motion_export_args;
+int pulse_sizeof_motion_export_args(void);
+int pulse_motion_export(const pulse_motion_export_args* args, pulse_stream_t s);
+
+/* ------------------------------------------------------------------------- *
  * 2b''. Evaluation metrics, accumulated per control step of an evaluation batch (IMAmpAgent.eval,
  *      phc/learning/im_amp.py:136-363).  The reference copies every env's body positions to the host on every step
  *      (HumanoidIm.post_physics_step under flags.im_eval, phc/env/tasks/humanoid_im.py:667-673), slices them per motion to

@@ -58,6 +58,17 @@ class MotionIngestArgs(Structure):
                 ("total_frames", c_int64)]
 
 
+class MotionExportArgs(Structure):
+    _fields_ = [("rb", c_void_p), ("rb_stride_t", c_int64), ("rb_stride_n", c_int64), ("rb_stride_b", c_int64),
+                ("dof_pos", c_void_p), ("dof_stride_t", c_int64), ("dof_stride_n", c_int64), ("num_steps", c_int64),
+                ("num_envs", c_int32), ("num_bodies", c_int32), ("num_segments", c_int32), ("upright_start", c_int32),
+                ("seg_env", c_void_p), ("seg_t0", c_void_p), ("seg_out_start", c_void_p),
+                ("seg_env_host", c_void_p), ("seg_t0_host", c_void_p), ("seg_frames_host", c_void_p), ("parent_indices_host", c_void_p),
+                ("joint_map", c_int32 * 32), ("root_offset", c_float * 3), ("reserved", c_int32),
+                ("out_rot", c_void_p), ("out_trans", c_void_p), ("out_pose_quat", c_void_p), ("out_pose_aa", c_void_p), ("out_trans_orig", c_void_p),
+                ("out_body_quat", c_void_p), ("out_dof_pos", c_void_p), ("total_frames", c_int64)]
+
+
 class ImEvalArgs(Structure):
     _fields_ = [("rb", c_void_p), ("rb_env_stride", c_int64), ("ref_pos", c_void_p), ("ref_env_stride", c_int64), ("num_envs", c_int32),
                 ("num_bodies", c_int32), ("num_steps", c_void_p), ("step", c_int32), ("env_mask", c_void_p), ("ring", c_void_p),
@@ -389,6 +400,8 @@ SIGNATURES = {
     "pulse_motion_build": (c_int, [POINTER(MotionBuildArgs), P]),
     "pulse_sizeof_motion_ingest_args": (c_int, []),
     "pulse_motion_ingest": (c_int, [POINTER(MotionIngestArgs), P]),
+    "pulse_sizeof_motion_export_args": (c_int, []),
+    "pulse_motion_export": (c_int, [POINTER(MotionExportArgs), P]),
     "pulse_sizeof_im_eval_args": (c_int, []),
     "pulse_im_eval_accum": (c_int, [POINTER(ImEvalArgs), P]),
     "pulse_gae": (c_int, [P, P, P, P, c_int32, c_int32, c_int64, c_int64, c_float, c_float, P, P, P]),

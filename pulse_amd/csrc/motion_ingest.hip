@@ -37,26 +37,6 @@ __device__ __forceinline__ Q4 rotvec_to_quat(const float x, const float y, const
     return Q4{scale * x, scale * y, scale * z, cosf(angle / 2.0f)};
 }
 
-// scipy's Rotation(q): q / sqrt(q . q)
-__device__ __forceinline__ Q4 qunit_scipy(const Q4 q) {
-    const float n = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
-    return Q4{q.x / n, q.y / n, q.z / n, q.w / n};
-}
-// scipy _compose_quat: p * q, the sign kept
-__device__ __forceinline__ Q4 qcompose_scipy(const Q4 p, const Q4 q) {
-    const float cx = p.y * q.z - p.z * q.y, cy = p.z * q.x - p.x * q.z, cz = p.x * q.y - p.y * q.x;
-    Q4 r;
-    r.x = p.w * q.x + q.w * p.x + cx;
-    r.y = p.w * q.y + q.w * p.y + cy;
-    r.z = p.w * q.z + q.w * p.z + cz;
-    r.w = p.w * q.w - p.x * q.x - p.y * q.y - p.z * q.z;
-    return r;
-}
-
-__device__ __forceinline__ Q4 lane_read(const Q4 q, const int lane) {
-    return Q4{__shfl(q.x, lane, kMiLanes), __shfl(q.y, lane, kMiLanes), __shfl(q.z, lane, kMiLanes), __shfl(q.w, lane, kMiLanes)};
-}
-
 __global__ void __launch_bounds__(kMiThreads) motion_ingest_kernel(const pulse_motion_ingest_args a, const MiTree tree) {
     const int slot = threadIdx.x / kMiLanes, b = threadIdx.x % kMiLanes;
     const long long g = (long long)blockIdx.x * kMiSlots + slot;

@@ -511,6 +511,62 @@ def motion_ingest(out_rot, out_trans, *, src_pose, src_trans, clip_src_start, cl
     return out_rot, out_trans
 
 
+EXPORT_MAX_BODIES = 32
+
+
+def motion_export(out_rot, out_trans, *, rb, seg_env, seg_t0, seg_frames, parents, joint_map, dof_pos=None, upright_start=True,
+                  root_offset=(0.0, 0.0, 0.0), out_pose_quat=None, out_pose_aa=None, out_trans_orig=None, out_body_quat=None, out_dof_pos=None):
+    """pulse_motion_export: a recording ``rb`` (T, N, J, 13) -> ``out_rot`` (F, J, 4) pose_quat_global and ``out_trans`` (F, 3) root_trans_offset of
+    every frame of every segment, one launch (include/pulse_hip.h section 2b'.2).  ``rb`` and ``dof_pos`` (T, N, 3 (J - 1)) are read in place:
+    any view with unit inner stride.  Host: the per-segment tables ``seg_env`` / ``seg_t0`` / ``seg_frames`` (M) int64 CPU tensors (the launcher
+    validates them; their device copies are made here), ``parents`` / ``joint_map`` sequences of J ints.  The optional outputs are contiguous."""
+    a = _lib.MotionExportArgs()
+    for name, t in (("out_rot", out_rot), ("out_trans", out_trans), ("out_pose_quat", out_pose_quat), ("out_pose_aa", out_pose_aa),
+                    ("out_trans_orig", out_trans_orig), ("out_body_quat", out_body_quat), ("out_dof_pos", out_dof_pos)):
+        ptr = _p(t, name, torch.float32)
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name}: contiguous tensor expected, got strides {tuple(t.stride())}")
+        setattr(a, name, ptr)
+    for name, t in (("seg_env", seg_env), ("seg_t0", seg_t0), ("seg_frames", seg_frames)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cpu" or t.dtype != torch.int64 or not t.is_contiguous() or t.dim() != 1:
+            raise TypeError(f"{name}: contiguous (M) int64 CPU tensor expected (the launcher validates the segment tables on the host)")
+    m, j = seg_frames.numel(), len(parents)
+    if j > EXPORT_MAX_BODIES:
+        raise ValueError(f"motion_export: num_bodies {j} > {EXPORT_MAX_BODIES} (one lane of a half-wave per body)")
+    if seg_env.numel() != m or seg_t0.numel() != m:
+        raise ValueError(f"seg_env / seg_t0: expected shape ({m},)")
+    a.rb = _p(rb, "rb", torch.float32)
+    if rb.dim() != 4 or tuple(rb.shape[2:]) != (j, 13):
+        raise ValueError(f"rb: expected (T, N, {j}, 13), got {tuple(rb.shape)}")
+    steps, envs = rb.shape[0], rb.shape[1]
+    a.rb_stride_t, a.rb_stride_n, a.rb_stride_b = rb.stride(0), rb.stride(1), rb.stride(2)
+    if dof_pos is not None:
+        a.dof_pos = _p(dof_pos, "dof_pos", torch.float32)
+        if tuple(dof_pos.shape) != (steps, envs, 3 * (j - 1)):
+            raise ValueError(f"dof_pos: expected {(steps, envs, 3 * (j - 1))}, got {tuple(dof_pos.shape)}")
+        a.dof_stride_t, a.dof_stride_n = dof_pos.stride(0), dof_pos.stride(1)
+    total, dev = int(seg_frames.sum()), out_rot.device
+    for name, t, shape in (("out_rot", out_rot, (total, j, 4)), ("out_trans", out_trans, (total, 3)), ("out_pose_quat", out_pose_quat, (total, j, 4)),
+                           ("out_pose_aa", out_pose_aa, (total, 3 * j)), ("out_trans_orig", out_trans_orig, (total, 3)),
+                           ("out_body_quat", out_body_quat, (total, j, 4)), ("out_dof_pos", out_dof_pos, (total, 3 * (j - 1)))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+    if len(joint_map) != j:
+        raise ValueError(f"joint_map: {j} entries expected, one per body")
+    out_start = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(seg_frames, 0)])
+    keep = [seg_env.to(dev), seg_t0.to(dev), out_start.to(dev)]
+    a.seg_env, a.seg_t0, a.seg_out_start = (t.data_ptr() for t in keep)
+    par = (ctypes.c_int32 * j)(*[int(p) for p in parents])
+    a.seg_env_host, a.seg_t0_host, a.seg_frames_host = seg_env.data_ptr(), seg_t0.data_ptr(), seg_frames.data_ptr()
+    a.parent_indices_host = ctypes.cast(par, ctypes.c_void_p)
+    a.num_steps, a.num_envs, a.num_bodies, a.num_segments = steps, envs, j, m
+    a.joint_map[:j] = [int(v) for v in joint_map]
+    a.upright_start, a.total_frames = int(bool(upright_start)), total
+    a.root_offset[:] = [float(v) for v in root_offset]
+    _launch("pulse_motion_export", ctypes.byref(a))
+    return out_rot, out_trans
+
+
 # --------------------------------------------------------------------------- #
 # planar ("x3p") fp32-grade GEMM: operands kept pre-split in HBM as three bf16 planes (include/pulse_hip.h section 4b)
 # --------------------------------------------------------------------------- #

@@ -96,15 +96,34 @@ class CommonPlayer:
         """The run loop as a motion generator: ``n_steps`` steps of every env, finished envs reset as in ``run``.  With z_source 'prior' (&c)
         the humanoid moves from the prior's samples alone.  -> {'steps', 'resets'}; ``record``: also 'rb' (T, N, J, 13), the simulator's
         rigid-body state after each step, and -- for a network with a latent -- 'z' (T, N, E), the latent of each step; both stay on the device."""
+        return self._generate(n_steps, record, record)
+
+    def generate_motion(self, n_steps, *, form="motion", min_frames=2, skeleton_trees=None, **export):
+        """``generate`` with a recorder attached (env/motion_export.py): the rollout as motion clips, one per episode segment of every env, keyed
+        f"{env}_{k}" -- ``MotionLib.from_motion_data`` takes the result as it is (form "motion"; ``min_frames=2`` because it rejects one-frame
+        clips; the dropped segments are reported in ``.dropped``).  For a network with a latent every clip also carries "z" (F, E).  ``export``: further
+        arguments of ``export_motion`` (fps, root_offset, upright_start ...).  One ``pulse_motion_export`` launch after the loop."""
+        from ..env.motion_export import MotionRecorder
+        recorder = MotionRecorder(self.env.task, int(n_steps))
+        run = self._generate(n_steps, False, True, recorder)
+        out = recorder.export(skeleton_trees, form=form, min_frames=min_frames, **export)
+        if "z" in run and len(out):
+            z, seg = run["z"].cpu().numpy(), out.segments
+            for key, e, t0, f in zip(seg["keys"], seg["env"].tolist(), seg["t0"].tolist(), seg["frames"].tolist()):
+                out[key]["z"] = z[t0:t0 + f, e].copy()
+        return out
+
+    def _generate(self, n_steps, record_rb, record_z, recorder=None):
         env, n, T = self.env, self.env.num_envs, int(n_steps)
+        record = record_rb
         obs = env.reset()
-        has_z = record and hasattr(self.model, "z_source")          # amp_z: the policy has a latent to record
+        has_z = record_z and hasattr(self.model, "z_source")        # amp_z: the policy has a latent to record
         ws = self.model.workspace(n, train=False) if has_z else None
         out = {}
         if record:
             out["rb"] = torch.empty((T,) + tuple(env.task.sim.rigid_body_state.shape), device=self.device)
-            if has_z:
-                out["z"] = torch.empty(T, n, ws["z"].shape[1], device=self.device)
+        if has_z:
+            out["z"] = torch.empty(T, n, ws["z"].shape[1], device=self.device)
         resets = torch.zeros((), dtype=torch.int64, device=self.device)
         try:
             for t in range(T):
@@ -117,6 +136,8 @@ class CommonPlayer:
                 self._post_step(info)
                 if record:
                     out["rb"][t].copy_(env.task.sim.rigid_body_state)
+                if recorder is not None:
+                    recorder.record()
                 d = done > 0
                 resets += d.sum()
                 obs = env.reset_masked(d)                           # (a mask, no read-back: one host sync at the end of the loop)
