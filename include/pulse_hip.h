@@ -604,6 +604,57 @@ int pulse_sizeof_motion_export_args(void);
 int pulse_motion_export(const pulse_motion_export_args* args, pulse_stream_t s);
 
 /* ------------------------------------------------------------------------- *
+ * 2b'.3. A streamed keypoint reference: what HumanoidImMCPDemo._compute_task_obs_demo does on the host every control step in front of the
+ *      task observation (phc/env/tasks/humanoid_im_mcp_demo.py:252-290, the obs_v == 7 branch; smpl_2_mujoco :32, mean_limb_lengths :66,
+ *      to_isaac_mat :56, the three deque(maxlen=30) :59-61) -- one launch per pushed frame, every env (a 32-lane half-wave per env,
+ *      lane = body, lane J = the root translation).  Per selected env e, with c = max(count[e], 0), slot w = c mod H, L = min(c + 1, H):
+ *        p[b]    = j3d[e, joint_map[b]]  (:255; written to ``raw`` as it is: ref_rb_pos_orig, :261, 314);  trans = p[0];  p -= trans  (:256, 263)
+ *        scale   = ((|p[parent[1]] - p[1]| / mean_limb_lengths[0]) + ... + (|p[parent[5]] - p[5]| / mean_limb_lengths[4])) / 5   (:265-271), summed in
+ *                  that order;  p /= scale  (:272; IEEE division: a coincident keypoint set has scale 0 and p = 0 / 0 = NaN, as numpy gives, and the
+ *                  NaN stays in the env's history for the next H - 1 pushes -- or until the env is cleared)
+ *        root_ring[e, w] = trans;  body_ring[e, w] = p  (:276, 282: the deques; the ring keeps the newest H)
+ *        the newest sample of scipy's gaussian_filter1d(history, sigma, axis=0, mode="mirror") (:278-285) is a fixed weighted sum of the L samples:
+ *                  f = sum_{i < L} taps[k, L - 1, i] * history[i], oldest first; k = 0 for the root's component 2 (sigma 10), 1 for its components
+ *                  0 and 1 (sigma 5), 2 for every body coordinate (sigma 2).  The table is the caller's (pulse_amd.kernels.keypoint_taps).
+ *        pos[b]  = frame * (p_f[b] + trans_f)  (:287-288; frame = to_isaac_mat, row-major: pos_i = frame[3 i] x_0 + frame[3 i + 1] x_1 + frame[3 i + 2] x_2)
+ *        vel[b]  = (pos[b] - prev_pos[b]) / dt  (:290: SkeletonMotion._compute_velocity on the two stacked frames without its filter,
+ *                  poselib skeleton3d.py:1100-1107; prev_pos is zero after a clear, so the first velocity is pos / dt, the reference's behaviour)
+ *        prev_pos[b] = pos[b] (:310);  count[e] = c + 1 (folded to H + (c + 1) mod H at 2^30: L and the slot are kept)
+ *      count is PER ENV: the envs of one launch may hold different L (the reference's single deque cannot).  Clearing an env = zeroing its
+ *      count and prev_pos (the caller's memset).  Envs outside env_mask are left untouched: state and outputs.
+ *      fp32, no FMA contraction, precise sqrtf and division.  Nothing is launched unless every argument passes.
+ * ------------------------------------------------------------------------- */
+#define PULSE_KEYPOINT_MAX_BODIES 31
+#define PULSE_KEYPOINT_MAX_HISTORY 64
+#define PULSE_KEYPOINT_LIMBS 5
+typedef struct pulse_keypoint_push_args {
+    const float* j3d;                   /* (N, J, 3) keypoints in SMPL joint order, device; element strides below, inner stride 1 */
+    int64_t j3d_stride_n, j3d_stride_j;
+    int32_t num_envs;                   /* N */
+    int32_t num_bodies;                 /* J in [6, 31] */
+    int32_t history;                    /* H in [1, 64] */
+    float dt;                           /* > 0 */
+    const uint8_t* env_mask;            /* (N) optional: 0 = leave the env alone */
+    const float* taps;                  /* (3, H, H) device: row L - 1 of table k holds the L weights, oldest sample first */
+    int32_t joint_map[32];              /* body -> SMPL joint: a permutation of 0 .. J-1, first J used */
+    int32_t parent_indices[32];         /* -1 for body 0, 0 <= parent < child; bodies 1 .. 5 are the limbs */
+    float mean_limb_lengths[PULSE_KEYPOINT_LIMBS];
+    float frame[9];                     /* row-major 3 x 3 */
+    int32_t reserved[2];
+    /* state, device */
+    float* root_ring;                   /* (N, H, 3) */
+    float* body_ring;                   /* (N, H, J, 3): slot-major inside the env, so the lanes of an env read one contiguous run per slot */
+    int32_t* count;                     /* (N) pushes since the env was cleared */
+    float* prev_pos;                    /* (N, J, 3) */
+    /* outputs, device */
+    float* pos;                         /* (N, J, 3) */
+    float* vel;                         /* (N, J, 3) */
+    float* raw;                         /* (N, J, 3) optional */
+} pulse_keypoint_push_args;
+int pulse_sizeof_keypoint_push_args(void);
+int pulse_keypoint_push(const pulse_keypoint_push_args* args, pulse_stream_t s);
+
+/* ------------------------------------------------------------------------- *
  * 2b''. Evaluation metrics, accumulated per control step of an evaluation batch (IMAmpAgent.eval,
  *      phc/learning/im_amp.py:136-363).  The reference copies every env's body positions to the host on every step
  *      (HumanoidIm.post_physics_step under flags.im_eval, phc/env/tasks/humanoid_im.py:667-673), slices them per motion to

@@ -69,6 +69,14 @@ class MotionExportArgs(Structure):
                 ("out_body_quat", c_void_p), ("out_dof_pos", c_void_p), ("total_frames", c_int64)]
 
 
+class KeypointPushArgs(Structure):
+    _fields_ = [("j3d", c_void_p), ("j3d_stride_n", c_int64), ("j3d_stride_j", c_int64), ("num_envs", c_int32), ("num_bodies", c_int32),
+                ("history", c_int32), ("dt", c_float), ("env_mask", c_void_p), ("taps", c_void_p), ("joint_map", c_int32 * 32),
+                ("parent_indices", c_int32 * 32), ("mean_limb_lengths", c_float * 5), ("frame", c_float * 9), ("reserved", c_int32 * 2),
+                ("root_ring", c_void_p), ("body_ring", c_void_p), ("count", c_void_p), ("prev_pos", c_void_p),
+                ("pos", c_void_p), ("vel", c_void_p), ("raw", c_void_p)]
+
+
 class ImEvalArgs(Structure):
     _fields_ = [("rb", c_void_p), ("rb_env_stride", c_int64), ("ref_pos", c_void_p), ("ref_env_stride", c_int64), ("num_envs", c_int32),
                 ("num_bodies", c_int32), ("num_steps", c_void_p), ("step", c_int32), ("env_mask", c_void_p), ("ring", c_void_p),
@@ -402,6 +410,8 @@ SIGNATURES = {
     "pulse_motion_ingest": (c_int, [POINTER(MotionIngestArgs), P]),
     "pulse_sizeof_motion_export_args": (c_int, []),
     "pulse_motion_export": (c_int, [POINTER(MotionExportArgs), P]),
+    "pulse_sizeof_keypoint_push_args": (c_int, []),
+    "pulse_keypoint_push": (c_int, [POINTER(KeypointPushArgs), P]),
     "pulse_sizeof_im_eval_args": (c_int, []),
     "pulse_im_eval_accum": (c_int, [POINTER(ImEvalArgs), P]),
     "pulse_gae": (c_int, [P, P, P, P, c_int32, c_int32, c_int64, c_int64, c_float, c_float, P, P, P]),

@@ -144,6 +144,11 @@ ENV_MCP = {"fut_tracks": False, "obs_v": 7, "has_pnn": True, "fitting": True, "n
            "enableEarlyTermination": True, "terminationDistance": 0.25, "numTrajSamples": 3, "trajSampleTimestepInv": 3, "enableTaskObs": True,
            "episode_length": 300}
 
+# the keypoint-driven demos (humanoid_im_mcp_demo.py, humanoid_im_demo.py): the MCP composer's switches without the get-up task's, and the plain
+# imitation env at obs_v 7; both with the far masking their task observation applies (close_distance is the class's own: 0.5 / 0.25)
+ENV_MCP_DEMO = {k: v for k, v in ENV_MCP.items() if k not in ("getup_schedule", "getup_udpate_epoch", "recoverySteps", "recoveryEpisodeProb", "fallInitProb")}
+ENV_IM_DEMO = dict(ENV_IM, obs_v=7, zero_out_far=True, zero_out_far_train=False)
+
 ENV_TERRAIN_Z = {"local_root_obs": True, "root_height_obs": True, "enableEarlyTermination": True, "episode_length": 300, "enableTaskObs": True,
                  "numTrajSamples": 10, "trajSampleTimestep": 0.5, "speedMin": 0.0, "speedMax": 3.0, "accelMax": 2.0, "sharpTurnProb": 0.02,
                  "terrain_obs": True, "terrain_obs_type": "square", "terrain_obs_root": "head", "use_center_height": True, "power_reward": False,
@@ -199,6 +204,10 @@ CONFIGS = {
     "mcp": {"num_envs": 1536, "horizon_length": 32, "minibatch_size": 16384, "network": "amp_mcp", "env": "mcp", "agent": "amp"},
     "mcp_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_mcp", "env": "mcp", "agent": "amp",
                   "units": [256, 128]},
+    # a trained tracker driven by streamed keypoints (HumanoidImMCPDemo / HumanoidImDemo on the recorded physics stand-in: the data path only)
+    "mcp_demo_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "network": "amp_mcp", "env": "mcp_demo", "agent": "amp",
+                       "units": [256, 128]},
+    "im_demo_small": {"num_envs": 64, "horizon_length": 16, "minibatch_size": 256, "units": [512, 512], "env": "im_demo"},
     # PHC's first stage (learning=im_pnn, env=phc_kp_pnn_iccv): column training_prim of num_prim progressive columns trains, the AMP
     # discriminator beside it.  ``pnn`` is cfg5's shape, env, discriminator and mixed_precision with the amp_pnn network: the same launches
     "pnn": {"num_envs": 8192, "horizon_length": 32, "minibatch_size": 16384, "units": [1024, 512], "network": "amp_pnn", "env": "amp", "agent": "amp",
@@ -282,6 +291,8 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
     ``robot_overrides``: cfg.robot keys on top of the humanoid's (bias_offset, has_smpl_pd_offset, freeze_toe, freeze_hand, ...).
     ``dof_limits``: the joint limits the stand-in simulator publishes -- None (none: the PD-target table stays offset 0 / scale 1), True
     (synthetic.synthetic_dof_limits of the humanoid) or a (lower, upper) pair.
+    ``env_kind`` 'mcp_demo' / 'im_demo': HumanoidImMCPDemo / HumanoidImDemo (env/humanoid_im_demo.py) over a KeypointStream the caller feeds, on
+    RecordedSim / RecordedRollout -- the recorded stand-in does not follow the keypoints: it exercises the data path only.
     ``terrain`` (env_kind 'terrain_z'): a TERRAINS name or an env/terrain.py:Terrain the simulator publishes as ``sim.terrain`` -- the task
     then walks on its height field and resets onto its valid start cells."""
     from .env.humanoid_im import HumanoidIm, VecTaskPythonWrapper, check_humanoid_options
@@ -338,6 +349,32 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
                                                                                           has_lateral=opts["has_lateral"]))
         task = HumanoidImMCPGetup(cfg, sim, motion, device=device, pnn_checkpoint=make)
         return VecTaskPythonWrapper(task, rl_device=device), None
+    if env_kind in ("mcp_demo", "im_demo"):
+        # HumanoidImMCPDemo / HumanoidImDemo: the reference is a KeypointStream the caller feeds (task.push_keypoints), the physics the recorded
+        # stand-in -- it does NOT follow the keypoints: this exercises the data path (stream -> observation -> policy -> PD targets) only.
+        # The MCP demo gets the synthetic PNN checkpoint as "mcp" does.
+        from . import synthetic as syn
+        from .env.humanoid_im_demo import HumanoidImDemo, HumanoidImMCPDemo, check_demo_options
+        from .env.humanoid_im_mcp import check_mcp_options
+        from .env.sim import RecordedRollout, RecordedSim
+        env_cfg = dict(ENV_MCP_DEMO if env_kind == "mcp_demo" else ENV_IM_DEMO)
+        env_cfg.update(env_overrides or {})
+        cfg = {"env": env_cfg, "robot": robot}
+        name = "HumanoidImMCPDemo" if env_kind == "mcp_demo" else "HumanoidImDemo"
+        check_demo_options(cfg, name)                   # an unbuilt combination raises by name before anything is allocated
+        if syn.skeleton(humanoid) is not syn.SKELETONS["smpl"]:
+            raise NotImplementedError(f"make_env: env_kind {env_kind!r} streams 24 SMPL keypoints; humanoid {humanoid!r} is not built")
+        make = None
+        if env_kind == "mcp_demo":
+            opts = check_mcp_options(cfg, name)
+            make = None if env_cfg.get("models") else (lambda t: syn.synthetic_pnn_checkpoint(opts["num_prim"], in_dim=t.num_obs, seed=seed + 11,
+                                                                                              has_lateral=opts["has_lateral"]))
+        if rollout is None:
+            rollout = RecordedRollout(num_envs, horizon + 1, seed=seed, rank=rank, humanoid=humanoid)
+        rollout.to(device)
+        sim = RecordedSim(rollout, dof_limits=dof_limits)
+        task = HumanoidImMCPDemo(cfg, sim, device=device, pnn_checkpoint=make) if env_kind == "mcp_demo" else HumanoidImDemo(cfg, sim, device=device)
+        return VecTaskPythonWrapper(task, rl_device=device), rollout
     env_cfg = dict(ENV_IM_VAE) if env_kind in ("vae", "vae_ppo") else dict(ENV_IM)
     if env_kind == "vae_ppo":
         env_cfg.update({"only_kin_loss": False, "save_kin_info": False, "distill": False})

@@ -44,6 +44,7 @@ SOURCES = [
     ("motion_build.hip", NO_CONTRACT),
     ("motion_ingest.hip", NO_CONTRACT),
     ("motion_export.hip", NO_CONTRACT),
+    ("keypoint_stream.hip", NO_CONTRACT),
     ("eval_metrics.hip", NO_CONTRACT),
     ("rollout_ops.hip", NO_CONTRACT),
     ("gae.hip", NO_CONTRACT),

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, EPI_BIAS_ACT, GEMM_RED_CONTIG, GemmDesc, PpoLossArgs
-from ._marshal import b16 as _b16, entry as _entry, launch as _launch, ptr, rows2d, stream as _stream
+from ._marshal import b16 as _b16, entry as _entry, launch as _launch, mask_u8 as _marshal_mask, ptr, rows2d, stream as _stream
 
 ACTIVATIONS = {"None": ACT_NONE, "none": ACT_NONE, None: ACT_NONE, "relu": ACT_RELU, "silu": ACT_SILU}
 
@@ -565,6 +565,101 @@ def motion_export(out_rot, out_trans, *, rb, seg_env, seg_t0, seg_frames, parent
     a.root_offset[:] = [float(v) for v in root_offset]
     _launch("pulse_motion_export", ctypes.byref(a))
     return out_rot, out_trans
+
+
+KEYPOINT_MAX_BODIES, KEYPOINT_MAX_HISTORY = 31, 64
+# humanoid_im_mcp_demo.py:66: the lengths of the limbs body 1 .. 5 hang on (parents 0, 1, 2, 3, 0), float32 as the reference keeps them
+KEYPOINT_MEAN_LIMB_LENGTHS = (0.1061, 0.3624, 0.4015, 0.1384, 0.1132)
+
+
+def keypoint_taps(sigmas=(10.0, 5.0, 2.0), history=30, truncate=4.0):
+    """The tap table of pulse_keypoint_push, (len(sigmas), H, H) float64 on the CPU (needs no device): row L - 1 of table k holds the L weights
+    with which ``scipy.ndimage.gaussian_filter1d(x, sigmas[k], axis=0, mode="mirror", truncate=truncate)[-1]`` combines L samples, oldest first;
+    the rest of the row is zero.  Tap t of the kernel (radius int(truncate * sigma + 0.5), weights exp(-t^2 / (2 sigma^2)) normalised) lands on
+    index (L - 1 + t) mod 2 (L - 1), reflected into 0 .. L - 1; L = 1 gives weight 1.  Default order: root component 2, root components 0 / 1,
+    body coordinates (humanoid_im_mcp_demo.py:278-284)."""
+    import numpy as np
+    h = int(history)
+    if not 1 <= h <= KEYPOINT_MAX_HISTORY:
+        raise ValueError(f"keypoint_taps: history {history!r} not in [1, {KEYPOINT_MAX_HISTORY}]")
+    out = np.zeros((len(sigmas), h, h), dtype=np.float64)
+    for k, sigma in enumerate(sigmas):
+        sigma = float(sigma)
+        if not sigma > 0:
+            raise ValueError(f"keypoint_taps: sigma {sigma!r} must be positive")
+        radius = int(float(truncate) * sigma + 0.5)
+        t = np.arange(-radius, radius + 1)
+        w = np.exp(-0.5 / (sigma * sigma) * t.astype(np.float64) ** 2)
+        w = w / w.sum()
+        out[k, 0, 0] = 1.0
+        for length in range(2, h + 1):
+            period = 2 * (length - 1)
+            idx = (length - 1 + t) % period
+            idx = np.where(idx > length - 1, period - idx, idx)
+            np.add.at(out[k, length - 1], idx, w)
+    return out
+
+
+def keypoint_frame(frame="y_up"):
+    """The 3 x 3 matrix pulse_keypoint_push applies last, float64: "y_up" = the reference's to_isaac_mat (humanoid_im_mcp_demo.py:56: the
+    rotation by -pi / 2 about x, built as scipy builds it from the quaternion (sin(-pi / 4), 0, 0, cos(-pi / 4))); "sim" = identity (keypoints
+    already in the simulator's z-up frame).  Needs no device."""
+    import numpy as np
+    if frame == "sim":
+        return np.eye(3)
+    if frame != "y_up":
+        raise ValueError(f"keypoint frame {frame!r}: 'y_up' or 'sim'")
+    x, w = np.sin(-np.pi / 4), np.cos(-np.pi / 4)
+    x2, w2, xw = x * x, w * w, x * w
+    return np.array([[x2 + w2, 0.0, 0.0], [0.0, -x2 + w2, -2 * xw], [0.0, 2 * xw, -x2 + w2]])
+
+
+def keypoint_push(j3d, *, taps, root_ring, body_ring, count, prev_pos, pos, vel, joint_map, parents, raw=None, env_mask=None,
+                  mean_limb_lengths=KEYPOINT_MEAN_LIMB_LENGTHS, frame=None, dt=1.0 / 30.0):
+    """pulse_keypoint_push: one frame of keypoints ``j3d`` (N, J, 3) float32 -> ``pos`` / ``vel`` (N, J, 3) of the filtered reference, one launch
+    (include/pulse_hip.h section 2b'.3).  ``j3d`` is read in place: any view with unit inner stride (env and joint strides are honoured).
+    State, updated in place, all contiguous: ``root_ring`` (N, H, 3), ``body_ring`` (N, H, J, 3), ``count`` (N,) int32, ``prev_pos`` (N, J, 3).
+    ``taps`` (3, H, H) float32 on the device (``keypoint_taps``); ``frame`` a 3 x 3 sequence (default ``keypoint_frame("y_up")``); ``joint_map`` /
+    ``parents`` sequences of J ints; ``env_mask`` (N,) bool / uint8: envs at 0 are left untouched.  ``raw`` (N, J, 3): the reordered input."""
+    a = _lib.KeypointPushArgs()
+    a.j3d = _p(j3d, "j3d", torch.float32)
+    j = len(parents)
+    if j3d.dim() != 3 or tuple(j3d.shape[1:]) != (j, 3):
+        raise ValueError(f"j3d: expected (N, {j}, 3), got {tuple(j3d.shape)}")
+    n = j3d.shape[0]
+    if not 6 <= j <= KEYPOINT_MAX_BODIES:
+        raise ValueError(f"keypoint_push: num_bodies {j} not in [6, {KEYPOINT_MAX_BODIES}] (one lane of a half-wave per body and one for the root)")
+    if len(joint_map) != j:
+        raise ValueError(f"joint_map: {j} entries expected, one per body")
+    a.root_ring = _p(root_ring, "root_ring", torch.float32)
+    if root_ring.dim() != 3 or root_ring.shape[0] != n or root_ring.shape[2] != 3:
+        raise ValueError(f"root_ring: expected ({n}, H, 3), got {tuple(root_ring.shape)}")
+    h = root_ring.shape[1]
+    if not 1 <= h <= KEYPOINT_MAX_HISTORY:
+        raise ValueError(f"keypoint_push: history {h} not in [1, {KEYPOINT_MAX_HISTORY}]")
+    a.body_ring, a.prev_pos = _p(body_ring, "body_ring", torch.float32), _p(prev_pos, "prev_pos", torch.float32)
+    a.count, a.taps = _p(count, "count", torch.int32), _p(taps, "taps", torch.float32)
+    a.pos, a.vel, a.raw = _p(pos, "pos", torch.float32), _p(vel, "vel", torch.float32), _p(raw, "raw", torch.float32)
+    for name, t, shape in (("root_ring", root_ring, (n, h, 3)), ("body_ring", body_ring, (n, h, j, 3)), ("count", count, (n,)), ("prev_pos", prev_pos, (n, j, 3)),
+                           ("taps", taps, (3, h, h)), ("pos", pos, (n, j, 3)), ("vel", vel, (n, j, 3)), ("raw", raw, (n, j, 3))):
+        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError(f"{name}: expected a contiguous tensor of shape {shape}, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
+    if env_mask is not None:
+        env_mask = _marshal_mask(env_mask)
+        a.env_mask = _p(env_mask, "env_mask", torch.uint8)
+        if tuple(env_mask.shape) != (n,):
+            raise ValueError(f"env_mask: expected shape ({n},), got {tuple(env_mask.shape)}")
+    a.j3d_stride_n, a.j3d_stride_j = j3d.stride(0), j3d.stride(1)
+    a.num_envs, a.num_bodies, a.history, a.dt = n, j, h, float(dt)
+    a.joint_map[:j] = [int(v) for v in joint_map]
+    a.parent_indices[:j] = [int(v) for v in parents]
+    if len(mean_limb_lengths) != 5:
+        raise ValueError("mean_limb_lengths: five lengths expected (the limbs of bodies 1 .. 5)")
+    a.mean_limb_lengths[:] = [float(v) for v in mean_limb_lengths]
+    m = keypoint_frame("y_up") if frame is None else frame
+    a.frame[:] = [float(m[r][c]) for r in range(3) for c in range(3)]
+    _launch("pulse_keypoint_push", ctypes.byref(a))
+    return pos, vel
 
 
 # --------------------------------------------------------------------------- #

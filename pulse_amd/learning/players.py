@@ -103,18 +103,39 @@ class CommonPlayer:
         f"{env}_{k}" -- ``MotionLib.from_motion_data`` takes the result as it is (form "motion"; ``min_frames=2`` because it rejects one-frame
         clips; the dropped segments are reported in ``.dropped``).  For a network with a latent every clip also carries "z" (F, E).  ``export``: further
         arguments of ``export_motion`` (fps, root_offset, upright_start ...).  One ``pulse_motion_export`` launch after the loop."""
+        return self._motion(n_steps, None, skeleton_trees, form=form, min_frames=min_frames, **export)
+
+    def track(self, keypoints, record=False):
+        """Drive a keypoint-demo env (HumanoidImMCPDemo / HumanoidImDemo, configs "mcp_demo_small" / "im_demo_small") with streamed keypoints:
+        ``keypoints`` is a (T, N, 24, 3) float32 device tensor or an iterable of (N, 24, 3) frames; per frame: ``task.push_keypoints(frame)``
+        (one pulse_keypoint_push launch), ``get_action``, ``env.step``.  Returns what ``generate`` returns (the demo never resets: 'resets' is 0)."""
+        return self._generate(None, record, record, frames=self._frames(keypoints))
+
+    def track_motion(self, keypoints, *, form="motion", min_frames=2, skeleton_trees=None, **export):
+        """``track`` with a recorder attached: the tracked motion as clips, one per env -- ``MotionLib.from_motion_data`` takes the result as it is
+        (``generate_motion``'s arguments and layout)."""
+        frames = self._frames(keypoints)
+        return self._motion(len(frames), frames, skeleton_trees, form=form, min_frames=min_frames, **export)
+
+    def _frames(self, keypoints):
+        if not hasattr(self.env.task, "push_keypoints"):
+            raise TypeError(f"track: {type(self.env.task).__name__} takes no keypoints (HumanoidImMCPDemo / HumanoidImDemo do: configs 'mcp_demo_small', "
+                            "'im_demo_small')")
+        return keypoints if isinstance(keypoints, torch.Tensor) else list(keypoints)
+
+    def _motion(self, n_steps, frames, skeleton_trees, **export):
         from ..env.motion_export import MotionRecorder
         recorder = MotionRecorder(self.env.task, int(n_steps))
-        run = self._generate(n_steps, False, True, recorder)
-        out = recorder.export(skeleton_trees, form=form, min_frames=min_frames, **export)
+        run = self._generate(n_steps, False, True, recorder, frames=frames)
+        out = recorder.export(skeleton_trees, **export)
         if "z" in run and len(out):
             z, seg = run["z"].cpu().numpy(), out.segments
             for key, e, t0, f in zip(seg["keys"], seg["env"].tolist(), seg["t0"].tolist(), seg["frames"].tolist()):
                 out[key]["z"] = z[t0:t0 + f, e].copy()
         return out
 
-    def _generate(self, n_steps, record_rb, record_z, recorder=None):
-        env, n, T = self.env, self.env.num_envs, int(n_steps)
+    def _generate(self, n_steps, record_rb, record_z, recorder=None, frames=None):
+        env, n, T = self.env, self.env.num_envs, int(n_steps if frames is None else len(frames))
         record = record_rb
         obs = env.reset()
         has_z = record_z and hasattr(self.model, "z_source")        # amp_z: the policy has a latent to record
@@ -129,6 +150,8 @@ class CommonPlayer:
             for t in range(T):
                 if has_z:
                     ws["z_record"] = out["z"][t]                    # the prior launch writes the step's z there itself
+                if frames is not None:
+                    env.task.push_keypoints(frames[t])              # the reference of the observation this step ends with
                 action = self.get_action(obs, self.is_determenistic)
                 if has_z and self.model.z_source == "posterior":    # (the posterior launch has no recorder output)
                     out["z"][t].copy_(ws["z"])
