@@ -15,15 +15,12 @@
 // in LDS and written with coalesced stores into the caller's pitch (e.g. slot 0 of the (N, 10, W) history).
 // HBM/launch bound: 52 B root record + 2 x 276 B dofs + 48 B key bodies read, 4 W bytes written per env.
 // Compiled with -ffp-contract=off (reference operation order).
-#include "common.h"
 #include "env_select.h"
-#include "rot_math.h"
 #include "motion_math.h"
 
 namespace pulse {
 
-constexpr int kAmpLanes = 32;
-constexpr int kAmpEnvs = 4;
+constexpr int kAmpLanes = kHalfWave, kAmpThreads = 128, kAmpEnvs = LaneGroup<kAmpLanes, kAmpThreads>::slots;
 constexpr int kAmpMaxW = 320;
 
 constexpr int kAmpMaxHist = 9;      // history frames behind the current one (numAMPObsSteps - 1)
@@ -57,14 +54,14 @@ __device__ __forceinline__ void amp_copy_rows(float* o, const AmpLayout& L, int 
 // PLAIN: the upright, version-1 frame without rows on aligned windows -- the shipped SMPL configuration -- with the variant switches folded at
 // compile time (measured: as runtime flags they cost the fused cfg5 launch 0.6 us of 46, profiles/amp_obs_variants_ab.txt).
 template <bool HIST, bool PLAIN>
-__global__ void __launch_bounds__(kAmpEnvs * kAmpLanes) amp_obs_kernel(const pulse_amp_obs_args a, const int vec4_arg) {
+__global__ void __launch_bounds__(kAmpThreads) amp_obs_kernel(const pulse_amp_obs_args a, const int vec4_arg) {
     const int vec4 = PLAIN ? 1 : vec4_arg, version = PLAIN ? 1 : a.version, upright_start = PLAIN ? 1 : a.upright_start;
     const int num_shape = PLAIN ? 0 : a.num_shape, num_limb = PLAIN ? 0 : a.num_limb;
     __shared__ __align__(16) float s_out[kAmpEnvs][kAmpMaxW];
     __shared__ __align__(16) float s_hist[HIST ? kAmpEnvs : 1][HIST ? kAmpMaxHist * kAmpMaxW : 1];
-    const int slot = threadIdx.x / kAmpLanes, lane = threadIdx.x % kAmpLanes;
+    const auto [slot, lane, idx] = lane_group<kAmpLanes, kAmpThreads>();
     int64_t e = 0;
-    const bool valid = select_env(a, blockIdx.x * kAmpEnvs + slot, e);      // (carried past the barrier: nobody returns early)
+    const bool valid = select_env(a, (int)idx, e);                           // (carried past the barrier: nobody returns early)
     const int Jd = a.num_joints, Kb = a.num_key_bodies;
     const AmpLayout L = amp_layout(Jd, Kb, a.root_height_obs, version, num_shape, num_limb);   // counts are 0 without a pointer (launcher)
     const int h0 = L.h0, off_vel = L.off_vel, off_ang = L.off_ang, off_dof = L.off_dof, off_dvel = L.off_dvel, off_key = L.off_key, W = L.W;
@@ -155,10 +152,9 @@ __global__ void __launch_bounds__(kAmpEnvs * kAmpLanes) amp_obs_kernel(const pul
 // env's motion at start_time[e] - dt (k + 1) -- MotionLib.get_motion_state (motion_lib_base.py:434-517) and build_amp_observations_smpl
 // fused, a half-wave per (env, k); envs outside the mask cost an index read.  (Was: a motion query and an AMP-frame pass over ALL
 // N x (S - 1) rows plus a where / copy of the window, 195 us per rollout step at 8192 envs.)
-__global__ void __launch_bounds__(kAmpEnvs * kAmpLanes) amp_hist_init_kernel(const pulse_amp_hist_args a) {
+__global__ void __launch_bounds__(kAmpThreads) amp_hist_init_kernel(const pulse_amp_hist_args a) {
     __shared__ float s_out[kAmpEnvs][kAmpMaxW];
-    const int slot = threadIdx.x / kAmpLanes, lane = threadIdx.x % kAmpLanes;
-    const long long idx = (long long)blockIdx.x * kAmpEnvs + slot;
+    const auto [slot, lane, idx] = lane_group<kAmpLanes, kAmpThreads>();
     const int Hs = a.hist_steps - 1;
     bool valid = idx < (long long)a.num_envs * Hs;
     const long long e = valid ? idx / Hs : 0;
@@ -257,7 +253,9 @@ int pulse_amp_obs(const pulse_amp_obs_args* args, pulse_stream_t s) {
     const int w = pulse_amp_obs_width_v(a.num_joints, a.num_key_bodies, a.root_height_obs, a.version, a.num_shape, a.num_limb);
     PULSE_REQUIRE(w <= kAmpMaxW && a.out_stride >= w, "pulse_amp_obs: width %d exceeds %d or the output pitch", w, kAmpMaxW);
     const bool plain = a.upright_start && a.version == 1 && a.num_shape == 0 && a.num_limb == 0;
-    const dim3 grid((unsigned)((count + kAmpEnvs - 1) / kAmpEnvs)), block(kAmpEnvs * kAmpLanes);
+    unsigned blocks;
+    if (const int rc = lane_group_blocks("pulse_amp_obs", count, kAmpEnvs, blocks)) return rc;
+    const dim3 grid(blocks), block(kAmpThreads);
     if (a.hist_steps > 1) {
         PULSE_REQUIRE(a.hist_steps - 1 <= kAmpMaxHist && a.out_stride >= (int64_t)a.hist_steps * w,
                       "pulse_amp_obs: history mode needs hist_steps <= %d and a window pitch of hist_steps * W floats", kAmpMaxHist + 1);
@@ -283,17 +281,16 @@ int pulse_amp_hist_init(const pulse_amp_hist_args* args, pulse_stream_t s) {
     PULSE_REQUIRE(a.num_envs >= 0 && a.hist_steps >= 1, "pulse_amp_hist_init: bad sizes");
     if (a.num_envs == 0 || a.hist_steps == 1) return PULSE_OK;
     const pulse_motion_tables& T = a.tab;
-    PULSE_REQUIRE(T.frames && T.motion_lengths && T.motion_dt && T.motion_num_frames && T.length_starts, "pulse_amp_hist_init: null table pointer");
-    PULSE_REQUIRE(T.num_bodies >= 1 && T.num_bodies <= kAmpLanes && T.frame_stride % 4 == 0 && T.off_grs % 4 == 0 && T.off_lrs % 4 == 0,
-                  "pulse_amp_hist_init: bad motion tables");
+    if (const int rc = check_motion_tables("pulse_amp_hist_init", T, kAmpLanes)) return rc;
     PULSE_REQUIRE(a.motion_ids && a.start_times && a.hist && a.key_body_ids, "pulse_amp_hist_init: null pointer");
     PULSE_REQUIRE(a.num_joints >= 1 && a.num_joints <= kAmpLanes && (a.joint_ids || a.num_joints <= T.num_bodies - 1) &&
                   a.num_key_bodies >= 0 && a.num_key_bodies <= kAmpLanes, "pulse_amp_hist_init: joints / key bodies must fit 32 lanes and the skeleton");
     if (const int rc = amp_check_variant(a, "pulse_amp_hist_init")) return rc;
     const int w = pulse_amp_obs_width_v(a.num_joints, a.num_key_bodies, a.root_height_obs, a.version, a.num_shape, a.num_limb);
     PULSE_REQUIRE(w <= kAmpMaxW && a.step_stride >= w && a.env_stride >= (int64_t)a.hist_steps * a.step_stride, "pulse_amp_hist_init: bad pitches");
-    const long long total = (long long)a.num_envs * (a.hist_steps - 1);
-    hipLaunchKernelGGL(amp_hist_init_kernel, dim3((unsigned)((total + kAmpEnvs - 1) / kAmpEnvs)), dim3(kAmpEnvs * kAmpLanes), 0, as_stream(s), a);
+    unsigned blocks;
+    if (const int rc = lane_group_blocks("pulse_amp_hist_init", (long long)a.num_envs * (a.hist_steps - 1), kAmpEnvs, blocks)) return rc;
+    hipLaunchKernelGGL(amp_hist_init_kernel, dim3(blocks), dim3(kAmpThreads), 0, as_stream(s), a);
     return check_launch("pulse_amp_hist_init");
 }
 }

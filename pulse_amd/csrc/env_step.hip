@@ -19,8 +19,6 @@
 //     stores straight into the caller's row pitch (e.g. a 960-float GEMM-ready pitch, pad zeroed).
 // Compiled with -ffp-contract=off so products/sums round exactly like the eager reference.
 #include <cstdlib>
-#include "common.h"
-#include "rot_math.h"
 #include "motion_math.h"
 
 namespace pulse {
@@ -221,13 +219,7 @@ __global__ void __launch_bounds__(E * R * LB) im_step_kernel(const pulse_im_step
                         o = d + J * 3 + 4 * lane;             o[0] = b.q.x; o[1] = b.q.y; o[2] = b.q.z; o[3] = b.q.w;
                         o = d + J * 7 + 3 * lane;             o[0] = b.v.x; o[1] = b.v.y; o[2] = b.v.z;
                         o = d + J * 10 + 3 * lane;            o[0] = b.w.x; o[1] = b.w.y; o[2] = b.w.z;
-                        if (k == 0 && a.track_rb) {
-                            float* rec = a.track_rb + e * a.track_rb_stride + 13 * lane;
-                            rec[0] = b.p.x; rec[1] = b.p.y; rec[2] = b.p.z;
-                            rec[3] = b.q.x; rec[4] = b.q.y; rec[5] = b.q.z; rec[6] = b.q.w;
-                            rec[7] = b.v.x; rec[8] = b.v.y; rec[9] = b.v.z;
-                            rec[10] = b.w.x; rec[11] = b.w.y; rec[12] = b.w.z;
-                        }
+                        if (k == 0 && a.track_rb) store_record(a.track_rb + e * a.track_rb_stride + 13 * lane, b);
                     }
                     if (k == 0 && (a.track_dof_pos || a.obs_version == 2) && lane < J - 1) {
                         V3 dp, dv;
@@ -632,10 +624,9 @@ int pulse_im_step(const pulse_im_step_args* args, pulse_stream_t s) {
     }
     if (a.use_motion) {
         const pulse_motion_tables& M = a.motion;
-        PULSE_REQUIRE(M.frames && M.motion_lengths && M.motion_dt && M.motion_num_frames && M.length_starts && a.motion_ids,
-                      "pulse_im_step: in-kernel reference needs the motion tables and motion_ids");
+        if (const int rc = check_motion_tables("pulse_im_step", M, kImMaxBodies)) return rc;
+        PULSE_REQUIRE(a.motion_ids != nullptr, "pulse_im_step: in-kernel reference needs motion_ids");
         PULSE_REQUIRE(M.num_bodies == a.num_bodies, "pulse_im_step: motion library has %d bodies, env %d", M.num_bodies, a.num_bodies);
-        PULSE_REQUIRE(M.frame_stride % 4 == 0 && M.off_grs % 4 == 0 && M.off_lrs % 4 == 0, "pulse_im_step: motion record fields must be 16-B aligned");
         PULSE_REQUIRE(a.progress != nullptr || a.progress_rw != nullptr, "pulse_im_step: in-kernel reference needs the episode clock (progress)");
         PULSE_REQUIRE(a.clock_dt > 0.f, "pulse_im_step: in-kernel reference needs clock_dt");
         PULSE_REQUIRE((a.track_dof_pos == nullptr) == (a.track_dof_vel == nullptr), "pulse_im_step: track_dof_pos / track_dof_vel go together");

@@ -7,7 +7,7 @@
 // 33 .. 64 (2 envs per workgroup).  Every per-env reduction is a butterfly shuffle (lane_sum, common.h), so all lanes of a group hold every sum (the 3 x 3 SVD
 // runs redundantly on all of them) and lanes J .. LB - 1 feed exact zeros.  No atomics, no LDS.
 #include <cstdint>
-#include "common.h"
+#include "body_lanes.h"
 #include "env_select.h"
 
 namespace pulse {
@@ -191,10 +191,10 @@ extern "C" int pulse_im_eval_accum(const pulse_im_eval_args* args, pulse_stream_
     PULSE_REQUIRE(reinterpret_cast<uintptr_t>(a.rb) % 4 == 0 && reinterpret_cast<uintptr_t>(a.ref_pos) % 4 == 0 && reinterpret_cast<uintptr_t>(a.ring) % 4 == 0 &&
                   reinterpret_cast<uintptr_t>(a.num_steps) % 4 == 0, "pulse_im_eval_accum: rb, ref_pos, ring and num_steps must be 4-byte aligned");
     PULSE_REQUIRE(reinterpret_cast<uintptr_t>(a.accum) % 8 == 0, "pulse_im_eval_accum: accum must be 8-byte aligned");
-    const bool wide = J > 32;
-    const int per = kEvalThreads / (wide ? 64 : 32);
-    const int64_t blocks = ((int64_t)a.num_envs + per - 1) / per;
-    if (wide) hipLaunchKernelGGL(im_eval_accum_kernel<64>, dim3((unsigned)blocks), dim3(kEvalThreads), 0, as_stream(s), a);
-    else hipLaunchKernelGGL(im_eval_accum_kernel<32>, dim3((unsigned)blocks), dim3(kEvalThreads), 0, as_stream(s), a);
+    const bool wide = J > kHalfWave;
+    unsigned blocks;
+    if (const int rc = lane_group_blocks("pulse_im_eval_accum", a.num_envs, kEvalThreads / (wide ? 64 : 32), blocks)) return rc;
+    if (wide) hipLaunchKernelGGL(im_eval_accum_kernel<64>, dim3(blocks), dim3(kEvalThreads), 0, as_stream(s), a);
+    else hipLaunchKernelGGL(im_eval_accum_kernel<32>, dim3(blocks), dim3(kEvalThreads), 0, as_stream(s), a);
     return check_launch("pulse_im_eval_accum");
 }

@@ -18,24 +18,21 @@
 // + 4 (count) + taps (cached: 3 x 30 floats), written 300 (ring slot) + 3 x 288 (pos, vel, prev_pos) + 288 (raw) + 4.
 // Measured: profiles/keypoint_stream.txt.
 // Compiled with -ffp-contract=off: fp32 in the operation order of the numpy statements.
-#include "common.h"
+#include "body_lanes.h"
 #include "env_select.h"
 
 namespace pulse {
 
-constexpr int kKpThreads = 256;
-constexpr int kKpLanes = 32;                     // lanes per env: J bodies + the root lane
-constexpr int kKpSlots = kKpThreads / kKpLanes;  // envs per workgroup
+using KpGroup = LaneGroup<kHalfWave>;            // lanes per env: J bodies + the root lane
 
 // what the launcher validated on the host, by value in the kernel arguments
 struct KpTables {
-    unsigned char joint[kKpLanes];               // body -> SMPL joint
+    unsigned char joint[kHalfWave];               // body -> SMPL joint
     unsigned char limb_parent[PULSE_KEYPOINT_LIMBS];
 };
 
-__global__ void __launch_bounds__(kKpThreads) keypoint_push_kernel(const pulse_keypoint_push_args a, const KpTables tb) {
-    const int slot = threadIdx.x / kKpLanes, b = threadIdx.x % kKpLanes;
-    const long long e = (long long)blockIdx.x * kKpSlots + slot;
+__global__ void __launch_bounds__(KpGroup::threads) keypoint_push_kernel(const pulse_keypoint_push_args a, const KpTables tb) {
+    const auto [slot, b, e] = lane_group<kHalfWave>();
     const int J = a.num_bodies, H = a.history;
     const bool env = env_enabled(a, e);                                           // no early return: every lane reaches every cross-lane read
     const bool body = env && b < J, root = env && b == J;
@@ -48,15 +45,15 @@ __global__ void __launch_bounds__(kKpThreads) keypoint_push_kernel(const pulse_k
         px = k[0]; py = k[1]; pz = k[2];
     }
     if (body && a.raw) { float* o = a.raw + (e * J + b) * 3; o[0] = px; o[1] = py; o[2] = pz; }
-    const float tx = __shfl(px, J, kKpLanes), ty = __shfl(py, J, kKpLanes), tz = __shfl(pz, J, kKpLanes);      // trans = p[0]
+    const float tx = __shfl(px, J, kHalfWave), ty = __shfl(py, J, kHalfWave), tz = __shfl(pz, J, kHalfWave);      // trans = p[0]
     float qx = px - tx, qy = py - ty, qz = pz - tz;                                // p -= trans
     // ---- limb-length scale: lanes 1 .. 5 take |p[parent] - p[own]| / mean length; every lane sums the five in order
     const int par = (b >= 1 && b <= PULSE_KEYPOINT_LIMBS) ? tb.limb_parent[b - 1] : 0;
-    const float dx = __shfl(qx, par, kKpLanes) - qx, dy = __shfl(qy, par, kKpLanes) - qy, dz = __shfl(qz, par, kKpLanes) - qz;
+    const float dx = __shfl(qx, par, kHalfWave) - qx, dy = __shfl(qy, par, kHalfWave) - qy, dz = __shfl(qz, par, kHalfWave) - qz;
     const float ratio = sqrtf(dx * dx + dy * dy + dz * dz) / a.mean_limb_lengths[(b >= 1 && b <= PULSE_KEYPOINT_LIMBS) ? b - 1 : 0];
-    float scale = __shfl(ratio, 1, kKpLanes);
+    float scale = __shfl(ratio, 1, kHalfWave);
 #pragma unroll
-    for (int i = 2; i <= PULSE_KEYPOINT_LIMBS; ++i) scale = scale + __shfl(ratio, i, kKpLanes);
+    for (int i = 2; i <= PULSE_KEYPOINT_LIMBS; ++i) scale = scale + __shfl(ratio, i, kHalfWave);
     scale = scale / (float)PULSE_KEYPOINT_LIMBS;
     if (root) { qx = tx; qy = ty; qz = tz; }                                       // the root lane carries trans itself, unscaled
     else { qx = qx / scale; qy = qy / scale; qz = qz / scale; }                    // scale 0: 0 / 0 = NaN, as numpy
@@ -88,7 +85,7 @@ __global__ void __launch_bounds__(kKpThreads) keypoint_push_kernel(const pulse_k
         fx = fx + w01 * qx; fy = fy + w01 * qy; fz = fz + w2 * qz;
     }
     // ---- pos = frame (p_f + trans_f); vel = (pos - prev_pos) / dt
-    const float x0 = fx + __shfl(fx, J, kKpLanes), x1 = fy + __shfl(fy, J, kKpLanes), x2 = fz + __shfl(fz, J, kKpLanes);
+    const float x0 = fx + __shfl(fx, J, kHalfWave), x1 = fy + __shfl(fy, J, kHalfWave), x2 = fz + __shfl(fz, J, kHalfWave);
     if (body) {
         const long long at = (e * J + b) * 3;
 #pragma unroll
@@ -113,7 +110,7 @@ extern "C" int pulse_sizeof_keypoint_push_args(void) { return (int)sizeof(pulse_
 
 extern "C" int pulse_keypoint_push(const pulse_keypoint_push_args* args, pulse_stream_t s) {
     using namespace pulse;
-    static_assert(PULSE_KEYPOINT_MAX_BODIES == kKpLanes - 1, "one lane per body and one for the root");
+    static_assert(PULSE_KEYPOINT_MAX_BODIES == kHalfWave - 1, "one lane per body and one for the root");
     PULSE_REQUIRE(args != nullptr, "pulse_keypoint_push: null args");
     const pulse_keypoint_push_args& a = *args;
     PULSE_REQUIRE(a.num_envs >= 0, "pulse_keypoint_push: negative num_envs");
@@ -129,23 +126,14 @@ extern "C" int pulse_keypoint_push(const pulse_keypoint_push_args* args, pulse_s
     PULSE_REQUIRE(a.taps != nullptr, "pulse_keypoint_push: null taps");
     PULSE_REQUIRE(a.root_ring && a.body_ring && a.count && a.prev_pos, "pulse_keypoint_push: null state (root_ring / body_ring / count / prev_pos)");
     PULSE_REQUIRE(a.pos && a.vel, "pulse_keypoint_push: null output (pos / vel)");
-    KpTables tb;
-    for (int b = 0; b < kKpLanes; ++b) tb.joint[b] = 0;
-    bool seen[kKpLanes] = {};
-    for (int b = 0; b < J; ++b) {
-        const int j = a.joint_map[b];
-        PULSE_REQUIRE(j >= 0 && j < J, "pulse_keypoint_push: joint_map[%d] = %d is no SMPL joint (0 .. %d)", b, j, J - 1);
-        PULSE_REQUIRE(!seen[j], "pulse_keypoint_push: joint_map[%d] = %d is taken twice: joint_map must be a permutation of 0 .. %d", b, j, J - 1);
-        seen[j] = true;
-        tb.joint[b] = (unsigned char)j;
-    }
-    PULSE_REQUIRE(a.parent_indices[0] == -1, "pulse_keypoint_push: body 0 must be the root (parent -1), got parent %d", a.parent_indices[0]);
-    for (int b = 1; b < J; ++b) {
-        const int p = a.parent_indices[b];
-        PULSE_REQUIRE(p >= 0 && p < b, "pulse_keypoint_push: parent_indices[%d] = %d: every parent must precede its child (0 <= parent < child)", b, p);
-        if (b <= PULSE_KEYPOINT_LIMBS) tb.limb_parent[b - 1] = (unsigned char)p;
-    }
-    const long long blocks = ((long long)a.num_envs + kKpSlots - 1) / kKpSlots;
-    hipLaunchKernelGGL(keypoint_push_kernel, dim3((unsigned)blocks), dim3(kKpThreads), 0, as_stream(s), a, tb);
+    KpTables tb = {};
+    if (const int rc = check_permutation<kHalfWave>("pulse_keypoint_push", "joint_map", a.joint_map, J, nullptr)) return rc;
+    for (int b = 0; b < J; ++b) tb.joint[b] = (unsigned char)a.joint_map[b];
+    BodyTree<kHalfWave> tree;
+    if (const int rc = check_tree("pulse_keypoint_push", a.parent_indices, J, tree)) return rc;
+    for (int i = 0; i < PULSE_KEYPOINT_LIMBS; ++i) tb.limb_parent[i] = (unsigned char)tree.parent[i + 1];
+    unsigned blocks;
+    if (const int rc = lane_group_blocks("pulse_keypoint_push", a.num_envs, KpGroup::slots, blocks)) return rc;
+    hipLaunchKernelGGL(keypoint_push_kernel, dim3(blocks), dim3(KpGroup::threads), 0, as_stream(s), a, tb);
     return check_launch("pulse_keypoint_push");
 }

@@ -25,23 +25,14 @@ constexpr int kMbRadius = 8;                      // gaussian_filter1d: int(trun
 constexpr int kMbTile = 16;                       // output records per block of pass 2
 constexpr int kMbRows = kMbTile + 2 * kMbRadius;  // records whose unfiltered velocities a tile needs
 
-// the tree, by value in the kernel arguments (from the launcher's validated host copy)
-struct MbTree { signed char parent[kMbMaxBodies]; unsigned char depth[kMbMaxBodies]; int max_depth; };
-
-__device__ __forceinline__ Q4 load_q(const float* p) {
-    const float4 v = *reinterpret_cast<const float4*>(p);
-    return Q4{v.x, v.y, v.z, v.w};
-}
-
 // ---- pass 1: heading, grs, lrs, FK -> gts, padding ------------------------------------------------------------------------------------
 template <int LB>
-__global__ void __launch_bounds__(kMbThreads) motion_build_frames_kernel(const pulse_motion_build_args a, const MbTree tree, const int pad_start) {
-    constexpr int kSlots = kMbThreads / LB;
+__global__ void __launch_bounds__(LaneGroup<LB>::threads) motion_build_frames_kernel(const pulse_motion_build_args a, const BodyTree<kMbMaxBodies> tree, const int pad_start) {
+    constexpr int kSlots = LaneGroup<LB>::slots;
     __shared__ Q4 s_g[kSlots][LB];        // global rotations of the frame (after the heading rotation)
     __shared__ Q4 s_r[kSlots][LB];        // FK: rotation of the global transformation
     __shared__ V3 s_t[kSlots][LB];        // FK: translation of the global transformation
-    const int slot = threadIdx.x / LB, b = threadIdx.x % LB;
-    const long long g = (long long)blockIdx.x * kSlots + slot;
+    const auto [slot, b, g] = lane_group<LB>();
     const int J = a.num_bodies;
     const bool live = g < a.total_frames && b < J;          // no early return: every thread reaches the barriers
     float* rec = nullptr;
@@ -53,7 +44,7 @@ __global__ void __launch_bounds__(kMbThreads) motion_build_frames_kernel(const p
         long long src = a.clip_src_start[m] + (a.clip_crop_start ? a.clip_crop_start[m] : 0) + t;
         src = src < 0 ? 0 : (src > a.src_frames - 1 ? a.src_frames - 1 : src);          // a bad clip table reads a wrong frame, never out of bounds
         rec = a.frames + g * a.frame_stride;
-        q = load_q(a.src_rot + (src * J + b) * 4);
+        q = load_q4(a.src_rot + (src * J + b) * 4);
         const float* tr = a.src_trans + 3 * src;
         lt = b == 0 ? V3{tr[0], tr[1], tr[2]} : V3{a.local_translation[((long long)m * J + b) * 3], a.local_translation[((long long)m * J + b) * 3 + 1],
                                                    a.local_translation[((long long)m * J + b) * 3 + 2]};
@@ -72,7 +63,7 @@ __global__ void __launch_bounds__(kMbThreads) motion_build_frames_kernel(const p
                 lt.y = (float)(s * tx + c * ty);
             }
         }
-        *reinterpret_cast<float4*>(rec + a.off_grs + 4 * b) = make_float4(q.x, q.y, q.z, q.w);
+        store_q4(rec + a.off_grs + 4 * b, q);
         for (int c = pad_start + b; c < a.frame_stride; c += J) rec[c] = 0.0f;
     }
     s_g[slot][b] = q;
@@ -80,7 +71,7 @@ __global__ void __launch_bounds__(kMbThreads) motion_build_frames_kernel(const p
     const int p = b < J ? tree.parent[b] : -1;
     if (live) {
         l = p < 0 ? q : qmul_norm(qconj(s_g[slot][p]), q);
-        *reinterpret_cast<float4*>(rec + a.off_lrs + 4 * b) = make_float4(l.x, l.y, l.z, l.w);
+        store_q4(rec + a.off_lrs + 4 * b, l);
     }
     // FK, one tree level per round: transform_mul(global[parent], local[b]) (rotation3d.py:318-326)
     const int depth = b < J ? tree.depth[b] : -1;
@@ -142,7 +133,7 @@ __global__ void __launch_bounds__(kMbThreads) motion_build_velocity_kernel(const
         for (int c = 0; c < 3; ++c) raw[c] = ((pn[c] - pp[c]) / den) / dt;
         // quat_mul_norm(r[t+1], inverse(r[t])), identity at the clip's last frame; quat_angle_axis (rotation3d.py:231-240)
         Q4 d{0.0f, 0.0f, 0.0f, 1.0f};
-        if (g < hi) d = qmul_plain(load_q(rec + a.frame_stride + a.off_grs + 4 * b), qconj(load_q(rec + a.off_grs + 4 * b)));
+        if (g < hi) d = qmul_plain(load_q4(rec + a.frame_stride + a.off_grs + 4 * b), qconj(load_q4(rec + a.off_grs + 4 * b)));
         d = qnormalize_pos(d);
         const float s = 2.0f * (d.w * d.w) - 1.0f;
         const float angle = acosf(fminf(fmaxf(s, -1.0f), 1.0f));
@@ -173,7 +164,7 @@ __global__ void __launch_bounds__(kMbThreads) motion_build_velocity_kernel(const
             // local_rotation_to_dof_vel (motion_lib_base.py:47-53) of frames (t, t + 1); the last frame repeats the one before it (:67)
             const long long gt = g < hi ? g : hi - 1;
             const float* r0 = a.frames + gt * a.frame_stride + a.off_lrs + 4 * b;
-            const Q4 dq = qmul(qconj(load_q(r0)), load_q(r0 + a.frame_stride));
+            const Q4 dq = qmul(qconj(load_q4(r0)), load_q4(r0 + a.frame_stride));
             V3 ax;
             const float ang = q_to_angle_axis(dq, &ax);
             const float dt = s_dt[r];
@@ -199,20 +190,10 @@ extern "C" int pulse_motion_build(const pulse_motion_build_args* args, pulse_str
     PULSE_REQUIRE(a.clip_src_start && a.clip_out_start && a.clip_dt, "pulse_motion_build: null per-clip table (clip_src_start / clip_out_start / clip_dt)");
     PULSE_REQUIRE(a.clip_frames_host != nullptr, "pulse_motion_build: null clip_frames_host (the host copy of the frame counts)");
     PULSE_REQUIRE(a.local_translation != nullptr, "pulse_motion_build: null local_translation");
-    PULSE_REQUIRE(a.parent_indices_host != nullptr, "pulse_motion_build: null parent_indices_host");
     PULSE_REQUIRE(a.frames != nullptr, "pulse_motion_build: null frames (the output records)");
     PULSE_REQUIRE(a.src_frames >= 1, "pulse_motion_build: src_frames %lld: the staging buffers are empty", (long long)a.src_frames);
-    MbTree tree;
-    tree.max_depth = 0;
-    for (int b = 0; b < kMbMaxBodies; ++b) { tree.parent[b] = -1; tree.depth[b] = 0; }
-    PULSE_REQUIRE(a.parent_indices_host[0] == -1, "pulse_motion_build: body 0 must be the root (parent -1), got parent %d", a.parent_indices_host[0]);
-    for (int b = 1; b < J; ++b) {
-        const int p = a.parent_indices_host[b];
-        PULSE_REQUIRE(p >= 0 && p < b, "pulse_motion_build: parent_indices[%d] = %d: every parent must precede its child (0 <= parent < child)", b, p);
-        tree.parent[b] = (signed char)p;
-        tree.depth[b] = (unsigned char)(tree.depth[p] + 1);
-        if (tree.depth[b] > tree.max_depth) tree.max_depth = tree.depth[b];
-    }
+    BodyTree<kMbMaxBodies> tree;
+    if (const int rc = check_tree("pulse_motion_build", a.parent_indices_host, J, tree)) return rc;
     long long sum = 0;
     for (int m = 0; m < a.num_clips; ++m) {
         const long long f = a.clip_frames_host[m];
@@ -220,26 +201,17 @@ extern "C" int pulse_motion_build(const pulse_motion_build_args* args, pulse_str
         sum += f;
     }
     PULSE_REQUIRE(sum == a.total_frames, "pulse_motion_build: the clips hold %lld frames but total_frames is %lld", sum, (long long)a.total_frames);
-    // record layout: the six fields tile [0, 20 J - 3) without overlap, quaternion fields and the pitch on 16-byte boundaries
-    const int off[6] = {a.off_grs, a.off_lrs, a.off_gts, a.off_gvs, a.off_gavs, a.off_dvs};
-    const int wid[6] = {4 * J, 4 * J, 3 * J, 3 * J, 3 * J, 3 * (J - 1)};
-    const int used = 20 * J - 3;
-    for (int i = 0; i < 6; ++i) {
-        PULSE_REQUIRE(off[i] >= 0 && off[i] + wid[i] <= used, "pulse_motion_build: field offset %d (width %d) outside the %d floats a %d-body record uses", off[i], wid[i], used, J);
-        for (int k = 0; k < i; ++k)
-            PULSE_REQUIRE(wid[i] == 0 || wid[k] == 0 || off[i] + wid[i] <= off[k] || off[k] + wid[k] <= off[i], "pulse_motion_build: record fields at offsets %d and %d overlap", off[k], off[i]);
-    }
-    PULSE_REQUIRE(a.frame_stride % 4 == 0 && a.frame_stride >= used, "pulse_motion_build: frame_stride %lld must be a multiple of 4 and >= %d floats for %d bodies", (long long)a.frame_stride, used, J);
-    PULSE_REQUIRE(a.off_grs % 4 == 0 && a.off_lrs % 4 == 0, "pulse_motion_build: quaternion fields (off_grs, off_lrs) must start on 16-byte boundaries");
-    PULSE_REQUIRE(reinterpret_cast<uintptr_t>(a.frames) % 16 == 0, "pulse_motion_build: frames (the record base) must be 16-byte aligned");
+    if (const int rc = check_record_layout("pulse_motion_build", J, a.frame_stride, a.off_gts, a.off_grs, a.off_lrs, a.off_gvs, a.off_gavs, a.off_dvs, a.frames)) return rc;
     PULSE_REQUIRE(reinterpret_cast<uintptr_t>(a.src_rot) % 16 == 0, "pulse_motion_build: src_rot must be 16-byte aligned");
-    const int per_block = kMbThreads / (J > 32 ? 64 : 32);
-    const long long blocks1 = (a.total_frames + per_block - 1) / per_block, blocks2 = (a.total_frames + kMbTile - 1) / kMbTile;
-    PULSE_REQUIRE(blocks1 <= 0x7fffffffLL && blocks2 <= 0x7fffffffLL, "pulse_motion_build: %lld frames exceed the grid", (long long)a.total_frames);
-    if (J > 32) hipLaunchKernelGGL(motion_build_frames_kernel<64>, dim3((unsigned)blocks1), dim3(kMbThreads), 0, as_stream(s), a, tree, used);
-    else hipLaunchKernelGGL(motion_build_frames_kernel<32>, dim3((unsigned)blocks1), dim3(kMbThreads), 0, as_stream(s), a, tree, used);
+    const bool wide = J > kHalfWave;
+    unsigned blocks1, blocks2;
+    if (const int rc = lane_group_blocks("pulse_motion_build", a.total_frames, wide ? LaneGroup<64>::slots : LaneGroup<32>::slots, blocks1)) return rc;
+    if (const int rc = lane_group_blocks("pulse_motion_build", a.total_frames, kMbTile, blocks2)) return rc;
+    const int used = 20 * J - 3;                            // the padding columns start behind the six fields
+    if (wide) hipLaunchKernelGGL(motion_build_frames_kernel<64>, dim3(blocks1), dim3(LaneGroup<64>::threads), 0, as_stream(s), a, tree, used);
+    else hipLaunchKernelGGL(motion_build_frames_kernel<32>, dim3(blocks1), dim3(LaneGroup<32>::threads), 0, as_stream(s), a, tree, used);
     const int rc = check_launch("pulse_motion_build (frames)");
     if (rc != PULSE_OK) return rc;
-    hipLaunchKernelGGL(motion_build_velocity_kernel, dim3((unsigned)blocks2), dim3(kMbThreads), 0, as_stream(s), a);
+    hipLaunchKernelGGL(motion_build_velocity_kernel, dim3(blocks2), dim3(kMbThreads), 0, as_stream(s), a);
     return check_launch("pulse_motion_build (velocities)");
 }

@@ -20,16 +20,13 @@
 
 namespace pulse {
 
-constexpr int kMxThreads = 256;
-constexpr int kMxLanes = kHalfWave;              // lanes per frame = PULSE_EXPORT_MAX_BODIES
-constexpr int kMxSlots = kMxThreads / kMxLanes;  // frames per workgroup
+using MxGroup = LaneGroup<kHalfWave>;            // lanes per frame = PULSE_EXPORT_MAX_BODIES
 
-// the tree and the inverse joint map, by value in the kernel arguments (from the launcher's validated host copies)
-struct MxTree { signed char parent[kMxLanes]; unsigned char body_of_joint[kMxLanes]; };
+// the parents of the tree (the kernel reads no depth) and the inverse joint map, by value in the kernel arguments (from the launcher's validated host copies)
+struct MxTree { signed char parent[kHalfWave]; unsigned char body_of_joint[kHalfWave]; };
 
-__global__ void __launch_bounds__(kMxThreads) motion_export_kernel(const pulse_motion_export_args a, const MxTree tree) {
-    const int slot = threadIdx.x / kMxLanes, b = threadIdx.x % kMxLanes;
-    const long long g = (long long)blockIdx.x * kMxSlots + slot;
+__global__ void __launch_bounds__(MxGroup::threads) motion_export_kernel(const pulse_motion_export_args a, const MxTree tree) {
+    const auto [slot, b, g] = lane_group<kHalfWave>();
     const int J = a.num_bodies;
     const bool frame = g < a.total_frames;                 // no early return: every lane reaches every cross-lane read
     const bool body = frame && b < J;
@@ -46,7 +43,7 @@ __global__ void __launch_bounds__(kMxThreads) motion_export_kernel(const pulse_m
     if (body) {
         const float* r = row + b * a.rb_stride_b + 3;
         G = Q4{r[0], r[1], r[2], r[3]};
-        *reinterpret_cast<float4*>(a.out_rot + (g * J + b) * 4) = make_float4(G.x, G.y, G.z, G.w);
+        store_q4(a.out_rot + (g * J + b) * 4, G);
     }
     if (frame && b < 3) {
         const float p = row[b];
@@ -63,7 +60,7 @@ __global__ void __launch_bounds__(kMxThreads) motion_export_kernel(const pulse_m
     }
     // the dump's body_quat = [root quat, exp_map_to_quat(dof_pos)]
     const Q4 bq = b == 0 ? G : exp_map_to_q(e);
-    if (body && a.out_body_quat) *reinterpret_cast<float4*>(a.out_body_quat + (g * J + b) * 4) = make_float4(bq.x, bq.y, bq.z, bq.w);
+    if (body && a.out_body_quat) store_q4(a.out_body_quat + (g * J + b) * 4, bq);
     Q4 l;
     V3 rv;
     if (a.upright_start) {                                 // uniform over the launch
@@ -78,11 +75,10 @@ __global__ void __launch_bounds__(kMxThreads) motion_export_kernel(const pulse_m
         l = bq;
         rv = b == 0 ? q_to_exp_map(G) : e;
     }
-    if (body && a.out_pose_quat) *reinterpret_cast<float4*>(a.out_pose_quat + (g * J + b) * 4) = make_float4(l.x, l.y, l.z, l.w);
+    if (body && a.out_pose_quat) store_q4(a.out_pose_quat + (g * J + b) * 4, l);
     // lane <-> SMPL joint: pose_aa[:, mujoco_2_smpl]
-    const int src = b < J ? tree.body_of_joint[b] : 0;
-    const float ax = __shfl(rv.x, src, kMxLanes), ay = __shfl(rv.y, src, kMxLanes), az = __shfl(rv.z, src, kMxLanes);
-    if (body && a.out_pose_aa) { float* o = a.out_pose_aa + g * (3 * J) + 3 * b; o[0] = ax; o[1] = ay; o[2] = az; }
+    const V3 aa = lane_read(rv, b < J ? tree.body_of_joint[b] : 0);
+    if (body && a.out_pose_aa) { float* o = a.out_pose_aa + g * (3 * J) + 3 * b; o[0] = aa.x; o[1] = aa.y; o[2] = aa.z; }
 }
 
 }  // namespace pulse
@@ -91,13 +87,13 @@ extern "C" int pulse_sizeof_motion_export_args(void) { return (int)sizeof(pulse_
 
 extern "C" int pulse_motion_export(const pulse_motion_export_args* args, pulse_stream_t s) {
     using namespace pulse;
-    static_assert(PULSE_EXPORT_MAX_BODIES == kMxLanes, "one lane per body");
+    static_assert(PULSE_EXPORT_MAX_BODIES == kHalfWave, "one lane per body");
     PULSE_REQUIRE(args != nullptr, "pulse_motion_export: null args");
     const pulse_motion_export_args& a = *args;
     PULSE_REQUIRE(a.num_segments >= 0 && a.total_frames >= 0, "pulse_motion_export: negative segment / frame count");
     if (a.num_segments == 0 && a.total_frames == 0) return PULSE_OK;
     const int J = a.num_bodies;
-    PULSE_REQUIRE(J >= 1 && J <= kMxLanes, "pulse_motion_export: num_bodies %d not in [1,32] (one lane of a half-wave per body)", J);
+    PULSE_REQUIRE(J >= 1 && J <= kHalfWave, "pulse_motion_export: num_bodies %d not in [1,32] (one lane of a half-wave per body)", J);
     PULSE_REQUIRE(a.rb != nullptr, "pulse_motion_export: null recording (rb)");
     PULSE_REQUIRE(a.num_steps >= 1 && a.num_envs >= 1, "pulse_motion_export: the recording is empty (num_steps %lld, num_envs %d)", (long long)a.num_steps, a.num_envs);
     PULSE_REQUIRE(a.rb_stride_t >= 0 && a.rb_stride_n >= 0 && a.rb_stride_b >= 13,
@@ -107,27 +103,15 @@ extern "C" int pulse_motion_export(const pulse_motion_export_args* args, pulse_s
     PULSE_REQUIRE(a.seg_env && a.seg_t0 && a.seg_out_start, "pulse_motion_export: null per-segment table (seg_env / seg_t0 / seg_out_start)");
     PULSE_REQUIRE(a.seg_env_host && a.seg_t0_host && a.seg_frames_host,
                   "pulse_motion_export: null host table (seg_env_host / seg_t0_host / seg_frames_host)");
-    PULSE_REQUIRE(a.parent_indices_host != nullptr, "pulse_motion_export: null parent_indices_host");
     PULSE_REQUIRE(a.out_rot && a.out_trans, "pulse_motion_export: null output (out_rot / out_trans)");
     PULSE_REQUIRE(a.dof_pos != nullptr || !(a.out_body_quat || a.out_dof_pos), "pulse_motion_export: out_body_quat / out_dof_pos need dof_pos");
     PULSE_REQUIRE(a.dof_pos != nullptr || a.upright_start || !(a.out_pose_quat || a.out_pose_aa),
                   "pulse_motion_export: without upright_start out_pose_quat / out_pose_aa need dof_pos");
-    MxTree tree;
-    for (int b = 0; b < kMxLanes; ++b) { tree.parent[b] = -1; tree.body_of_joint[b] = 0; }
-    PULSE_REQUIRE(a.parent_indices_host[0] == -1, "pulse_motion_export: body 0 must be the root (parent -1), got parent %d", a.parent_indices_host[0]);
-    for (int b = 1; b < J; ++b) {
-        const int p = a.parent_indices_host[b];
-        PULSE_REQUIRE(p >= 0 && p < b, "pulse_motion_export: parent_indices[%d] = %d: every parent must precede its child (0 <= parent < child)", b, p);
-        tree.parent[b] = (signed char)p;
-    }
-    bool seen[kMxLanes] = {};
-    for (int b = 0; b < J; ++b) {
-        const int j = a.joint_map[b];
-        PULSE_REQUIRE(j >= 0 && j < J, "pulse_motion_export: joint_map[%d] = %d is no SMPL joint (0 .. %d)", b, j, J - 1);
-        PULSE_REQUIRE(!seen[j], "pulse_motion_export: joint_map[%d] = %d is taken twice: joint_map must be a permutation of 0 .. %d", b, j, J - 1);
-        seen[j] = true;
-        tree.body_of_joint[j] = (unsigned char)b;
-    }
+    BodyTree<kHalfWave> checked;
+    if (const int rc = check_tree("pulse_motion_export", a.parent_indices_host, J, checked)) return rc;
+    MxTree tree = {};
+    for (int b = 0; b < kHalfWave; ++b) tree.parent[b] = checked.parent[b];
+    if (const int rc = check_permutation<kHalfWave>("pulse_motion_export", "joint_map", a.joint_map, J, tree.body_of_joint)) return rc;
     long long sum = 0;
     for (int m = 0; m < a.num_segments; ++m) {
         const long long f = a.seg_frames_host[m], t0 = a.seg_t0_host[m], e = a.seg_env_host[m];
@@ -136,14 +120,15 @@ extern "C" int pulse_motion_export(const pulse_motion_export_args* args, pulse_s
         // t0 + f is not formed before it is known to fit
         PULSE_REQUIRE(t0 >= 0 && t0 < a.num_steps && f <= a.num_steps - t0,
                       "pulse_motion_export: segment %d reads %lld steps from %lld, outside [0,%lld)", m, f, t0, (long long)a.num_steps);
-        PULSE_REQUIRE(f <= 0x7fffffffLL * kMxSlots - sum, "pulse_motion_export: %lld and more frames exceed the grid", sum + f);
+        PULSE_REQUIRE(f <= 0x7fffffffLL * MxGroup::slots - sum, "pulse_motion_export: %lld and more frames exceed the grid", sum + f);
         sum += f;
     }
     PULSE_REQUIRE(sum == a.total_frames, "pulse_motion_export: the segments hold %lld frames but total_frames is %lld", sum, (long long)a.total_frames);
     PULSE_REQUIRE(reinterpret_cast<uintptr_t>(a.out_rot) % 16 == 0, "pulse_motion_export: out_rot must be 16-byte aligned");
     PULSE_REQUIRE(reinterpret_cast<uintptr_t>(a.out_pose_quat) % 16 == 0, "pulse_motion_export: out_pose_quat must be 16-byte aligned");
     PULSE_REQUIRE(reinterpret_cast<uintptr_t>(a.out_body_quat) % 16 == 0, "pulse_motion_export: out_body_quat must be 16-byte aligned");
-    const long long blocks = (a.total_frames + kMxSlots - 1) / kMxSlots;
-    hipLaunchKernelGGL(motion_export_kernel, dim3((unsigned)blocks), dim3(kMxThreads), 0, as_stream(s), a, tree);
+    unsigned blocks;
+    if (const int rc = lane_group_blocks("pulse_motion_export", a.total_frames, MxGroup::slots, blocks)) return rc;
+    hipLaunchKernelGGL(motion_export_kernel, dim3(blocks), dim3(MxGroup::threads), 0, as_stream(s), a, tree);
     return check_launch("pulse_motion_export");
 }

@@ -16,13 +16,8 @@
 
 namespace pulse {
 
-constexpr int kMiThreads = 256;
-constexpr int kMiLanes = 32;                     // lanes per frame = PULSE_INGEST_MAX_BODIES
-constexpr int kMiSlots = kMiThreads / kMiLanes;  // frames per workgroup
+using MiGroup = LaneGroup<kHalfWave>;            // lanes per frame = PULSE_INGEST_MAX_BODIES
 constexpr int kMiJoints = PULSE_INGEST_SMPL_JOINTS, kMiHandCol = PULSE_INGEST_SMPL_HAND_COL;
-
-// the tree, by value in the kernel arguments (from the launcher's validated host copy)
-struct MiTree { signed char parent[kMiLanes]; unsigned char depth[kMiLanes]; int max_depth; };
 
 // scipy Rotation.from_rotvec (_rotation.pyx): xyzw, Taylor series of sin(angle / 2) / angle at angle <= 1e-3, w = cos(angle / 2) as it comes
 __device__ __forceinline__ Q4 rotvec_to_quat(const float x, const float y, const float z) {
@@ -37,9 +32,8 @@ __device__ __forceinline__ Q4 rotvec_to_quat(const float x, const float y, const
     return Q4{scale * x, scale * y, scale * z, cosf(angle / 2.0f)};
 }
 
-__global__ void __launch_bounds__(kMiThreads) motion_ingest_kernel(const pulse_motion_ingest_args a, const MiTree tree) {
-    const int slot = threadIdx.x / kMiLanes, b = threadIdx.x % kMiLanes;
-    const long long g = (long long)blockIdx.x * kMiSlots + slot;
+__global__ void __launch_bounds__(MiGroup::threads) motion_ingest_kernel(const pulse_motion_ingest_args a, const BodyTree<kHalfWave> tree) {
+    const auto [slot, b, g] = lane_group<kHalfWave>();
     const int J = a.num_bodies;
     const bool frame = g < a.total_frames;                 // no early return: every lane reaches every cross-lane read
     const bool body = frame && b < J;
@@ -62,7 +56,8 @@ __global__ void __launch_bounds__(kMiThreads) motion_ingest_kernel(const pulse_m
     }
     // lane <-> body: pose_aa.reshape(-1, 24, 3)[:, smpl_2_mujoco] -> from_rotvec
     const int jm = b < J ? a.joint_map[b] : 0;
-    const Q4 q = rotvec_to_quat(__shfl(ax, jm, kMiLanes), __shfl(ay, jm, kMiLanes), __shfl(az, jm, kMiLanes));
+    const V3 aa = lane_read(V3{ax, ay, az}, jm);
+    const Q4 q = rotvec_to_quat(aa.x, aa.y, aa.z);
     // SkeletonState.global_rotation of local rotations: transform_mul's quat_mul_norm down the tree, the root as scipy gave it
     const int p = b < J ? tree.parent[b] : -1, ps = p < 0 ? 0 : p;
     const int depth = b < J ? tree.depth[b] : 0;
@@ -79,11 +74,11 @@ __global__ void __launch_bounds__(kMiThreads) motion_ingest_kernel(const pulse_m
         const Q4 Gp = lane_read(G, ps);
         l = p < 0 ? G : qmul_norm(qconj(Gp), G);
     }
-    if (body && a.out_pose_quat) *reinterpret_cast<float4*>(a.out_pose_quat + (g * J + b) * 4) = make_float4(l.x, l.y, l.z, l.w);
+    if (body && a.out_pose_quat) store_q4(a.out_pose_quat + (g * J + b) * 4, l);
     // the mirrored copy: pose_quat_global[:, left_to_right_index], x and z negated
     const Q4 Gm = lane_read(G, b < J ? a.mirror_map[b] : 0);
     if (mirror) G = Q4{-Gm.x, Gm.y, -Gm.z, Gm.w};
-    if (body) *reinterpret_cast<float4*>(a.out_rot + (g * J + b) * 4) = make_float4(G.x, G.y, G.z, G.w);
+    if (body) store_q4(a.out_rot + (g * J + b) * 4, G);
     if (frame && b < 3) {
         const float t = a.src_trans[3 * src + b];
         const float o = t + a.root_offset[b];
@@ -98,32 +93,22 @@ extern "C" int pulse_sizeof_motion_ingest_args(void) { return (int)sizeof(pulse_
 
 extern "C" int pulse_motion_ingest(const pulse_motion_ingest_args* args, pulse_stream_t s) {
     using namespace pulse;
-    static_assert(PULSE_INGEST_MAX_BODIES == kMiLanes, "one lane per body");
+    static_assert(PULSE_INGEST_MAX_BODIES == kHalfWave, "one lane per body");
     PULSE_REQUIRE(args != nullptr, "pulse_motion_ingest: null args");
     const pulse_motion_ingest_args& a = *args;
     PULSE_REQUIRE(a.num_clips >= 0 && a.total_frames >= 0, "pulse_motion_ingest: negative clip / frame count");
     if (a.num_clips == 0 && a.total_frames == 0) return PULSE_OK;
     const int J = a.num_bodies;
-    static_assert(kMiJoints <= kMiLanes && kMiHandCol % 3 == 0, "one lane per SMPL joint; the hand columns start at a joint");
-    PULSE_REQUIRE(J >= 1 && J <= kMiLanes, "pulse_motion_ingest: num_bodies %d not in [1,32] (one lane of a half-wave per body)", J);
+    static_assert(kMiJoints <= kHalfWave && kMiHandCol % 3 == 0, "one lane per SMPL joint; the hand columns start at a joint");
+    PULSE_REQUIRE(J >= 1 && J <= kHalfWave, "pulse_motion_ingest: num_bodies %d not in [1,32] (one lane of a half-wave per body)", J);
     PULSE_REQUIRE(a.src_pose && a.src_trans, "pulse_motion_ingest: null staging pointer (src_pose / src_trans)");
     PULSE_REQUIRE(a.src_frames >= 1, "pulse_motion_ingest: src_frames %lld: the staging buffers are empty", (long long)a.src_frames);
     PULSE_REQUIRE(a.clip_src_start && a.clip_skip && a.clip_out_start, "pulse_motion_ingest: null per-clip table (clip_src_start / clip_skip / clip_out_start)");
     PULSE_REQUIRE(a.clip_src_start_host && a.clip_skip_host && a.clip_frames_host,
                   "pulse_motion_ingest: null host table (clip_src_start_host / clip_skip_host / clip_frames_host)");
-    PULSE_REQUIRE(a.parent_indices_host != nullptr, "pulse_motion_ingest: null parent_indices_host");
     PULSE_REQUIRE(a.out_rot && a.out_trans, "pulse_motion_ingest: null output (out_rot / out_trans)");
-    MiTree tree;
-    tree.max_depth = 0;
-    for (int b = 0; b < kMiLanes; ++b) { tree.parent[b] = -1; tree.depth[b] = 0; }
-    PULSE_REQUIRE(a.parent_indices_host[0] == -1, "pulse_motion_ingest: body 0 must be the root (parent -1), got parent %d", a.parent_indices_host[0]);
-    for (int b = 1; b < J; ++b) {
-        const int p = a.parent_indices_host[b];
-        PULSE_REQUIRE(p >= 0 && p < b, "pulse_motion_ingest: parent_indices[%d] = %d: every parent must precede its child (0 <= parent < child)", b, p);
-        tree.parent[b] = (signed char)p;
-        tree.depth[b] = (unsigned char)(tree.depth[p] + 1);
-        if (tree.depth[b] > tree.max_depth) tree.max_depth = tree.depth[b];
-    }
+    BodyTree<kHalfWave> tree;
+    if (const int rc = check_tree("pulse_motion_ingest", a.parent_indices_host, J, tree)) return rc;
     for (int b = 0; b < J; ++b) {
         PULSE_REQUIRE(a.joint_map[b] >= 0 && a.joint_map[b] < kMiJoints, "pulse_motion_ingest: joint_map[%d] = %d is no SMPL joint (0 .. %d)", b, a.joint_map[b], kMiJoints - 1);
         PULSE_REQUIRE(a.mirror_map[b] >= 0 && a.mirror_map[b] < J, "pulse_motion_ingest: mirror_map[%d] = %d is no body (0 .. %d)", b, a.mirror_map[b], J - 1);
@@ -141,8 +126,8 @@ extern "C" int pulse_motion_ingest(const pulse_motion_ingest_args* args, pulse_s
     PULSE_REQUIRE(sum == a.total_frames, "pulse_motion_ingest: the clips hold %lld frames but total_frames is %lld", sum, (long long)a.total_frames);
     PULSE_REQUIRE(reinterpret_cast<uintptr_t>(a.out_rot) % 16 == 0, "pulse_motion_ingest: out_rot must be 16-byte aligned");
     PULSE_REQUIRE(reinterpret_cast<uintptr_t>(a.out_pose_quat) % 16 == 0, "pulse_motion_ingest: out_pose_quat must be 16-byte aligned");
-    const long long blocks = (a.total_frames + kMiSlots - 1) / kMiSlots;
-    PULSE_REQUIRE(blocks <= 0x7fffffffLL, "pulse_motion_ingest: %lld frames exceed the grid", (long long)a.total_frames);
-    hipLaunchKernelGGL(motion_ingest_kernel, dim3((unsigned)blocks), dim3(kMiThreads), 0, as_stream(s), a, tree);
+    unsigned blocks;
+    if (const int rc = lane_group_blocks("pulse_motion_ingest", a.total_frames, MiGroup::slots, blocks)) return rc;
+    hipLaunchKernelGGL(motion_ingest_kernel, dim3(blocks), dim3(MiGroup::threads), 0, as_stream(s), a, tree);
     return check_launch("pulse_motion_ingest");
 }

@@ -2,8 +2,7 @@
 // MotionLibBase._calc_frame_blend and the per-body blend of two packed frame records
 // (phc/utils/motion_lib_base.py:434-517, 546-557).  Compile with -ffp-contract=off.
 #pragma once
-#include "common.h"
-#include "rot_math.h"
+#include "body_lanes.h"
 
 namespace pulse {
 
@@ -33,23 +32,25 @@ __device__ __forceinline__ V3 lerp3(const float* p0, const float* p1, float b) {
 // body j of the blended frame: position (+ offset), global rotation, linear / angular velocity
 struct BodyState { V3 p; Q4 q; V3 v; V3 w; };
 
+// the 13-float rigid-body record of a body: position, rotation, linear / angular velocity
+__device__ __forceinline__ void store_record(float* rec, const BodyState s) {
+    rec[0] = s.p.x; rec[1] = s.p.y; rec[2] = s.p.z; rec[3] = s.q.x; rec[4] = s.q.y; rec[5] = s.q.z; rec[6] = s.q.w;
+    rec[7] = s.v.x; rec[8] = s.v.y; rec[9] = s.v.z; rec[10] = s.w.x; rec[11] = s.w.y; rec[12] = s.w.z;
+}
+
 __device__ __forceinline__ BodyState blend_body(const pulse_motion_tables& T, const float* r0, const float* r1, float b, int j, const float* offset) {
     BodyState s;
     s.p = lerp3(r0 + T.off_gts + 3 * j, r1 + T.off_gts + 3 * j, b);
     if (offset) { s.p.x = s.p.x + offset[0]; s.p.y = s.p.y + offset[1]; s.p.z = s.p.z + offset[2]; }
     s.v = lerp3(r0 + T.off_gvs + 3 * j, r1 + T.off_gvs + 3 * j, b);
     s.w = lerp3(r0 + T.off_gavs + 3 * j, r1 + T.off_gavs + 3 * j, b);
-    const float4 q0 = *reinterpret_cast<const float4*>(r0 + T.off_grs + 4 * j);
-    const float4 q1 = *reinterpret_cast<const float4*>(r1 + T.off_grs + 4 * j);
-    s.q = slerp(Q4{q0.x, q0.y, q0.z, q0.w}, Q4{q1.x, q1.y, q1.z, q1.w}, b);
+    s.q = slerp(load_q4(r0 + T.off_grs + 4 * j), load_q4(r1 + T.off_grs + 4 * j), b);
     return s;
 }
 
 // dof joint d (= body d + 1): exp-map of the slerped local rotation and the blended dof velocity
 __device__ __forceinline__ void blend_dof(const pulse_motion_tables& T, const float* r0, const float* r1, float b, int d, V3* pos, V3* vel) {
-    const float4 q0 = *reinterpret_cast<const float4*>(r0 + T.off_lrs + 4 * (d + 1));
-    const float4 q1 = *reinterpret_cast<const float4*>(r1 + T.off_lrs + 4 * (d + 1));
-    const Q4 q = slerp(Q4{q0.x, q0.y, q0.z, q0.w}, Q4{q1.x, q1.y, q1.z, q1.w}, b);
+    const Q4 q = slerp(load_q4(r0 + T.off_lrs + 4 * (d + 1)), load_q4(r1 + T.off_lrs + 4 * (d + 1)), b);
     V3 ax;
     const float ang = q_to_angle_axis(q, &ax);               // quat_to_exp_map, torch_utils.py:81-97
     *pos = V3{ang * ax.x, ang * ax.y, ang * ax.z};

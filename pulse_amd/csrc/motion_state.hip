@@ -15,7 +15,6 @@
 
 namespace pulse {
 
-constexpr int kMsThreads = 256;
 constexpr int kMsMaxBodies = 64;
 
 __device__ __forceinline__ float query_time(const pulse_motion_state_args& a, long long i, long long e) {
@@ -27,11 +26,10 @@ __device__ __forceinline__ float query_time(const pulse_motion_state_args& a, lo
     return t;
 }
 
-// LB lanes per query (32 | 64), kMsThreads / LB queries per block; every lane works on its own body: no cross-lane traffic
+// LB lanes per query (32 | 64); every lane works on its own body: no cross-lane traffic
 template <int LB>
-__global__ void __launch_bounds__(kMsThreads) motion_state_kernel(const pulse_motion_state_args a) {
-    const int slot = threadIdx.x / LB, lane = threadIdx.x % LB;
-    const long long i = (long long)blockIdx.x * (kMsThreads / LB) + slot;
+__global__ void __launch_bounds__(LaneGroup<LB>::threads) motion_state_kernel(const pulse_motion_state_args a) {
+    const auto [slot, lane, i] = lane_group<LB>();
     if (i >= a.n) return;
     const pulse_motion_tables& T = a.tab;
     const long long e = a.motion_times ? i : i / (a.time_steps > 1 ? a.time_steps : 1);     // per-env arrays in clock mode
@@ -81,14 +79,8 @@ __global__ void __launch_bounds__(kMsThreads) motion_state_kernel(const pulse_mo
         if (a.rg_pos) { float* o = a.rg_pos + (i * J + j) * 3; o[0] = s.p.x; o[1] = s.p.y; o[2] = s.p.z; }
         if (a.body_vel) { float* o = a.body_vel + (i * J + j) * 3; o[0] = s.v.x; o[1] = s.v.y; o[2] = s.v.z; }
         if (a.body_ang_vel) { float* o = a.body_ang_vel + (i * J + j) * 3; o[0] = s.w.x; o[1] = s.w.y; o[2] = s.w.z; }
-        if (a.rb_rot) *reinterpret_cast<float4*>(a.rb_rot + (i * J + j) * 4) = make_float4(s.q.x, s.q.y, s.q.z, s.q.w);
-        if (a.rb_records) {
-            float* rec = a.rb_records + i * a.rb_query_stride + 13 * j;
-            rec[0] = s.p.x; rec[1] = s.p.y; rec[2] = s.p.z;
-            rec[3] = s.q.x; rec[4] = s.q.y; rec[5] = s.q.z; rec[6] = s.q.w;
-            rec[7] = s.v.x; rec[8] = s.v.y; rec[9] = s.v.z;
-            rec[10] = s.w.x; rec[11] = s.w.y; rec[12] = s.w.z;
-        }
+        if (a.rb_rot) store_q4(a.rb_rot + (i * J + j) * 4, s.q);
+        if (a.rb_records) store_record(a.rb_records + i * a.rb_query_stride + 13 * j, s);
     }
     if (lane < J - 1 && (a.dof_pos || a.dof_vel)) {
         const int d = lane, nd = 3 * (J - 1);
@@ -110,19 +102,17 @@ extern "C" int pulse_motion_state(const pulse_motion_state_args* args, pulse_str
     const pulse_motion_tables& T = a.tab;
     PULSE_REQUIRE(a.n >= 0, "pulse_motion_state: negative query count");
     if (a.n == 0) return PULSE_OK;
-    PULSE_REQUIRE(T.frames && T.motion_lengths && T.motion_dt && T.motion_num_frames && T.length_starts, "pulse_motion_state: null table pointer");
-    PULSE_REQUIRE(T.num_bodies >= 1 && T.num_bodies <= kMsMaxBodies, "pulse_motion_state: num_bodies %d not in [1,64]", T.num_bodies);
-    PULSE_REQUIRE(T.frame_stride % 4 == 0 && T.off_grs % 4 == 0 && T.off_lrs % 4 == 0, "pulse_motion_state: record pitch / quaternion fields must be 16-B aligned");
-    PULSE_REQUIRE(T.off_gts >= 0 && T.off_grs >= 0 && T.off_lrs >= 0 && T.off_gvs >= 0 && T.off_gavs >= 0 && T.off_dvs >= 0, "pulse_motion_state: negative field offset");
+    if (const int rc = check_motion_tables("pulse_motion_state", T, kMsMaxBodies)) return rc;
     PULSE_REQUIRE(a.motion_ids != nullptr, "pulse_motion_state: null motion_ids");
     PULSE_REQUIRE(a.motion_times != nullptr || a.progress != nullptr || a.reset_mask != nullptr, "pulse_motion_state: need motion_times, progress or reset_mask");
     PULSE_REQUIRE(a.reset_mask == nullptr || (a.motion_times == nullptr && a.time_steps <= 1), "pulse_motion_state: reset mode is per env");
     PULSE_REQUIRE(!a.root_only || a.root_pos != nullptr, "pulse_motion_state: root_only needs root_pos");
     PULSE_REQUIRE(a.motion_times != nullptr || a.time_steps <= 1 || a.n % a.time_steps == 0, "pulse_motion_state: n must be num_envs * time_steps");
     PULSE_REQUIRE(a.rb_records == nullptr || a.rb_query_stride >= 13 * T.num_bodies, "pulse_motion_state: rb_query_stride too small");
-    const int per_block = kMsThreads / (T.num_bodies > 32 ? 64 : 32);
-    const long long blocks = (a.n + per_block - 1) / per_block;
-    if (T.num_bodies > 32) hipLaunchKernelGGL(motion_state_kernel<64>, dim3((unsigned)blocks), dim3(kMsThreads), 0, as_stream(s), a);
-    else hipLaunchKernelGGL(motion_state_kernel<32>, dim3((unsigned)blocks), dim3(kMsThreads), 0, as_stream(s), a);
+    const bool wide = T.num_bodies > kHalfWave;
+    unsigned blocks;
+    if (const int rc = lane_group_blocks("pulse_motion_state", a.n, wide ? LaneGroup<64>::slots : LaneGroup<32>::slots, blocks)) return rc;
+    if (wide) hipLaunchKernelGGL(motion_state_kernel<64>, dim3(blocks), dim3(LaneGroup<64>::threads), 0, as_stream(s), a);
+    else hipLaunchKernelGGL(motion_state_kernel<32>, dim3(blocks), dim3(LaneGroup<32>::threads), 0, as_stream(s), a);
     return check_launch("pulse_motion_state");
 }

@@ -3,8 +3,7 @@
 // (motion_build.hip, motion_ingest.hip, motion_export.hip).
 // Compile with -ffp-contract=off.
 #pragma once
-#include "common.h"
-#include "rot_math.h"
+#include "body_lanes.h"
 
 namespace pulse {
 
@@ -45,12 +44,6 @@ __device__ __forceinline__ Q4 qcompose_scipy(const Q4 p, const Q4 q) {
     r.z = p.w * q.z + q.w * p.z + cz;
     r.w = p.w * q.w - p.x * q.x - p.y * q.y - p.z * q.z;
     return r;
-}
-
-// a quaternion from another lane of the 32-lane half-wave (every lane of the wave must execute it)
-constexpr int kHalfWave = 32;
-__device__ __forceinline__ Q4 lane_read(const Q4 q, const int lane) {
-    return Q4{__shfl(q.x, lane, kHalfWave), __shfl(q.y, lane, kHalfWave), __shfl(q.z, lane, kHalfWave), __shfl(q.w, lane, kHalfWave)};
 }
 
 // scipy Rotation.as_rotvec (_rotation.pyx) of Rotation.from_quat(q): normalise, w made >= 0, angle = 2 atan2(|xyz|, w), the Taylor series of

@@ -23,9 +23,7 @@
 
 namespace pulse {
 
-constexpr int kTrThreads = 256;
-constexpr int kTrLanes = 32;                          // lanes per env = the most bodies
-constexpr int kTrEnvs = kTrThreads / kTrLanes;
+constexpr int kTrLanes = kHalfWave, kTrThreads = LaneGroup<kTrLanes>::threads, kTrEnvs = LaneGroup<kTrLanes>::slots;      // lanes per env = the most bodies
 constexpr int kTrRec = 13 * kTrLanes;
 constexpr int kTrDof = 3 * (kTrLanes - 1);
 
@@ -35,8 +33,7 @@ __global__ void __launch_bounds__(kTrThreads) task_reset_kernel(const pulse_task
     __shared__ float s_dv[kTrEnvs][kTrDof];
     __shared__ float s_root[kTrEnvs][8];              // blended root: position, rotation
     __shared__ float s_cpt[kTrEnvs][kTrLanes];        // centre-grid heights
-    const int slot = threadIdx.x / kTrLanes, lane = threadIdx.x % kTrLanes;
-    const long long e = (long long)blockIdx.x * kTrEnvs + slot;
+    const auto [slot, lane, e] = lane_group<kTrLanes>();
     const pulse_motion_tables& T = a.tab;
     const int J = T.num_bodies;
     long long m = 0;
@@ -107,11 +104,7 @@ __global__ void __launch_bounds__(kTrThreads) task_reset_kernel(const pulse_task
             s.p.y = lane == 0 ? ny : s.p.y + dy;
             s.p.z = s.p.z + center;
         }
-        float* rec = s_rec[slot] + 13 * lane;
-        rec[0] = s.p.x; rec[1] = s.p.y; rec[2] = s.p.z;
-        rec[3] = s.q.x; rec[4] = s.q.y; rec[5] = s.q.z; rec[6] = s.q.w;
-        rec[7] = s.v.x; rec[8] = s.v.y; rec[9] = s.v.z;
-        rec[10] = s.w.x; rec[11] = s.w.y; rec[12] = s.w.z;
+        store_record(s_rec[slot] + 13 * lane, s);
     }
     __syncthreads();
     if (!active) return;
@@ -143,10 +136,7 @@ extern "C" int pulse_task_ref_state_init(const pulse_task_reset_args* args, puls
     PULSE_REQUIRE(T.num_bodies >= 2 && T.num_bodies <= kTrLanes, "pulse_task_ref_state_init: num_bodies %d not in [2,32] (a 32-lane half-wave per env, lane = body)",
                   T.num_bodies);
     if (a.num_envs == 0) return PULSE_OK;
-    PULSE_REQUIRE(T.frames && T.motion_lengths && T.motion_dt && T.motion_num_frames && T.length_starts && T.num_motions >= 1,
-                  "pulse_task_ref_state_init: null table pointer");
-    PULSE_REQUIRE(T.frame_stride % 4 == 0 && T.off_grs % 4 == 0 && T.off_lrs % 4 == 0, "pulse_task_ref_state_init: record pitch / quaternion fields must be 16-B aligned");
-    PULSE_REQUIRE(T.off_gts >= 0 && T.off_grs >= 0 && T.off_lrs >= 0 && T.off_gvs >= 0 && T.off_gavs >= 0 && T.off_dvs >= 0, "pulse_task_ref_state_init: negative field offset");
+    if (const int rc = check_motion_tables("pulse_task_ref_state_init", T, kTrLanes)) return rc;
     PULSE_REQUIRE(a.transform >= PULSE_TASK_RESET_NONE && a.transform <= PULSE_TASK_RESET_TERRAIN, "pulse_task_ref_state_init: unknown transform %d", a.transform);
     PULSE_REQUIRE(a.env_mask && a.motion_ids && a.times, "pulse_task_ref_state_init: null env_mask / motion_ids / times");
     PULSE_REQUIRE(a.rb && a.rb_env_stride >= 13LL * T.num_bodies && a.dof_pos && a.dof_vel && a.start_times && a.sampled_ids,
@@ -157,7 +147,8 @@ extern "C" int pulse_task_ref_state_init(const pulse_task_reset_args* args, puls
         PULSE_REQUIRE(!a.heightsamples || (a.center_points && a.num_center_points >= 1 && a.num_center_points <= kTrLanes),
                       "pulse_task_ref_state_init: TERRAIN needs the centre grid (1 .. 32 points)");
     }
-    const long long blocks = ((long long)a.num_envs + kTrEnvs - 1) / kTrEnvs;
-    hipLaunchKernelGGL(task_reset_kernel, dim3((unsigned)blocks), dim3(kTrThreads), 0, as_stream(s), a);
+    unsigned blocks;
+    if (const int rc = lane_group_blocks("pulse_task_ref_state_init", a.num_envs, kTrEnvs, blocks)) return rc;
+    hipLaunchKernelGGL(task_reset_kernel, dim3(blocks), dim3(kTrThreads), 0, as_stream(s), a);
     return check_launch("pulse_task_ref_state_init");
 }
