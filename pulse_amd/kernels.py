@@ -545,6 +545,10 @@ def motion_export(out_rot, out_trans, *, rb, seg_env, seg_t0, seg_frames, parent
         if tuple(dof_pos.shape) != (steps, envs, 3 * (j - 1)):
             raise ValueError(f"dof_pos: expected {(steps, envs, 3 * (j - 1))}, got {tuple(dof_pos.shape)}")
         a.dof_stride_t, a.dof_stride_n = dof_pos.stride(0), dof_pos.stride(1)
+        if j == 1:
+            # a single body has no joint: dof_pos is zero floats wide, torch gives an empty tensor no address, and the launcher would take the
+            # null for "no dof_pos" and refuse out_body_quat.  No float of it is read at J = 1; the recording's address says "present".
+            a.dof_pos = a.rb
     total, dev = int(seg_frames.sum()), out_rot.device
     for name, t, shape in (("out_rot", out_rot, (total, j, 4)), ("out_trans", out_trans, (total, 3)), ("out_pose_quat", out_pose_quat, (total, j, 4)),
                            ("out_pose_aa", out_pose_aa, (total, 3 * j)), ("out_trans_orig", out_trans_orig, (total, 3)),
