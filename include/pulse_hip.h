@@ -545,6 +545,67 @@ int pulse_sizeof_motion_ingest_args(void);
 int pulse_motion_ingest(const pulse_motion_ingest_args* args, pulse_stream_t s);
 
 /* ------------------------------------------------------------------------- *
+ * 2b'.1a. Generated (text-to-motion) SMPL motion around section 2b'.1: what scripts/data_process/convert_data_mdm.py does before and
+ *      after the conversion pulse_motion_ingest stands for (:102-126), for every frame of every clip of a packed buffer.
+ *      pulse_motion_euler_pose (:48-61), one launch, a 32-lane half-wave per frame, lane = SMPL joint:
+ *        pose    joint s = Rotation.from_euler('XYZ', theta[s], degrees=True).as_rotvec(): deg2rad, the three elementary quaternions
+ *                composed left to right (intrinsic), as_rotvec (w made >= 0, 2 atan2(|xyz|, w), the Taylor series at angle <= 1e-3);
+ *        root    joint 0 = (transform * Rotation.from_rotvec(root)).as_rotvec() with transform = root_quat (from_euler('xyz', [pi/2, 0, 0]));
+ *        trans   trans . trans_matrix^T (transform.as_matrix()), then z - (z of frame 0 of the frame's own clip - floor_height).
+ *      Evaluated in DOUBLE as scipy evaluates it whatever the dtype of its input, rounded once on the store.  out_pose / out_trans are
+ *      the (F, 72) / (F, 3) staging rows pulse_motion_ingest reads (skip 1, clip m at clip_start[m]).
+ *      pulse_motion_smooth (:128-141), three launches, over the (total, J, 4) globals and (total, 3) root translations ingest wrote:
+ *        sign    quat_correct per body along every clip: frame t is negated when, against the corrected frame t - 1,
+ *                |q[t-1] - q[t]| > |q[t-1] + q[t]| (strict; the criterion :135 states); frame 0 of a clip never.  Bit b of sign_words[g] = the
+ *                raw test of body b between frames g - 1 and g, then the prefix XOR along the clip (a wave per clip, 64 frames a step);
+ *        rot     scipy gaussian_filter1d(sigma 2, axis 0, mode "nearest") of the corrected globals: 2 radius_rot + 1 taps, the tap index
+ *                clamped to the frame's own clip, summed in correlate1d's order and double accumulator, rounded to fp32; then / its norm;
+ *        local   out_pose_quat = SkeletonState.local_rotation of the filtered globals (skeleton3d.py:444-460);
+ *        trans   gaussian_filter1d(sigma 3) of the root translation, the same way.
+ *      w_rot / w_trans: scipy _gaussian_kernel1d's weights of |tap| = 0 .. radius in double (pulse_amd.kernels.gaussian_taps); a radius
+ *      of -1 leaves that filter out (rot: the sign-corrected input, bit for bit, NOT renormalised).  The filters read their neighbours'
+ *      unfiltered values: no output may overlap an input.  Nothing is launched unless every argument passes.
+ * ------------------------------------------------------------------------- */
+#define PULSE_SMOOTH_MAX_RADIUS 12
+typedef struct pulse_motion_euler_pose_args {
+    const float* src_theta;             /* (total_frames, 72) Euler 'XYZ' angles in degrees, SMPL joint order, device */
+    const float* src_trans;             /* (total_frames, 3) device */
+    int64_t total_frames;
+    int32_t num_clips;
+    int32_t reserved;
+    const int64_t* clip_start;          /* (M + 1) device: first frame of clip m; [M] = total_frames */
+    const int64_t* clip_frames_host;    /* (M) HOST: validated before anything is launched (>= 1 each, sum = total_frames) */
+    double root_quat[4];                /* xyzw of the rotation composed on the left of the root */
+    double trans_matrix[9];             /* its matrix, row-major */
+    double floor_height;                /* z of every clip's first frame (0.92) */
+    float* out_pose;                    /* (total_frames, 72) axis-angle rows, device; must not overlap src_theta */
+    float* out_trans;                   /* (total_frames, 3) device; must not overlap src_trans */
+} pulse_motion_euler_pose_args;
+int pulse_sizeof_motion_euler_pose_args(void);
+int pulse_motion_euler_pose(const pulse_motion_euler_pose_args* args, pulse_stream_t s);
+
+typedef struct pulse_motion_smooth_args {
+    const float* in_rot;                /* (total_frames, J, 4) global rotations xyzw, device, 16-byte aligned */
+    const float* in_trans;              /* (total_frames, 3) root translations, device */
+    int64_t total_frames;
+    int32_t num_clips;
+    int32_t num_bodies;                 /* J in [1, 32] */
+    const int64_t* clip_start;          /* (M + 1) device: first frame of clip m; [M] = total_frames */
+    const int64_t* clip_frames_host;    /* (M) HOST: validated before anything is launched (>= 1 each, sum = total_frames) */
+    const int32_t* parent_indices_host; /* (J) HOST: -1 for body 0, parent < child */
+    uint32_t* sign_words;               /* (total_frames) device workspace: bit b of word g = body b of frame g is negated */
+    int32_t radius_rot;                 /* taps each side, 0 .. 12; -1: no filter */
+    int32_t radius_trans;
+    double w_rot[PULSE_SMOOTH_MAX_RADIUS + 1];    /* weights of |tap| = 0 .. radius */
+    double w_trans[PULSE_SMOOTH_MAX_RADIUS + 1];
+    float* out_rot;                     /* (total_frames, J, 4) device, 16-byte aligned */
+    float* out_trans;                   /* (total_frames, 3) device */
+    float* out_pose_quat;               /* (total_frames, J, 4) optional, 16-byte aligned */
+} pulse_motion_smooth_args;
+int pulse_sizeof_motion_smooth_args(void);
+int pulse_motion_smooth(const pulse_motion_smooth_args* args, pulse_stream_t s);
+
+/* ------------------------------------------------------------------------- *
  * 2b'.2. A recorded rollout -> motion clips and SMPL pose sequences: the way back out of section 2b'.1.  What the reference does frame by
  *      frame on the CPU -- HumanoidIm.render's conversion of the simulator's body rotations into SMPL pose_aa / trans
  *      (phc/env/tasks/humanoid_im.py:217-257) and Humanoid._write_states_to_file's per-episode dump (phc/env/tasks/humanoid.py:439-491) --

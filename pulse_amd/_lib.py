@@ -7,7 +7,7 @@ loudly (build it with ``python pulse_amd/csrc/build.py`` or
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PULSE_HIP_LIB: another build of the SAME library (tools/im_step_repro.py compares compile variants); default = the in-tree build
@@ -56,6 +56,19 @@ class MotionIngestArgs(Structure):
                 ("joint_map", c_int32 * 32), ("mirror_map", c_int32 * 32), ("upright_start", c_int32), ("root_offset", c_float * 3),
                 ("out_rot", c_void_p), ("out_trans", c_void_p), ("out_pose_quat", c_void_p), ("out_pose_aa", c_void_p), ("out_trans_orig", c_void_p),
                 ("total_frames", c_int64)]
+
+
+class MotionEulerPoseArgs(Structure):
+    _fields_ = [("src_theta", c_void_p), ("src_trans", c_void_p), ("total_frames", c_int64), ("num_clips", c_int32), ("reserved", c_int32),
+                ("clip_start", c_void_p), ("clip_frames_host", c_void_p), ("root_quat", c_double * 4), ("trans_matrix", c_double * 9),
+                ("floor_height", c_double), ("out_pose", c_void_p), ("out_trans", c_void_p)]
+
+
+class MotionSmoothArgs(Structure):
+    _fields_ = [("in_rot", c_void_p), ("in_trans", c_void_p), ("total_frames", c_int64), ("num_clips", c_int32), ("num_bodies", c_int32),
+                ("clip_start", c_void_p), ("clip_frames_host", c_void_p), ("parent_indices_host", c_void_p), ("sign_words", c_void_p),
+                ("radius_rot", c_int32), ("radius_trans", c_int32), ("w_rot", c_double * 13), ("w_trans", c_double * 13),
+                ("out_rot", c_void_p), ("out_trans", c_void_p), ("out_pose_quat", c_void_p)]
 
 
 class MotionExportArgs(Structure):
@@ -408,6 +421,10 @@ SIGNATURES = {
     "pulse_motion_build": (c_int, [POINTER(MotionBuildArgs), P]),
     "pulse_sizeof_motion_ingest_args": (c_int, []),
     "pulse_motion_ingest": (c_int, [POINTER(MotionIngestArgs), P]),
+    "pulse_sizeof_motion_euler_pose_args": (c_int, []),
+    "pulse_motion_euler_pose": (c_int, [POINTER(MotionEulerPoseArgs), P]),
+    "pulse_sizeof_motion_smooth_args": (c_int, []),
+    "pulse_motion_smooth": (c_int, [POINTER(MotionSmoothArgs), P]),
     "pulse_sizeof_motion_export_args": (c_int, []),
     "pulse_motion_export": (c_int, [POINTER(MotionExportArgs), P]),
     "pulse_sizeof_keypoint_push_args": (c_int, []),

@@ -287,7 +287,9 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
     'motion_data' = the same, with the library built on the device from synthetic RAW clips (MotionLib.from_motion_data: one resident clip per
     env out of ``num_clips`` unique ones -- min(num_envs, 1024) / 2 + 1 unless given -- re-drawn by resample_motions);
     'smpl_data' = the same one step earlier: synthetic raw SMPL pose sequences (axis-angle poses at 30 / 60 / 120 Hz) converted on the device by
-    MotionLib.from_smpl_data (SMPL humanoid only).
+    MotionLib.from_smpl_data (SMPL humanoid only);
+    'mdm_data' = the same from synthetic GENERATED motion (per-joint Euler angles in degrees, 196 jittery frames a clip, as a text-to-motion
+    model emits it): converted, sign-corrected and smoothed on the device by MotionLib.from_mdm_data (SMPL humanoid only).
     ``robot_overrides``: cfg.robot keys on top of the humanoid's (bias_offset, has_smpl_pd_offset, freeze_toe, freeze_hand, ...).
     ``dof_limits``: the joint limits the stand-in simulator publishes -- None (none: the PD-target table stays offset 0 / scale 1), True
     (synthetic.synthetic_dof_limits of the humanoid) or a (lower, upper) pair.
@@ -381,7 +383,7 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
     if env_kind == "amp":
         env_cfg.update({"enable_amp_obs": True, "numAMPObsSteps": 10})
     env_cfg.update(env_overrides or {})
-    if reference in ("motion_lib", "motion_data", "smpl_data"):
+    if reference in ("motion_lib", "motion_data", "smpl_data", "mdm_data"):
         from . import synthetic as syn
         from .env.motion_lib import MotionLib
         from .env.sim import KinematicSim, PdSim
@@ -402,6 +404,14 @@ def make_env(num_envs, horizon, device, seed=1234, rank=0, rollout=None, env_kin
             data, trees = syn.synthetic_smpl_data(g, clips, framerate=[(30, 60, 120)[c % 3] for c in range(clips)], num_slots=num_envs)
             bodies, limb = syn.motion_shape_rows(syn.make_generator(7117), num_envs)
             motion = MotionLib.from_smpl_data(data, trees, gender_betas=bodies, limb_weights=limb, device=device, generator=g)
+        elif reference == "mdm_data":
+            if syn.skeleton(humanoid) is not syn.SKELETONS["smpl"]:
+                raise NotImplementedError(f"make_env: reference 'mdm_data' converts generated SMPL motion; humanoid {humanoid!r} is not built")
+            g = syn.make_generator(seed + 5, rank)
+            clips = min(num_envs, 1024) // 2 + 1 if num_clips is None else int(num_clips)
+            result, trees = syn.synthetic_mdm_result(g, clips, jitter=1.0, num_slots=num_envs)
+            bodies, limb = syn.motion_shape_rows(syn.make_generator(7117), num_envs)
+            motion = MotionLib.from_mdm_data(result, trees, gender_betas=bodies, limb_weights=limb, device=device, generator=g)
         else:
             tables = syn.synthetic_motion_library(syn.make_generator(seed + 5, rank), min(num_envs, 1024), humanoid=humanoid, shape_rows=disc_rows)
             motion = MotionLib.from_tables(tables, device)

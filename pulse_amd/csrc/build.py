@@ -43,6 +43,7 @@ SOURCES = [
     ("task_reset.hip", NO_CONTRACT),
     ("motion_build.hip", NO_CONTRACT),
     ("motion_ingest.hip", NO_CONTRACT),
+    ("motion_smooth.hip", NO_CONTRACT),
     ("motion_export.hip", NO_CONTRACT),
     ("keypoint_stream.hip", NO_CONTRACT),
     ("eval_metrics.hip", NO_CONTRACT),

@@ -19,19 +19,6 @@ namespace pulse {
 using MiGroup = LaneGroup<kHalfWave>;            // lanes per frame = PULSE_INGEST_MAX_BODIES
 constexpr int kMiJoints = PULSE_INGEST_SMPL_JOINTS, kMiHandCol = PULSE_INGEST_SMPL_HAND_COL;
 
-// scipy Rotation.from_rotvec (_rotation.pyx): xyzw, Taylor series of sin(angle / 2) / angle at angle <= 1e-3, w = cos(angle / 2) as it comes
-__device__ __forceinline__ Q4 rotvec_to_quat(const float x, const float y, const float z) {
-    const float angle = sqrtf(x * x + y * y + z * z);
-    float scale;
-    if ((double)angle <= 1e-3) {
-        const float a2 = angle * angle;
-        scale = 0.5f - a2 / 48.0f + a2 * a2 / 3840.0f;
-    } else {
-        scale = sinf(angle / 2.0f) / angle;
-    }
-    return Q4{scale * x, scale * y, scale * z, cosf(angle / 2.0f)};
-}
-
 __global__ void __launch_bounds__(MiGroup::threads) motion_ingest_kernel(const pulse_motion_ingest_args a, const BodyTree<kHalfWave> tree) {
     const auto [slot, b, g] = lane_group<kHalfWave>();
     const int J = a.num_bodies;

@@ -1,6 +1,6 @@
 // poselib's quaternion algebra (poselib/core/rotation3d.py) and the scipy Rotation calls the conversion scripts make, in fp32, terms in the
 // reference's order, and the clip lookup of a packed table: shared by the kernels that stand for poselib / scipy calls on whole clips
-// (motion_build.hip, motion_ingest.hip, motion_export.hip).
+// (motion_build.hip, motion_ingest.hip, motion_smooth.hip, motion_export.hip).
 // Compile with -ffp-contract=off.
 #pragma once
 #include "body_lanes.h"
@@ -46,6 +46,18 @@ __device__ __forceinline__ Q4 qcompose_scipy(const Q4 p, const Q4 q) {
     return r;
 }
 
+// scipy Rotation.from_rotvec (_rotation.pyx): xyzw, Taylor series of sin(angle / 2) / angle at angle <= 1e-3, w = cos(angle / 2) as it comes
+__device__ __forceinline__ Q4 rotvec_to_quat(const float x, const float y, const float z) {
+    const float angle = sqrtf(x * x + y * y + z * z);
+    float scale;
+    if ((double)angle <= 1e-3) {
+        const float a2 = angle * angle;
+        scale = 0.5f - a2 / 48.0f + a2 * a2 / 3840.0f;
+    } else {
+        scale = sinf(angle / 2.0f) / angle;
+    }
+    return Q4{scale * x, scale * y, scale * z, cosf(angle / 2.0f)};
+}
 // scipy Rotation.as_rotvec (_rotation.pyx) of Rotation.from_quat(q): normalise, w made >= 0, angle = 2 atan2(|xyz|, w), the Taylor series of
 // angle / sin(angle / 2) at angle <= 1e-3
 __device__ __forceinline__ V3 quat_to_rotvec_scipy(Q4 q) {

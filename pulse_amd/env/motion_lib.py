@@ -23,6 +23,11 @@ A third way in, one step earlier: ``from_smpl_data`` takes raw SMPL pose sequenc
 reference's scripts/data_process/convert_amass_data.py and convert_amass_isaac.py do with smpl_sim, scipy and poselib -- into the staging
 buffers ``load_motions`` reads; ``motion_data()`` hands the converted dict back.
 
+A fourth, for GENERATED motion: ``from_mdm_data`` takes a text-to-motion model's result (per-joint Euler angles in degrees, a root translation) and does
+what scripts/data_process/convert_data_mdm.py does -- Euler poses to rotation vectors (``pulse_motion_euler_pose``), the conversion above, then the sign
+correction along every clip and the Gaussian smoothing of rotations and root translation (``pulse_motion_smooth``, csrc/motion_smooth.hip);
+``from_smpl_data(..., smooth=True)`` applies the last step to raw SMPL clips.
+
 Same names and return keys as MotionLibBase: ``get_motion_state``, ``get_root_pos_smpl``, ``get_motion_length``,
 ``get_motion_num_steps``, ``sample_motions``, ``sample_time``, ``sample_time_interval``, ``num_motions``,
 ``get_total_length``; attributes ``_motion_lengths``, ``_motion_fps``, ``_motion_dt``, ``_motion_num_frames``,
@@ -140,6 +145,25 @@ def plan_smpl_clips(data, bounds=None, mirror=False, min_length=-1, im_eval=Fals
     order = filter_motion_data({c["key"]: {"pose_quat_global": range(c["frames"])} for c in clips}, min_length, im_eval)
     by_key = {c["key"]: c for c in clips}
     return [by_key[k] for k in order], dropped
+
+
+def plan_mdm_clips(result, min_length=-1, im_eval=False):
+    """What ``from_mdm_data`` will build, decided on the host: (clips, dropped keys, thetas, roots).  ``result``: {thetas: B sequences of (F, 24, 3) or
+    (F, 72), root_translation: B sequences of (F, 3)} (convert_data_mdm.py:48-51).  Sequence i becomes key str(i), 30 fps, skip 1, never mirrored;
+    ``plan_smpl_clips``' ten-frame minimum and selection apply.  thetas / roots: key -> float32 CPU tensor (F, 72) / (F, 3)."""
+    if not isinstance(result, dict) or "thetas" not in result or "root_translation" not in result:
+        raise KeyError("from_mdm_data: result needs 'thetas' and 'root_translation' (the json_file layout of the generator's output)")
+    if len(result["thetas"]) != len(result["root_translation"]):
+        raise ValueError(f"from_mdm_data: {len(result['thetas'])} thetas sequences but {len(result['root_translation'])} root_translation sequences")
+    thetas, roots, data = {}, {}, {}
+    for i in range(len(result["thetas"])):
+        th, tr = torch.as_tensor(result["thetas"][i]).to(torch.float32), torch.as_tensor(result["root_translation"][i]).to(torch.float32)
+        if not ((th.dim() == 3 and tuple(th.shape[1:]) == (24, 3)) or (th.dim() == 2 and th.shape[1] == 72)) or tuple(tr.shape) != (th.shape[0], 3):
+            raise ValueError(f"clip {str(i)!r}: thetas (F, 24, 3) or (F, 72) and root_translation (F, 3) expected, got {tuple(th.shape)} and {tuple(tr.shape)}")
+        thetas[str(i)], roots[str(i)] = th.reshape(th.shape[0], 72), tr
+        data[str(i)] = {"pose_aa": thetas[str(i)], "trans": tr, "beta": torch.zeros(10)}
+    clips, dropped = plan_smpl_clips(data, None, False, min_length, im_eval)
+    return clips, dropped, thetas, roots
 
 
 class MotionLib:
@@ -262,9 +286,27 @@ class MotionLib:
         self.load_motions(skeleton_trees, gender_betas, limb_weights)
         return self
 
+    @staticmethod
+    def _smooth_sigmas(smooth, upright_start, what):
+        """``smooth`` of from_smpl_data / from_mdm_data -> None or (sigma_rot, sigma_trans), refused by name where it cannot run."""
+        if smooth is None or smooth is False:
+            return None
+        if smooth is True:
+            smooth = {}
+        if not isinstance(smooth, dict) or set(smooth) - {"sigma_rot", "sigma_trans"}:
+            raise ValueError(f"{what}: smooth is None, True or a dict with sigma_rot / sigma_trans, got {smooth!r}")
+        if not upright_start:
+            raise ValueError(f"{what}: smooth requires upright_start=True: convert_data_mdm.py filters in that branch only (:125-141), its other branch does not run")
+        from .. import kernels
+        sigmas = (float(smooth.get("sigma_rot", 2.0)), float(smooth.get("sigma_trans", 3.0)))
+        for s in sigmas:
+            if s != 0.0:
+                kernels.gaussian_taps(s)                   # a negative sigma or more than 12 taps a side: refused here, before anything is staged
+        return sigmas
+
     @classmethod
     def from_smpl_data(cls, data, skeleton_trees, *, upright_start=True, mirror=False, bounds=None, root_offset=None, gender_betas=None,
-                       limb_weights=None, device="cuda:0", min_length=-1, im_eval=False, generator=None):
+                       limb_weights=None, device="cuda:0", min_length=-1, im_eval=False, generator=None, smooth=None):
         """A library over RAW SMPL pose sequences, as motion data sets ship them: ``data`` maps key -> {pose_aa | poses (F, >= 72) axis-angle in SMPL
         joint order, trans (F, 3), beta | betas, gender, [mocap_framerate]}, numpy or torch, fp32 or fp64.  What the reference's
         scripts/data_process/convert_amass_data.py:88-141 and convert_amass_isaac.py:85-137 do on the CPU first happens here in ONE launch of
@@ -281,13 +323,21 @@ class MotionLib:
             commented out; its live line (:119) reuses the key, so that the copy overwrites the original;
           * ``root_offset``: three floats added to ``trans`` (default: local_translation[0] of skeleton slot 0, :114);
           * ``upright_start=False`` leaves the (0.5, 0.5, 0.5, 0.5)^-1 factor out; the reference has no runnable counterpart (both scripts
-            hard-code True).
+            hard-code True);
+          * ``smooth``: None (default: nothing below happens, the staged bits are what they were), True or {"sigma_rot": 2, "sigma_trans": 3}:
+            what scripts/data_process/convert_data_mdm.py:128-141 does to generated motion after the conversion, in the three launches of
+            ``pulse_motion_smooth`` (csrc/motion_smooth.hip) -- quat_correct per body along every clip, gaussian_filter1d(sigma_rot,
+            mode="nearest") on the global quaternions and renormalisation, gaussian_filter1d(sigma_trans) on root_trans_offset.  A sigma of 0
+            leaves that filter out.  ``motion_data()`` then hands back the filtered pose_quat_global / root_trans_offset and pose_quat = the
+            local rotations of the clip's OWN filtered globals -- for a mirrored clip too, where the unsmoothed path keeps the unmirrored
+            clip's pose_quat; pose_aa and trans_orig stay unfiltered (:146-150).  Needs ``upright_start=True``.
         The humanoid is SMPL (24 bodies): SMPL-X / SMPL-H sources, reading .npz trees from disk and fix_trans_height are out of scope."""
         import warnings
         from .. import kernels, synthetic
         dev = torch.device(device)
         if dev.type != "cuda":
             raise ValueError("MotionLib lives in HBM (pulse_amd has no CPU path)")
+        sigmas = cls._smooth_sigmas(smooth, upright_start, "from_smpl_data")
         parents, lt = _parse_skeleton_trees(skeleton_trees)
         clips, dropped = plan_smpl_clips(data, bounds, mirror, min_length, im_eval)
         if dropped:
@@ -310,25 +360,79 @@ class MotionLib:
             src_start.append(sources[c["source"]])
         pose = torch.cat([_smpl_field(data[k], "pose_aa", "poses")[:, :72].to(torch.float32) for k in sources]).contiguous().to(dev)
         trans = torch.cat([torch.as_tensor(data[k]["trans"]).to(torch.float32) for k in sources]).contiguous().to(dev)
+        # beta: zeros of the input's length (a (1, n) row counts as n, convert_amass_isaac.py:62-64, 96)
+        beta_len = [int(_smpl_field(data[c["source"]], "beta", "betas").shape[-1]) for c in clips]
+        off = lt[0, 0].tolist() if root_offset is None else [float(v) for v in root_offset]
+        return self._ingest_staged(pose, trans, clips, src_start, beta_len, parents, upright_start, off, sigmas, im_eval, generator, skeleton_trees,
+                                   gender_betas, limb_weights)
+
+    def _ingest_staged(self, pose, trans, clips, src_start, beta_len, parents, upright_start, root_offset, sigmas, im_eval, generator, skeleton_trees,
+                       gender_betas, limb_weights):
+        """Staged SMPL pose rows -> the staging buffers of ``load_motions``: the ingest launch, the smoothing launches when ``sigmas`` is given
+        (ingest then writes scratch buffers: the filters read their neighbours' unfiltered values), ``_finish_staged``."""
+        from .. import kernels, synthetic
+        dev = self._device
         frames = torch.tensor([c["frames"] for c in clips], dtype=torch.int64)
         total, j = int(frames.sum()), len(parents)
         src = {"rot": torch.empty(total, j, 4, dtype=torch.float32, device=dev), "trans": torch.empty(total, 3, dtype=torch.float32, device=dev),
                "start": torch.cumsum(frames, 0) - frames, "frames": frames, "fps": torch.full((len(clips),), 30.0, dtype=torch.float64),
                "has_beta": torch.ones(len(clips), dtype=torch.bool)}              # the converted file always carries a (zeroed) beta
         self._smpl = {"pose_quat": torch.empty(total, j, 4, dtype=torch.float32, device=dev), "pose_aa": torch.empty(total, 72, dtype=torch.float32, device=dev),
-                      "trans_orig": torch.empty(total, 3, dtype=torch.float32, device=dev),
-                      # beta: zeros of the input's length (a (1, n) row counts as n, convert_amass_isaac.py:62-64, 96)
-                      "beta_len": [int(_smpl_field(data[c["source"]], "beta", "betas").shape[-1]) for c in clips]}
-        off = lt[0, 0].tolist() if root_offset is None else [float(v) for v in root_offset]
-        kernels.motion_ingest(src["rot"], src["trans"], src_pose=pose, src_trans=trans, clip_src_start=torch.tensor(src_start, dtype=torch.int64),
+                      "trans_orig": torch.empty(total, 3, dtype=torch.float32, device=dev), "beta_len": beta_len}
+        rot, rto = (src["rot"], src["trans"]) if sigmas is None else (torch.empty_like(src["rot"]), torch.empty_like(src["trans"]))
+        kernels.motion_ingest(rot, rto, src_pose=pose, src_trans=trans, clip_src_start=torch.tensor(src_start, dtype=torch.int64),
                               clip_skip=torch.tensor([c["skip"] for c in clips], dtype=torch.int64), clip_frames=frames, parents=parents,
-                              joint_map=joint_map, mirror_map=synthetic.mirror_body_map(), clip_mirror=torch.tensor([c["mirror"] for c in clips]),
-                              upright_start=upright_start, root_offset=off, out_pose_quat=self._smpl["pose_quat"], out_pose_aa=self._smpl["pose_aa"],
+                              joint_map=synthetic.smpl_joint_map(), mirror_map=synthetic.mirror_body_map(),
+                              clip_mirror=torch.tensor([c["mirror"] for c in clips]), upright_start=upright_start, root_offset=root_offset,
+                              out_pose_quat=self._smpl["pose_quat"] if sigmas is None else None, out_pose_aa=self._smpl["pose_aa"],
                               out_trans_orig=self._smpl["trans_orig"])
+        if sigmas is not None:
+            kernels.motion_smooth(src["rot"], src["trans"], in_rot=rot, in_trans=rto, clip_frames=frames, parents=parents, sigma_rot=sigmas[0],
+                                  sigma_trans=sigmas[1], out_pose_quat=self._smpl["pose_quat"])
         return self._finish_staged(src, j, im_eval, generator, skeleton_trees, gender_betas, limb_weights)
 
+    @classmethod
+    def from_mdm_data(cls, result, skeleton_trees, *, floor_height=0.92, smooth=True, root_offset=None, gender_betas=None, limb_weights=None,
+                      device="cuda:0", min_length=-1, im_eval=False, generator=None):
+        """A library over GENERATED motion, as a text-to-motion model (MDM) hands it back: ``result`` is the ``res_data["json_file"]`` layout
+        scripts/data_process/convert_data_mdm.py:48-51 reads -- ``thetas``: B sequences of (F, 24, 3) or (F, 72) per-joint Euler 'XYZ' angles in
+        DEGREES, SMPL joint order; ``root_translation``: B sequences of (F, 3), y up.  What the script does on the CPU happens here on the device:
+        one launch of ``pulse_motion_euler_pose`` (:48-61: angles -> rotation vectors, the root turned by +90 degrees about x, the translation
+        turned with it and its first frame set on ``floor_height``), the ``pulse_motion_ingest`` launch (:102-126) and, with ``smooth`` (True or
+        {"sigma_rot": 2, "sigma_trans": 3}; None leaves it out), the three launches of ``pulse_motion_smooth`` (:128-141, see ``from_smpl_data``).
+        Keys are "0", "1", ...; 30 fps, no decimation; beta is zeros(10) and gender "neutral" (:110); a sequence of fewer than 10 frames is
+        dropped with a warning that names it.  The remaining arguments are ``from_smpl_data``'s.  The transport to the model (the reference's
+        scripts/mdm_test.py) is the caller's."""
+        import warnings
+        from .. import kernels, synthetic
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("MotionLib lives in HBM (pulse_amd has no CPU path)")
+        sigmas = cls._smooth_sigmas(smooth, True, "from_mdm_data")
+        parents, lt = _parse_skeleton_trees(skeleton_trees)
+        if len(parents) != len(synthetic.smpl_joint_map()):
+            raise ValueError(f"from_mdm_data: the skeleton trees have {len(parents)} bodies, the SMPL humanoid {len(synthetic.smpl_joint_map())}")
+        clips, dropped, thetas, roots = plan_mdm_clips(result, min_length, im_eval)
+        if dropped:
+            warnings.warn(f"from_mdm_data: dropped {len(dropped)} clip(s) left with fewer than {SMPL_MIN_FRAMES} frames: {', '.join(map(str, dropped))}")
+        if not clips:
+            raise ValueError("from_mdm_data: no clip left" + (f" with at least {min_length} frames" if min_length != -1 else ""))
+        self = cls.__new__(cls)
+        self._device = dev
+        self._motion_data_keys = [c["key"] for c in clips]
+        self._num_unique_motions = len(clips)
+        frames = torch.tensor([c["frames"] for c in clips], dtype=torch.int64)
+        theta = torch.cat([thetas[c["key"]] for c in clips]).contiguous().to(dev)
+        raw = torch.cat([roots[c["key"]] for c in clips]).contiguous().to(dev)
+        pose, trans = torch.empty_like(theta), torch.empty_like(raw)
+        kernels.motion_euler_pose(pose, trans, src_theta=theta, src_trans=raw, clip_frames=frames, floor_height=floor_height)
+        off = lt[0, 0].tolist() if root_offset is None else [float(v) for v in root_offset]
+        src_start = (torch.cumsum(frames, 0) - frames).tolist()
+        return self._ingest_staged(pose, trans, clips, src_start, [10] * len(clips), parents, True, off, sigmas, im_eval, generator, skeleton_trees,
+                                   gender_betas, limb_weights)
+
     def motion_data(self):
-        """The converted motion data of a library built by ``from_smpl_data``, in the layout the reference's scripts dump (convert_amass_isaac.py:129-138)
+        """The converted motion data of a library built by ``from_smpl_data`` or ``from_mdm_data``, in the layout the reference's scripts dump (convert_amass_isaac.py:129-138)
         as CPU numpy arrays: key -> {pose_quat_global, pose_quat, trans_orig, root_trans_offset, beta (zeros of the input's length), gender "neutral",
         pose_aa, fps}.  A mirrored clip carries the unmirrored pose_quat / pose_aa / trans_orig, as the reference leaves them.
         ``from_motion_data(lib.motion_data(), ...)`` stages the same bits."""

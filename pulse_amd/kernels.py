@@ -4,6 +4,7 @@ Same rules as ``ops.py``: GPU tensors only, enqueue on torch's current stream, n
 """
 import ctypes
 import functools
+import math
 import os
 
 import torch
@@ -508,6 +509,110 @@ def motion_ingest(out_rot, out_trans, *, src_pose, src_trans, clip_src_start, cl
     a.upright_start, a.total_frames = int(bool(upright_start)), total
     a.root_offset[:] = [float(v) for v in root_offset]
     _launch("pulse_motion_ingest", ctypes.byref(a))
+    return out_rot, out_trans
+
+
+SMOOTH_MAX_RADIUS = 12
+# convert_data_mdm.py:54: Rotation.from_euler('xyz', [pi / 2, 0, 0]) as scipy holds it, xyzw
+MDM_ROOT_QUAT = (math.sin(math.pi / 4), 0.0, 0.0, math.cos(math.pi / 4))
+
+
+def gaussian_taps(sigma, radius=None):
+    """The weights of scipy's gaussian_filter1d(sigma) (scipy.ndimage._filters._gaussian_kernel1d, order 0) in double, |tap| = 0 .. radius;
+    ``radius`` defaults to gaussian_filter1d's int(4 sigma + 0.5).  More than SMOOTH_MAX_RADIUS taps a side are refused."""
+    import numpy as np
+    sigma = float(sigma)
+    if not math.isfinite(sigma) or sigma <= 0:
+        raise ValueError(f"gaussian_taps: sigma {sigma} is not a positive finite number")
+    radius = int(4.0 * sigma + 0.5) if radius is None else int(radius)
+    if radius < 0 or radius > SMOOTH_MAX_RADIUS:
+        raise ValueError(f"gaussian_taps: radius {radius} (sigma {sigma}) not in [0,{SMOOTH_MAX_RADIUS}]: pulse_motion_smooth holds {SMOOTH_MAX_RADIUS} taps a side")
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return [float(v) for v in phi[radius:]]
+
+
+def quat_matrix(q):
+    """scipy Rotation.as_matrix of a unit quaternion xyzw, row-major in double."""
+    x, y, z, w = (float(v) for v in q)
+    x2, y2, z2, w2 = x * x, y * y, z * z, w * w
+    xy, zw, xz, yw, yz, xw = x * y, z * w, x * z, y * w, y * z, x * w
+    return [x2 - y2 - z2 + w2, 2 * (xy - zw), 2 * (xz + yw), 2 * (xy + zw), -x2 + y2 - z2 + w2, 2 * (yz - xw), 2 * (xz - yw), 2 * (yz + xw),
+            -x2 - y2 + z2 + w2]
+
+
+def _clip_table(what, clip_frames, dev):
+    if not isinstance(clip_frames, torch.Tensor) or clip_frames.device.type != "cpu" or clip_frames.dtype != _I64 or not clip_frames.is_contiguous() \
+            or clip_frames.dim() != 1:
+        raise TypeError(f"{what}: clip_frames: contiguous (M) int64 CPU tensor expected (the launcher validates the clip table on the host)")
+    start = torch.cat([torch.zeros(1, dtype=_I64), torch.cumsum(clip_frames, 0)])
+    return start.to(dev), int(clip_frames.sum())
+
+
+def motion_euler_pose(out_pose, out_trans, *, src_theta, src_trans, clip_frames, floor_height=0.92, root_quat=MDM_ROOT_QUAT):
+    """pulse_motion_euler_pose: per-joint Euler 'XYZ' angles in degrees ``src_theta`` (T, 72) and ``src_trans`` (T, 3) of packed clips ->
+    ``out_pose`` (T, 72) axis-angle rows and ``out_trans`` (T, 3), the staging rows ``motion_ingest`` reads (include/pulse_hip.h section
+    2b'.1a).  Host: ``clip_frames`` (M) int64 CPU tensor."""
+    a = _lib.MotionEulerPoseArgs()
+    for name, t in (("src_theta", src_theta), ("src_trans", src_trans), ("out_pose", out_pose), ("out_trans", out_trans)):
+        ptr = _p(t, name, torch.float32)
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: contiguous tensor expected, got strides {tuple(t.stride())}")
+        setattr(a, name, ptr)
+    start, total = _clip_table("motion_euler_pose", clip_frames, out_pose.device)
+    for name, t, shape in (("src_theta", src_theta, (total, 72)), ("src_trans", src_trans, (total, 3)), ("out_pose", out_pose, (total, 72)),
+                           ("out_trans", out_trans, (total, 3))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+    a.total_frames, a.num_clips = total, clip_frames.numel()
+    a.clip_start, a.clip_frames_host = start.data_ptr(), clip_frames.data_ptr()
+    a.root_quat[:] = [float(v) for v in root_quat]
+    a.trans_matrix[:] = quat_matrix(root_quat)
+    a.floor_height = float(floor_height)
+    _launch("pulse_motion_euler_pose", ctypes.byref(a))
+    return out_pose, out_trans
+
+
+def motion_smooth(out_rot, out_trans, *, in_rot, in_trans, clip_frames, parents, sigma_rot=2.0, sigma_trans=3.0, out_pose_quat=None, sign_words=None):
+    """pulse_motion_smooth: quat_correct along every clip, gaussian_filter1d(sigma_rot) of the corrected globals ``in_rot`` (T, J, 4) and
+    renormalisation -> ``out_rot``, their local rotations -> ``out_pose_quat``, gaussian_filter1d(sigma_trans) of ``in_trans`` (T, 3) ->
+    ``out_trans`` (include/pulse_hip.h section 2b'.1a).  A sigma of 0 leaves that filter out.  Host: ``clip_frames`` (M) int64 CPU tensor,
+    ``parents`` J ints.  ``sign_words``: (T) int32 workspace, allocated here when not given.  No output may overlap an input."""
+    a = _lib.MotionSmoothArgs()
+    for name, t in (("in_rot", in_rot), ("in_trans", in_trans), ("out_rot", out_rot), ("out_trans", out_trans), ("out_pose_quat", out_pose_quat)):
+        ptr = _p(t, name, torch.float32)
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name}: contiguous tensor expected, got strides {tuple(t.stride())}")
+        setattr(a, name, ptr)
+    j = len(parents)
+    if j > INGEST_MAX_BODIES:
+        raise ValueError(f"motion_smooth: num_bodies {j} > {INGEST_MAX_BODIES} (one lane of a half-wave per body)")
+    start, total = _clip_table("motion_smooth", clip_frames, out_rot.device)
+    for name, t, shape in (("in_rot", in_rot, (total, j, 4)), ("in_trans", in_trans, (total, 3)), ("out_rot", out_rot, (total, j, 4)),
+                           ("out_trans", out_trans, (total, 3)), ("out_pose_quat", out_pose_quat, (total, j, 4))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+    for out_name, o, in_name, i in (("out_rot", out_rot, "in_rot", in_rot), ("out_pose_quat", out_pose_quat, "in_rot", in_rot),
+                                    ("out_pose_quat", out_pose_quat, "out_rot", out_rot), ("out_trans", out_trans, "in_trans", in_trans)):
+        if o is not None and o.data_ptr() < i.data_ptr() + i.numel() * 4 and i.data_ptr() < o.data_ptr() + o.numel() * 4:
+            raise ValueError(f"motion_smooth: {out_name} overlaps {in_name}: the filters read their neighbours' unfiltered values, no output may alias an input")
+    if sign_words is None:
+        sign_words = torch.empty(max(total, 1), dtype=torch.int32, device=out_rot.device)
+    if sign_words.dtype != torch.int32 or sign_words.numel() < total or not sign_words.is_contiguous():
+        raise ValueError(f"sign_words: contiguous int32 tensor of at least {total} words expected")
+    a.sign_words = _p(sign_words, "sign_words", torch.int32)
+    for which, sigma in (("rot", sigma_rot), ("trans", sigma_trans)):
+        if float(sigma) == 0.0:
+            setattr(a, "radius_" + which, -1)
+            continue
+        taps = gaussian_taps(sigma)
+        setattr(a, "radius_" + which, len(taps) - 1)
+        getattr(a, "w_" + which)[:len(taps)] = taps
+    par = (ctypes.c_int32 * j)(*[int(p) for p in parents])
+    a.total_frames, a.num_clips, a.num_bodies = total, clip_frames.numel(), j
+    a.clip_start, a.clip_frames_host, a.parent_indices_host = start.data_ptr(), clip_frames.data_ptr(), ctypes.cast(par, ctypes.c_void_p)
+    _launch("pulse_motion_smooth", ctypes.byref(a))
     return out_rot, out_trans
 
 

@@ -372,6 +372,44 @@ def synthetic_smpl_data(g, num_clips, frames=None, min_frames=45, max_frames=180
     return data, (list(SMPL_PARENTS), lt.contiguous())
 
 
+def synthetic_mdm_result(g, num_clips, frames=196, num_slots=None, jitter=0.0, spin=9.0):
+    """What a text-to-motion model hands back (the ``res_data["json_file"]`` layout scripts/data_process/convert_data_mdm.py:48-51 reads), and
+    skeleton trees to load it with: ``(result, (parents, local_translation (num_slots, 24, 3)))``.  ``result``: {thetas: ``num_clips`` arrays
+    (F, 24, 3) float32, per-joint Euler 'XYZ' angles in DEGREES in SMPL joint order; root_translation: ``num_clips`` arrays (F, 3) float32, y up}.
+    ``frames``: one length or one per clip (196 is what MDM emits).  Every clip turns the root about the vertical by about ``spin`` degrees
+    a frame, and swings one shoulder around a half turn: the rotation angle of the root and of that limb passes pi between consecutive
+    frames, where the rotation-vector representation wraps and the converted quaternions change sign.  ``jitter``: standard deviation in
+    degrees of white noise added to every angle (generated motion is jittery).  For ``MotionLib.from_mdm_data``."""
+    m = num_clips
+    lengths = [int(frames)] * m if not isinstance(frames, (list, tuple)) else [int(f) for f in frames]
+    if len(lengths) != m:
+        raise ValueError(f"synthetic_mdm_result: {m} clips need {m} lengths")
+    shoulder = SMPL_BONE_ORDER_NAMES.index("L_Shoulder")
+    thetas, roots = [], []
+    for c in range(m):
+        f = lengths[c]
+        t = torch.arange(f, dtype=torch.float32)[:, None, None] / 30.0
+        amp = 18.0 * _rand(g, 24, 3, 2)
+        frq = 0.3 + 1.7 * _rand(g, 24, 3, 2)
+        pha = 6.2831853 * _rand(g, 24, 3, 2)
+        e = (amp * torch.sin(6.2831853 * frq * t[..., None] + pha)).sum(-1)                     # (F, 24, 3) degrees
+        e[:, 0, 1] += 360.0 * _rand(g, 1) + (spin * (1.0 + 0.3 * _rand(g, 1))) * 30.0 * t[:, 0, 0]        # y is up before the script's +90 degrees about x
+        e[:, shoulder, 0] += 180.0 + 35.0 * torch.sin(6.2831853 * (1.5 + _rand(g, 1)) * t[:, 0, 0] + 6.2831853 * _rand(g, 1))
+        if jitter:
+            e = e + float(jitter) * _randn(g, f, 24, 3)
+        tt = t[:, 0]
+        root = (0.6 * _randn(g, 3) * torch.tensor([1.0, 0.0, 1.0])) * tt + 0.05 * _randn(g, 3) * torch.sin(3.0 * tt) + torch.tensor([0.0, 0.9, 0.0])
+        if jitter:
+            root = root + 0.002 * float(jitter) * _randn(g, f, 3)
+        thetas.append(e.contiguous().numpy())
+        roots.append(root.contiguous().numpy())
+    slots = m if num_slots is None else num_slots
+    offsets = 0.08 + 0.3 * _rand(g, 24, 3) * torch.tensor([0.4, 0.4, 1.0])
+    lt = offsets[None] * (1.0 + 0.1 * _randn(g, slots, 1, 1))
+    lt[:, 0] = 0.0
+    return {"thetas": thetas, "root_translation": roots}, (list(SMPL_PARENTS), lt.contiguous())
+
+
 # --------------------------------------------------------------------------- #
 # Action-dependent physics stand-in (return-parity experiments): constants shared by the HIP kernel's host class
 # (pulse_amd/env/sim.py:PdSim) and its CPU twin (oracle/pd_sim_oracle.py).  See include/pulse_hip.h: pulse_pd_sim_args.
