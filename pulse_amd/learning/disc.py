@@ -162,7 +162,9 @@ class DiscNetwork:
         # scratch whose ordered sum lands in slab 0 (slabs 1.. of these regions stay zero)
         def wide(A, B, M_, N_, lin, lda_note=None):
             tiles = t256(M_, N_)
-            split = 1
+            # at least two splits: an unsplit single-plane launch hands its output on rounded to bf16 (the autocast Linear's output), and a
+            # weight gradient is an fp32 sum at every batch size (b <= 47 used to get a W2 gradient rounded to bf16, b >= 48 an unrounded one)
+            split = 2
             while tiles * split < 256 and split < 64 and m // (2 * split) >= 96:
                 split *= 2
             count = lin.rows * lin.pitch
