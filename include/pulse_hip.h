@@ -728,7 +728,18 @@ int pulse_keypoint_push(const pulse_keypoint_push_args* args, pulse_stream_t s);
  *        accum[2] += mean_j |a P~_j R + t - G~_j|                                    mpjpe_pa: P~, G~ root-relative, (a, R, t) the similarity
  *                    Procrustes fit of the common p_mpjpe with X = G~ (target), Y = P~ (predicted): centre both, divide each by its
  *                    Frobenius norm, H = X0^T Y0 = U S V^T, R = V U^T (last column of V and last singular value flipped when
- *                    det R < 0), a = tr(S) |X| / |Y|, t = mu_X - a mu_Y R.  The SVD is a fixed-sweep one-sided Jacobi.
+ *                    det R < 0), a = tr(S) |X| / |Y|, t = mu_X - a mu_Y R.  The SVD is a fixed-sweep one-sided Jacobi.  U and V are
+ *                    full orthonormal matrices whatever the rank of H, as LAPACK's are, so R is a rotation for every input; a
+ *                    singular value at or below 1e-13 of the largest counts as zero, adds nothing to tr(S), and its column of U
+ *                    is completed from the others so that det R = + 1.  By the rank of H:
+ *                      3  as above.
+ *                      2  (either cloud planar, or J = 3) R is fixed by the two planes: the part of P~ out of its plane is turned
+ *                         onto the normal of G~'s plane with the rest, not dropped.  The value is as determined as for rank 3.
+ *                      1  (either cloud on a line, or J = 2) R turns v_1 onto u_1; the turn about u_1 is the completion's choice
+ *                         (u_2 = u_1 x e / |u_1 x e|, e the coordinate axis furthest from u_1, u_3 = u_1 x u_2).  The value does
+ *                         not depend on that choice when one of the clouds does lie on a line: a turn about the line moves no distance to it.
+ *                      0  (a cloud collapsed to one point, or J = 1) tr(S) = 0, so a = 0 and every body is aligned onto mu_X: the
+ *                         term is mean_j |mu_X - G~_j|, finite, and 0 when G~ is the collapsed one.
  *        accum[3] += mean_j |(P_t - P_t-1) - (G_t - G_t-1)|                          vel_dist, steps >= 1
  *        accum[4] += mean_j |(P_t - 2 P_t-1 + P_t-2) - (G_t - 2 G_t-1 + G_t-2)|      accel_dist, steps >= 2
  *        accum[5], [6], [7] += 1                                                     frames counted for [0..2], [3], [4]

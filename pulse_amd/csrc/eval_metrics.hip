@@ -18,9 +18,16 @@ constexpr int kEvalThreads = 128;
 __device__ __forceinline__ double norm3(double x, double y, double z) { return sqrt(x * x + y * y + z * z); }
 
 // One-sided (Hestenes) Jacobi on the columns of the 3 x 3 matrix A: A V = U Sigma, V a product of plane rotations (det + 1).  Columns
-// are rotated in place until mutually orthogonal; a fixed number of sweeps (convergence is quadratic: a well-conditioned 3 x 3 settles
-// to the last bit in 4 - 6).  Afterwards sigma_i = |A[:, i]| and U[:, i] = A[:, i] / sigma_i, in no particular order.
+// are rotated in place until mutually orthogonal; a fixed number of sweeps.  Convergence is quadratic: in an fp64 port of this loop every
+// H of tests/eval_metrics_cases.py, rank-deficient ones included, stopped moving by more than 1e-15 after 2 - 4 sweeps (one took 8).  The
+// skip test below asks for more than rounding leaves of a full-rank H, so the later sweeps go on turning by angles of about 1e-17, which
+// moves nothing.  Afterwards sigma_i = |A[:, i]| and U[:, i] = A[:, i] / sigma_i, in no particular order; the column of a zero singular
+// value ends as zero or as a remnant far below kRankTol, wherever the squares underflowed.
 constexpr int kJacobiSweeps = 12;
+// A column of U Sigma this much shorter than the longest is not normalised but completed (im_eval_accum_kernel).  The sums of up to 64 products
+// that build H (|H| <= 1) carry about 8 eps = 2e-15 of rounding, which is the size a zero singular value comes out at; 1e-13 is well above
+// that, and a true singular value below it changes the trace, and so the scale, by less than 1e-13 of itself.
+constexpr double kRankTol = 1e-13;
 __device__ __forceinline__ void jacobi_svd3(double A[3][3], double V[3][3]) {
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -115,26 +122,74 @@ __global__ void __launch_bounds__(kEvalThreads) im_eval_accum_kernel(const pulse
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int k = 0; k < 3; ++k) H[i][k] = lane_sum<LB>(X0[i] * Y0[k]);
-    const double detH = H[0][0] * (H[1][1] * H[2][2] - H[1][2] * H[2][1]) - H[0][1] * (H[1][0] * H[2][2] - H[1][2] * H[2][0]) +
-                        H[0][2] * (H[1][0] * H[2][1] - H[1][1] * H[2][0]);
     jacobi_svd3(H, V);                                        // H now holds U Sigma, column by column
     double sig[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) sig[i] = norm3(H[0][i], H[1][i], H[2][i]);
-    // det(V U^T) = det(U) = sign(det H) (det V = + 1): a reflection flips the column of the SMALLEST singular value (numpy's last)
+    // U: the columns that can be normalised.  One shorter than kRankTol of the longest is what rounding left of a zero singular value: its
+    // direction means nothing (dividing it by its length gave a unit vector INSIDE the span of the others), and LAPACK, which the
+    // definition rests on, returns an orthonormal U whatever the rank.  So the missing columns are completed (det U = + 1), add nothing to
+    // the trace, and R = V D U^T is a rotation for every H: rank 2 fixes it (the out-of-plane part of the other cloud is turned with the
+    // rest, not dropped), rank 1 fixes how v_1 goes onto u_1 and leaves the turn about u_1 to the completion, rank 0 gives R = V.
+    const double smax = fmax(sig[0], fmax(sig[1], sig[2]));
+    bool keep[3];
+    double U[3][3];
+    int kept = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        keep[i] = sig[i] > kRankTol * smax;
+        kept += keep[i] ? 1 : 0;
+        const double w = keep[i] ? 1.0 / sig[i] : 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) U[c][i] = H[c][i] * w;
+    }
+    if (kept < 3) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {                          // k: the only kept column (rank 1); its two successors are built from it
+            if (!(kept == 1 && keep[k])) continue;
+            const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+            const double a0 = fabs(U[0][k]), a1 = fabs(U[1][k]), a2 = fabs(U[2][k]);
+            const int ax = (a0 <= a1 && a0 <= a2) ? 0 : (a1 <= a2 ? 1 : 2);                  // the coordinate axis furthest from u_k
+            const double ex = ax == 0 ? 1.0 : 0.0, ey = ax == 1 ? 1.0 : 0.0, ez = ax == 2 ? 1.0 : 0.0;
+            double t[3] = {U[1][k] * ez - U[2][k] * ey, U[2][k] * ex - U[0][k] * ez, U[0][k] * ey - U[1][k] * ex};
+            const double it = 1.0 / norm3(t[0], t[1], t[2]);                                 // |u_k x e| >= sqrt(2 / 3)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) U[c][k1] = t[c] * it;
+            U[0][k2] = U[1][k] * U[2][k1] - U[2][k] * U[1][k1];
+            U[1][k2] = U[2][k] * U[0][k1] - U[0][k] * U[2][k1];
+            U[2][k2] = U[0][k] * U[1][k1] - U[1][k] * U[0][k1];
+        }
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {                          // m: the only missing column (rank 2) = the cross product of its two successors
+            if (!(kept == 2 && !keep[m])) continue;
+            const int m1 = (m + 1) % 3, m2 = (m + 2) % 3;
+            U[0][m] = U[1][m1] * U[2][m2] - U[2][m1] * U[1][m2];
+            U[1][m] = U[2][m1] * U[0][m2] - U[0][m1] * U[2][m2];
+            U[2][m] = U[0][m1] * U[1][m2] - U[1][m1] * U[0][m2];
+        }
+        if (kept == 0) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) U[c][i] = (c == i) ? 1.0 : 0.0;
+        }
+    }
+    // det(V U^T) = det U (det V = + 1; + 1 for a completed U): a reflection flips the column of the SMALLEST singular value (numpy's last).
+    // The sign is taken from the orthonormal U, where it is + 1 or - 1 to rounding, not from det H, which is all rounding once H is near singular
+    const double detU = U[0][0] * (U[1][1] * U[2][2] - U[1][2] * U[2][1]) - U[0][1] * (U[1][0] * U[2][2] - U[1][2] * U[2][0]) +
+                        U[0][2] * (U[1][0] * U[2][1] - U[1][1] * U[2][0]);
     int kmin = 0;
     if (sig[1] < sig[kmin]) kmin = 1;
     if (sig[2] < sig[kmin]) kmin = 2;
     double R[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, tr = 0.0;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        const double d = (detH < 0.0 && i == kmin) ? -1.0 : 1.0;
-        tr += d * sig[i];
-        const double w = sig[i] > 0.0 ? d / sig[i] : 0.0;
+        const double d = (detU < 0.0 && i == kmin) ? -1.0 : 1.0;
+        tr += keep[i] ? d * sig[i] : 0.0;
 #pragma unroll
         for (int r = 0; r < 3; ++r)
 #pragma unroll
-            for (int c = 0; c < 3; ++c) R[r][c] += V[r][i] * (H[c][i] * w);          // R = V D U^T
+            for (int c = 0; c < 3; ++c) R[r][c] += V[r][i] * (d * U[c][i]);          // R = V D U^T
     }
     const double scale = tr * normX * invY;
     double tvec[3], al[3];

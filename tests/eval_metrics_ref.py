@@ -3,9 +3,10 @@
 import numpy as np
 
 
-def procrustes(pred, gt):
+def procrustes_fit(pred, gt):
     """The similarity Procrustes fit of the common p_mpjpe (predicted aligned onto target) for one frame: pred, gt (J, 3) float64.
-    Returns the aligned prediction and H (for the conditioning check)."""
+    Returns (a, r, t, H): a * pred @ r + t is the aligned prediction.  LAPACK returns full orthonormal U and V whatever the rank of H,
+    so r is a rotation also where H has a zero singular value (tests/test_eval_metrics_edges_cpu.py)."""
     mu_x, mu_y = gt.mean(0, keepdims=True), pred.mean(0, keepdims=True)
     x0, y0 = gt - mu_x, pred - mu_y
     norm_x, norm_y = np.sqrt((x0 ** 2).sum()), np.sqrt((y0 ** 2).sum())
@@ -20,16 +21,26 @@ def procrustes(pred, gt):
         r = v @ u.T
     a = s.sum() * norm_x / norm_y
     t = mu_x - a * mu_y @ r
+    return a, r, t, h
+
+
+def procrustes(pred, gt):
+    """The aligned prediction of procrustes_fit and H (for the conditioning check)."""
+    a, r, t, h = procrustes_fit(pred, gt)
     return a * pred @ r + t, h
 
 
-def step_terms(pred, gt):
-    """pred, gt (T, J, 3) float64 -> dict of per-frame terms in mm: mpjpe_g / mpjpe_l / mpjpe_pa (T,), vel_dist (T - 1,), accel_dist (T - 2,)."""
+def step_terms(pred, gt, pa=True):
+    """pred, gt (T, J, 3) float64 -> dict of per-frame terms in mm: mpjpe_g / mpjpe_l / mpjpe_pa (T,), vel_dist (T - 1,), accel_dist (T - 2,).
+    pa=False leaves the fit out (mpjpe_pa is NaN): for clouds on which it divides 0 / 0 or its rotation is arbitrary."""
     t = pred.shape[0]
     out = {"mpjpe_g": np.linalg.norm(pred - gt, axis=-1).mean(-1) * 1000.0}
     pl, gl = pred - pred[:, :1], gt - gt[:, :1]
     out["mpjpe_l"] = np.linalg.norm(pl - gl, axis=-1).mean(-1) * 1000.0
-    out["mpjpe_pa"] = np.array([np.linalg.norm(procrustes(pl[i], gl[i])[0] - gl[i], axis=-1).mean() for i in range(t)]).reshape(t) * 1000.0
+    if pa:
+        out["mpjpe_pa"] = np.array([np.linalg.norm(procrustes(pl[i], gl[i])[0] - gl[i], axis=-1).mean() for i in range(t)]).reshape(t) * 1000.0
+    else:
+        out["mpjpe_pa"] = np.full(t, np.nan)
     dv = (pred[1:] - pred[:-1]) - (gt[1:] - gt[:-1]) if t >= 2 else np.zeros((0,) + pred.shape[1:])
     da = (pred[2:] - 2 * pred[1:-1] + pred[:-2]) - (gt[2:] - 2 * gt[1:-1] + gt[:-2]) if t >= 3 else np.zeros((0,) + pred.shape[1:])
     out["vel_dist"] = np.linalg.norm(dv, axis=-1).mean(-1) * 1000.0
@@ -37,9 +48,9 @@ def step_terms(pred, gt):
     return out
 
 
-def accumulator_row(pred, gt):
+def accumulator_row(pred, gt, pa=True):
     """The (8,) row the kernel holds after the counted frames pred / gt (T, J, 3) of one env: five sums and three frame counts."""
-    m = step_terms(np.asarray(pred, np.float64), np.asarray(gt, np.float64))
+    m = step_terms(np.asarray(pred, np.float64), np.asarray(gt, np.float64), pa)
     return np.array([m["mpjpe_g"].sum(), m["mpjpe_l"].sum(), m["mpjpe_pa"].sum(), m["vel_dist"].sum(), m["accel_dist"].sum(),
                      len(m["mpjpe_g"]), len(m["vel_dist"]), len(m["accel_dist"])], dtype=np.float64)
 
