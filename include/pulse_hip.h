@@ -1154,6 +1154,7 @@ int pulse_split_planes(const float* in, int64_t ld_in, int32_t rows_out, int32_t
 /* ------------------------------------------------------------------------- *
  * 4d. Glue of the bf16-STORAGE training path (mixed_precision: the reference wraps calc_gradients in autocast, amp_agent.py:671,
  *     common_agent.py:426,461): activations, gradients and per-step weight copies are bf16 matrices feeding pulse_gemm_x3p(planes = 1).
+ *     csrc/b16_ops.hip; the discriminator's pulse_disc_penalty / _reg / _reward: csrc/disc_ops.hip.
  * ------------------------------------------------------------------------- */
 /* out[z][c][r] = bf16(in[z][r][c]) for z < batch: W[out][in] -> W^T[in][out], so an input-gradient GEMM (nn.Linear backward,
  * network_builder.py:105-124) reads both operands reduction-contiguous.  Columns [rows_in, ld_out) of the output rows are not written
@@ -1348,7 +1349,8 @@ int pulse_colsum_partial(const float* x, int32_t m, int32_t n, int32_t ld, int32
                          int64_t ld_partial, pulse_stream_t s);
 
 /* ------------------------------------------------------------------------- *
- * 5. Learner-side elementwise / reduction kernels (PPO update).
+ * 5. Learner-side elementwise / reduction kernels (PPO update).  By subject: csrc/rms_normalize.hip (pulse_rms_*), policy_ops.hip
+ *    (policy_sample, ppo_loss, advantage_*), optim_ops.hip (sqnorm_partial, adam_step*), disc_ops.hip (disc_head*); formulas in learner_math.h.
  * ------------------------------------------------------------------------- */
 /* RunningMeanStd.forward, phc/utils/running_mean_std.py:69-109.
  *   mode 0: y = clamp((x - mean) / sqrt(var + eps), -clip, clip);  mode 1 (unnorm): y = sqrt(var+eps)*clamp(x)+mean.

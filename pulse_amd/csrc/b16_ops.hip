@@ -5,11 +5,7 @@
 //   transpose_to_b16     fp32 W[out][in] -> bf16 W^T[in][out] once per optimiser step, so every input-gradient GEMM runs in the forward
 //                        (both operands reduction-contiguous) form                       (nn.Linear backward, network_builder.py:105-124)
 //   colsum_partial_b16   bias gradients = column sums of a bf16 gradient matrix          (same call sites as pulse_colsum_partial)
-//   disc_penalty         AMPAgent._disc_loss gradient penalty (amp_agent.py:925-934): sum ||dD/dx||^2 partials + the scaled gradient dg
-//                        that starts the penalty's backward pass, as fp32 and / or bf16
-//   disc_reg             disc_logit_reg / disc_weight_decay gradient terms (amp_agent.py:919-923, 936-940): grad += alpha * w over up to
-//                        four parameter ranges, with the ranges' sums of squares for the reported loss
-//   disc_reward          AMPAgent._calc_disc_rewards (amp_agent.py:1027-1041): -log(max(1 - sigmoid(logit), 1e-4)) * scale
+//   reduce_grads         the slab reduce of a whole gradient buffer with the regularisers' terms and the gradient norm's partials
 #include "common.h"
 
 namespace pulse {
@@ -158,68 +154,6 @@ __global__ void __launch_bounds__(256) colsum_partial_b16_kernel(const unsigned 
     }
 }
 
-// dg = scale * G (fp32 and / or bf16), partials[block] = sum of G^2 over the block's elements.  G is (rows, ld) with its pad columns zero.
-__global__ void __launch_bounds__(256) disc_penalty_kernel(const float* __restrict__ G, long long ldg, int rows, int cols4, float scale,
-                                                          float* __restrict__ out32, long long ld32, unsigned short* __restrict__ out16, long long ld16,
-                                                          float* __restrict__ partials) {
-    __shared__ float red[4];
-    float acc = 0.f;
-    const long long total = (long long)rows * cols4;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const int r = (int)(i / cols4), c = (int)(i - (long long)r * cols4) * 4;
-        const float4 v = *reinterpret_cast<const float4*>(G + (long long)r * ldg + c);
-        acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-        const float a = v.x * scale, b = v.y * scale, cc = v.z * scale, d = v.w * scale;
-        if (out32) *reinterpret_cast<float4*>(out32 + (long long)r * ld32 + c) = make_float4(a, b, cc, d);
-        if (out16) *reinterpret_cast<uint2*>(out16 + (long long)r * ld16 + c) = make_uint2(split_pack_rn(a, b), split_pack_rn(cc, d));
-    }
-    acc = lane_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-struct DiscRegArgs { long long off[4]; long long len[4]; float alpha[4]; int n; };
-
-// grad[off_r + i] += alpha_r * flat[off_r + i];  partials[block * 4 + r] = sum over the block's share of flat[range r]^2
-__global__ void __launch_bounds__(256) disc_reg_kernel(const float* __restrict__ flat, float* __restrict__ grad, const DiscRegArgs a, float* __restrict__ partials) {
-    __shared__ float red[4][4];
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        if (r >= a.n) break;
-        const float* w = flat + a.off[r];
-        float* g = grad ? grad + a.off[r] : nullptr;
-        const float al = a.alpha[r];
-        if (((a.off[r] | a.len[r]) & 3) == 0) {                          // 16-byte path (every weight matrix of a ParamBook)
-            const long long n4 = a.len[r] >> 2;
-            const bool upd = g && al != 0.f;
-            for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-                const float4 v = reinterpret_cast<const float4*>(w)[i];
-                acc[r] += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-                if (upd) {
-                    float4 t = reinterpret_cast<float4*>(g)[i];
-                    t.x += al * v.x; t.y += al * v.y; t.z += al * v.z; t.w += al * v.w;
-                    reinterpret_cast<float4*>(g)[i] = t;
-                }
-            }
-            continue;
-        }
-        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.len[r]; i += (long long)gridDim.x * 256) {
-            const float v = w[i];
-            acc[r] += v * v;
-            if (g && al != 0.f) g[i] += al * v;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        acc[r] = lane_sum(acc[r]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][r] = acc[r];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) partials[blockIdx.x * 4 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-}
-
 // out[off_r + i] = scale * sum_{s < nslabs_r} slabs[s * stride + off_r + i] (+ alpha_r * flat[off_r + i]) over up to 8 regions of a flat
 // gradient buffer, each with its own slab count (a weight-gradient launch that split its reduction 4 ways wrote 4 slabs: the other slabs of
 // that region are never read); sq_partials[block] = the block's share of sum out^2 (the gradient-norm clip needs it: no separate pass over
@@ -323,14 +257,6 @@ __global__ void __launch_bounds__(256) reduce_grads_kernel(const float* __restri
     }
 }
 
-__global__ void __launch_bounds__(256) disc_reward_kernel(const float* __restrict__ logits, long long ls, long long n, float scale, float* __restrict__ out, long long os) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float x = logits[i * ls];
-    const float prob = 1.f / (1.f + expf(-x));                          // the reference's op sequence, op for op (amp_agent.py:1033-1038)
-    out[i * os] = -logf(fmaxf(1.f - prob, 0.0001f)) * scale;
-}
-
 }  // namespace pulse
 
 using namespace pulse;
@@ -419,34 +345,6 @@ int pulse_colsum_weighted_b16(const void* x, int32_t m, int32_t n, int64_t ld, c
     return colsum_b16_launch("pulse_colsum_weighted_b16", x, m, n, ld, w, w_stride, num_chunks, partial, ld_partial, s);
 }
 
-int pulse_disc_penalty(const float* g, int64_t ldg, int32_t rows, int32_t cols, float scale, float* out32, int64_t ld32, void* out16, int64_t ld16,
-                       float* partials, int32_t num_blocks, pulse_stream_t s) {
-    PULSE_REQUIRE(rows >= 1 && cols >= 1 && num_blocks >= 1, "pulse_disc_penalty: bad sizes");
-    PULSE_REQUIRE(g && partials, "pulse_disc_penalty: null pointer");
-    PULSE_REQUIRE((cols % 4) == 0 && (ldg % 4) == 0 && ldg >= cols && (reinterpret_cast<uintptr_t>(g) & 15) == 0,
-                  "pulse_disc_penalty: cols / pitch must be multiples of 4 floats (the pad columns of G are zero and are processed with it)");
-    PULSE_REQUIRE(!out32 || ((ld32 % 4) == 0 && ld32 >= cols && (reinterpret_cast<uintptr_t>(out32) & 15) == 0), "pulse_disc_penalty: fp32 output rows must be 16-byte aligned");
-    PULSE_REQUIRE(!out16 || ((ld16 % 4) == 0 && ld16 >= cols && (reinterpret_cast<uintptr_t>(out16) & 7) == 0), "pulse_disc_penalty: bf16 output rows must be 8-byte aligned");
-    hipLaunchKernelGGL(disc_penalty_kernel, dim3((unsigned)num_blocks), dim3(256), 0, as_stream(s), g, (long long)ldg, rows, cols / 4, scale, out32,
-                       (long long)ld32, reinterpret_cast<unsigned short*>(out16), (long long)ld16, partials);
-    return check_launch("pulse_disc_penalty");
-}
-
-int pulse_disc_reg(const float* flat, float* grad, int32_t num_ranges, const int64_t* offsets, const int64_t* lengths, const float* alphas,
-                   float* partials, int32_t num_blocks, pulse_stream_t s) {
-    PULSE_REQUIRE(num_ranges >= 1 && num_ranges <= 4 && num_blocks >= 1, "pulse_disc_reg: 1..4 ranges");
-    PULSE_REQUIRE(flat && offsets && lengths && alphas && partials, "pulse_disc_reg: null pointer");
-    PULSE_REQUIRE((reinterpret_cast<uintptr_t>(flat) & 15) == 0 && (!grad || (reinterpret_cast<uintptr_t>(grad) & 15) == 0), "pulse_disc_reg: flat / grad must be 16-byte aligned");
-    DiscRegArgs a;
-    a.n = num_ranges;
-    for (int r = 0; r < 4; ++r) {
-        a.off[r] = r < num_ranges ? offsets[r] : 0; a.len[r] = r < num_ranges ? lengths[r] : 0; a.alpha[r] = r < num_ranges ? alphas[r] : 0.f;
-        PULSE_REQUIRE(a.off[r] >= 0 && a.len[r] >= 0, "pulse_disc_reg: negative range");
-    }
-    hipLaunchKernelGGL(disc_reg_kernel, dim3((unsigned)num_blocks), dim3(256), 0, as_stream(s), flat, grad, a, partials);
-    return check_launch("pulse_disc_reg");
-}
-
 int pulse_reduce_grads(const float* slabs, int64_t slab_stride, int32_t num_regions, const int64_t* offsets, const int64_t* counts, const int32_t* nslabs,
                        const float* alphas, const float* const* region_src, const int64_t* region_src_stride, float* out, float scale, const float* flat,
                        float* sq_partials, float* w2_partials, int32_t num_blocks, pulse_stream_t s) {
@@ -469,14 +367,5 @@ int pulse_reduce_grads(const float* slabs, int64_t slab_stride, int32_t num_regi
     hipLaunchKernelGGL(reduce_grads_kernel, dim3((unsigned)num_blocks), dim3(256), 0, as_stream(s), slabs, (long long)slab_stride, rg, out, scale, flat,
                        sq_partials, w2_partials);
     return check_launch("pulse_reduce_grads");
-}
-
-int pulse_disc_reward(const float* logits, int64_t logit_stride, int64_t n, float scale, float* out, int64_t out_stride, pulse_stream_t s) {
-    PULSE_REQUIRE(n >= 0, "pulse_disc_reward: negative size");
-    if (n == 0) return PULSE_OK;
-    PULSE_REQUIRE(logits && out && logit_stride >= 1 && out_stride >= 1, "pulse_disc_reward: bad arguments");
-    hipLaunchKernelGGL(disc_reward_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(s), logits, (long long)logit_stride, (long long)n, scale, out,
-                       (long long)out_stride);
-    return check_launch("pulse_disc_reward");
 }
 }

@@ -62,7 +62,10 @@ SOURCES = [
     ("gemm_x3w.hip", ["-mllvm", "-pragma-unroll-threshold=4000000", "-Wno-unused-const-variable"]),
     # the skinny-N x3 kernel: one wave per SIMD with plenty of registers (a phase of raw A + B staging units in flight)
     ("gemm_x3s.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form"]),
-    ("learner_ops.hip", NO_CONTRACT),
+    ("rms_normalize.hip", NO_CONTRACT),
+    ("policy_ops.hip", NO_CONTRACT),
+    ("optim_ops.hip", NO_CONTRACT),
+    ("disc_ops.hip", NO_CONTRACT),
     ("b16_ops.hip", NO_CONTRACT),
     ("vae_head.hip", NO_CONTRACT),
     ("mcp.hip", NO_CONTRACT),

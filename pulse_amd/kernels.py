@@ -919,6 +919,7 @@ def colsum_partial(x, m, n, ld, num_chunks, partial, ld_partial, x_off=0, partia
 
 def rms_copy_supported(x, cols, y, y_cols, raw_out):
     """Can ``rms_normalize(..., raw_out=raw_out)`` run (pulse_rms_normalize_copy's wide-row form)?  Decided by the caller once per buffer set."""
+    # the Python mirror of rms_wide_rows(c, 16) in csrc/rms_normalize.hip, plus _copy's own raw_out check: change the two together
     ok = lambda t: t is not None and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
     c4 = (cols + 3) // 4 * 4
     return bool(ok(x) and ok(y) and ok(raw_out) and 64 <= cols and y_cols <= 3072 and y_cols % 4 == 0 and y_cols >= cols and x.stride(0) >= c4 and

@@ -1,4 +1,4 @@
-"""GPU: the glue kernels of the bf16-storage training path (include/pulse_hip.h 4d, csrc/b16_ops.hip + the bf16 outputs of the normaliser,
+"""GPU: the glue kernels of the bf16-storage training path (include/pulse_hip.h 4d, csrc/b16_ops.hip, csrc/disc_ops.hip + the bf16 outputs of the normaliser,
 the PPO loss and the discriminator head) against plain torch on the same inputs; then the two networks trained on bf16 storage against
 the SAME networks on the fp32-storage bf16 kernel (identical arithmetic -- operands rounded to bf16, fp32 accumulation, bf16-rounded
 outputs -- so the two paths may differ by accumulation order only)."""
